@@ -22,6 +22,9 @@ Printed JSON (rank 0, one line): the contract fields plus
   exact_bf16x3  (default run, N=1) the same workload with the exact operand form of rounds 3-4 -- bf16 triples, six partial
                 products instead of the three of the scaled fp16 pairs `value` is measured with -- from a subprocess with
                 HPL_MATH=bf16x3 after this run's timed regions: both arithmetics in one line.
+
+`--dump-outputs DIR` writes the output of the last timed step (the flow; with --train also a seeded sample of the updated
+parameters) as DIR/<name>.npy.  Inputs and weights are seeded, so two builds run with the same arguments compare file by file.
 """
 import argparse
 import json
@@ -613,6 +616,33 @@ def emit(full, detail_path):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+NPY_HEADER = 128                 # bytes ahead of the data in a .npy file of up to 4-d shape
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """Write {name: array} as dirname/<name>.npy in float32 / float64.  An array that would take the files past `limit` bytes in
+    all is replaced by a fixed sample of its flattened entries (seeded, so two runs pick the same ones) stored under
+    <name>_sample.npy, with the flat indices of the sample in <name>_sample_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    written, used = [], 0
+    for i, (name, x) in enumerate(arrays.items()):
+        x = np.ascontiguousarray(x)
+        if x.dtype != np.float64:
+            x = x.astype(np.float32)
+        room = (limit - used) // max(1, len(arrays) - i) - 2 * NPY_HEADER     # an even share of what is left for this and the later arrays
+        if x.nbytes > room:
+            k = max(1, min(x.size, room // (x.itemsize + 8)))
+            idx = np.sort(np.random.RandomState(1234).choice(x.size, k, replace=False)).astype(np.int64)
+            x = x.reshape(-1)[idx]
+            np.save(os.path.join(dirname, name + '_sample_index.npy'), idx.astype(np.float64))
+            name, used = name + '_sample', used + idx.nbytes + NPY_HEADER
+        np.save(os.path.join(dirname, name + '.npy'), x)
+        written.append(name)
+        used += x.nbytes + NPY_HEADER
+    return written
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a torchrun environment: start N ranks of this same command line, one per visible
     GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as torchrun would set them, rendezvous on 127.0.0.1 at a free port), pass
@@ -697,6 +727,10 @@ def main():
     ap.add_argument('--detail', default=os.path.join(ROOT, DETAIL_FILE),
                     help='where rank 0 writes the full record (per-class kernel tables, notes, power, host timings); the ONE stdout '
                          'line carries the contract fields and stays below %d bytes; empty: no file' % LINE_LIMIT)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='rank 0 writes what the last timed step computed as DIR/<name>.npy (float32): the flow (1, 3, N); with '
+                         '--train also a seeded sample of the updated parameters.  Inputs and weights are seeded, so two builds '
+                         'run with the same arguments can be compared file by file')
     a = ap.parse_args()
 
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -906,6 +940,13 @@ def main():
         elapsed = time.perf_counter() - t0
         rank_elapsed = elapsed
         timers.enabled = False
+        dumped = None
+        if a.dump_outputs and rank == 0:
+            # the timed path's last step as its caller receives it (copied off the device outside the timed region)
+            outs = {'flow': y.detach().float().cpu().numpy()}
+            if a.train:
+                outs['params'] = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()]).cpu().numpy()
+            dumped = dump_outputs(a.dump_outputs, outs)
         native_prof = None
         if plan is not None:
             plan.profile(-1)
@@ -1287,6 +1328,8 @@ def main():
             raise SystemExit('bench.py: %d of %d ranks reported (--gpus %d): not printing a line for a job of another size'
                              % (line['ranks']['ranks_seen'], line['n_gpus'], a.gpus))
         line['dominant_class'] = dominant
+        if dumped:
+            line['dumped_outputs'] = {'dir': os.path.abspath(a.dump_outputs), 'files': dumped}
         emit(line, a.detail)
     if world > 1:
         torch.distributed.destroy_process_group()

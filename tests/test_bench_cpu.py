@@ -134,3 +134,21 @@ def test_split3_maybe_covers_every_launch_the_split_kernel_takes():
     assert not ops.split3_maybe(1787, 512, 1, 256) and not ops.split3_maybe(1787, 256, 1, 512)
     assert ops.split3_maybe(1787, 260, 15, 256)           # level 3's stencil: split over K into one round of workgroups
     assert ops.split3_maybe(9433, 256, 1, 256) and ops.split3_maybe(8192, 1024, 1, 512)
+
+
+def test_dump_outputs_writes_float_files_under_the_limit(tmp_path):
+    """--dump-outputs: small arrays are written whole in float32 (float64 stays float64); an array past the byte limit becomes a
+    seeded sample of its flat entries plus their indices, the same sample on every call, and all files together stay in the limit."""
+    import numpy as np
+    flow = np.arange(3 * 64, dtype=np.float32).reshape(1, 3, 64)
+    big = np.random.RandomState(0).randn(50000)
+    names = bench.dump_outputs(str(tmp_path / 'a'), {'flow': flow, 'ids': np.arange(5), 'big': big}, limit=100000)
+    assert names == ['flow', 'ids', 'big_sample']
+    got = np.load(tmp_path / 'a' / 'flow.npy')
+    assert got.dtype == np.float32 and np.array_equal(got, flow)
+    assert np.load(tmp_path / 'a' / 'ids.npy').dtype == np.float32
+    s, idx = np.load(tmp_path / 'a' / 'big_sample.npy'), np.load(tmp_path / 'a' / 'big_sample_index.npy')
+    assert s.dtype == np.float64 and idx.dtype == np.float64 and np.array_equal(s, big[idx.astype(np.int64)])
+    assert sum(f.stat().st_size for f in (tmp_path / 'a').iterdir()) <= 100000
+    bench.dump_outputs(str(tmp_path / 'b'), {'flow': flow, 'ids': np.arange(5), 'big': big}, limit=100000)
+    assert np.array_equal(np.load(tmp_path / 'b' / 'big_sample_index.npy'), idx)

@@ -75,7 +75,10 @@ def _worker(rank, world, port, out_dir):
     tmax = P.max_over_ranks(1.0 + rank)
     gathered = P.gather_floats([10.0 + rank, -1.0 * rank])
     os.environ['HPL_PIN'] = '1'                      # (off by default until validated on an 8-GPU node)
-    pin = P.pin_host_threads(rank, world)            # (no GPU here: an even split of the visible cores by local rank)
+    # no GPU here: an even split of the visible cores by local rank.  On a box with one GPU, rank 0 would take its GPU's NUMA node
+    # and rank 1 (no device 1) the even split, which overlap; this spawned process is told there is no GPU instead.
+    torch.cuda.is_available = lambda: False
+    pin = P.pin_host_threads(rank, world)
     affinity = sorted(os.sched_getaffinity(0))
     torch.save({'seeds': seeds, 'gathered': gathered, 'pin': pin, 'affinity': affinity, 'grads': [p.grad.clone() for p in model.parameters()], 'same': same,
                 'extra': extra.grad.clone(), 'launched': (launched_in_backward, second_launched, len(red.buckets)),

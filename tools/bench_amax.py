@@ -1,5 +1,5 @@
-import sys, torch
-sys.path.insert(0, '/root/repo')
+import os, sys, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from hplflownet_amd import ops
 for rows, cols in [(25841, 1024), (25841, 580), (34631, 512), (9433, 388)]:
     X = torch.randn(rows, cols, device='cuda')
