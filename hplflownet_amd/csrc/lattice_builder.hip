@@ -57,6 +57,7 @@ struct hpl_lattice {
     hipEvent_t counts_ev = nullptr;
     int64_t bounds[HPL_MAX_LEVELS] = {0};
     int32_t stat_launches = 0, stat_fallbacks = 0, stat_fused = 0;
+    int batch = 1;                    // pairs of the build in progress (> 1: hpl_lattice_begin_batch, fused driver only)
     bool last_fused = false;          // the last finished build came from the fused driver
 
     template <class T> T *take(int64_t count) {
@@ -263,8 +264,9 @@ int fused_finish(hpl_lattice *b) {
     return HPL_OK;
 }
 
-int fused_begin(hpl_lattice *b) {
-    const int64_t need = fused::layout(b->spec, b->n[0], b->n[1], b->bounds, b->pc[0], b->pc[1], b->arena, b->plan);
+int fused_begin(hpl_lattice *b, bool default_bounds = false) {
+    const int64_t need = fused::layout(b->spec, b->n[0], b->n[1], default_bounds ? nullptr : b->bounds, b->pc[0], b->pc[1], b->arena,
+                                       b->plan, b->batch);
     if (need < 0) { set_error("hpl_lattice (fused): clouds too large"); return HPL_EINVAL; }
     if (need > b->end - b->arena) return HPL_ENOMEM;
     b->cur = b->arena + need;
@@ -297,7 +299,7 @@ extern "C" hpl_lattice *hpl_lattice_create(const hpl_lattice_spec *spec) {
     if (spec->fused) {
         if (!fused::supported(*spec)) { set_error("hpl_lattice_create: this spec needs the staged builder (fused = 0)"); hpl_lattice_destroy(b); return nullptr; }
         if (hipHostMalloc(reinterpret_cast<void **>(&b->lv_stage), sizeof(fused::Level) * HPL_MAX_LEVELS, hipHostMallocDefault) != hipSuccess ||
-            hipHostMalloc(reinterpret_cast<void **>(&b->dims_host), sizeof(int32_t) * fused::DIM_INTS * (1 + HPL_MAX_LEVELS), hipHostMallocDefault) != hipSuccess ||
+            hipHostMalloc(reinterpret_cast<void **>(&b->dims_host), sizeof(int32_t) * fused::READBACK_INTS, hipHostMallocDefault) != hipSuccess ||
             hipEventCreateWithFlags(&b->counts_ev, hipEventDisableTiming) != hipSuccess) {
             set_error("hpl_lattice_create: no pinned memory / event for the fused driver");
             hpl_lattice_destroy(b);
@@ -327,11 +329,54 @@ extern "C" int hpl_lattice_begin(hpl_lattice *b, const float *pc1, const float *
     b->level = 0; b->active = true; b->done = false; b->overflow = false;
     b->n[0] = n0; b->n[1] = n1; b->pc[0] = pc1; b->pc[1] = pc2;
     b->n_start[0] = n0; b->n_start[1] = n1;
+    b->batch = 1;
     b->fused_run = b->spec.fused != 0;
     b->last_fused = false;
     const int rc = b->fused_run ? fused_begin(b) : level_head(b);
     if (rc) b->active = false;
     return rc;
+}
+
+extern "C" int hpl_lattice_begin_batch(hpl_lattice *b, const float *pc1, const float *pc2, int64_t batch, int64_t n0, int64_t n1,
+                                       void *arena, int64_t arena_bytes, hplStream stream) {
+    HPL_REQUIRE(b && pc1 && pc2 && n0 > 0 && n1 > 0 && arena && arena_bytes > 0, "hpl_lattice_begin_batch: bad arguments");
+    HPL_REQUIRE(batch >= 1 && batch <= fused::MAX_BATCH, "hpl_lattice_begin_batch: %lld pairs (1 .. %d)", (long long)batch,
+                fused::MAX_BATCH);
+    if (batch == 1) return hpl_lattice_begin(b, pc1, pc2, n0, n1, arena, arena_bytes, stream);     // the single-pair build as is
+    HPL_REQUIRE(b->spec.fused, "hpl_lattice_begin_batch: batches need the fused driver (spec.fused != 0)");
+    HPL_REQUIRE((reinterpret_cast<uintptr_t>(arena) & 255u) == 0, "hpl_lattice_begin_batch: the arena must be 256-byte aligned");
+    b->arena = b->cur = reinterpret_cast<char *>(arena);
+    b->end = b->arena + arena_bytes;
+    b->hs = stream; b->s = to_stream(stream);
+    b->level = 0; b->active = true; b->done = false; b->overflow = false;
+    b->n[0] = batch * n0; b->n[1] = batch * n1; b->pc[0] = pc1; b->pc[1] = pc2;
+    b->n_start[0] = b->n[0]; b->n_start[1] = b->n[1];
+    b->batch = (int)batch;
+    b->fused_run = true;
+    b->last_fused = false;
+    const int rc = fused_begin(b);
+    if (rc) b->active = false;
+    return rc;
+}
+
+extern "C" int64_t hpl_lattice_arena_bytes_batch(const hpl_lattice *b, int64_t batch, int64_t n0, int64_t n1) {
+    if (!b || n0 <= 0 || n1 <= 0 || batch < 1 || batch > fused::MAX_BATCH) return -1;
+    if (batch == 1) return hpl_lattice_arena_bytes(b, n0, n1);
+    if (!b->spec.fused) return -1;
+    fused::Plan tmp;
+    return fused::layout(b->spec, batch * n0, batch * n1, b->bounds, nullptr, nullptr, nullptr, tmp, (int)batch);
+}
+
+extern "C" int hpl_lattice_pair_counts(const hpl_lattice *b, int64_t *out) {
+    HPL_REQUIRE(b && b->done && out, "hpl_lattice_pair_counts: no finished build");
+    const int B = b->batch;
+    for (int L = 0; L < b->spec.n_levels; ++L)
+        for (int c = 0; c < 2; ++c) {
+            if (B == 1) { out[(L * 2 + c)] = c ? b->tab[L].H1 : b->tab[L].H0; continue; }
+            const int32_t *v = b->dims_host + fused::DIMS_BYTES / 4 + L * fused::PAIR_INTS + c * (fused::MAX_BATCH + 1);
+            for (int p = 0; p < B; ++p) out[(L * 2 + c) * B + p] = v[p + 1] - v[p];
+        }
+    return HPL_OK;
 }
 
 extern "C" int64_t hpl_lattice_arena_bytes(const hpl_lattice *b, int64_t n0, int64_t n1) {
@@ -366,6 +411,13 @@ extern "C" int hpl_lattice_advance(hpl_lattice *b, int *done) {
     HPL_REQUIRE(b->active, "hpl_lattice_advance: no build in progress");
     if (b->fused_run) {
         if (hipEventSynchronize(b->counts_ev) != hipSuccess) { set_error("hpl_lattice_advance: event wait failed"); return HPL_EHIP; }
+        if (b->batch > 1 && b->dims_host[fused::HDR_RANGE]) {
+            b->active = false;
+            set_error("hpl_lattice_advance: the key range of a pair of the batch needs more than the %d bits below its pair digit at some "
+                      "level (coordinates too far apart for the scales): use smaller batches or build its pairs one at a time",
+                      b->plan.lv[0].pair_shift);
+            return HPL_EINVAL;
+        }
         if (!b->dims_host[fused::HDR_OVERFLOW]) {
             const int rc = fused_finish(b);
             if (rc) { b->active = false; return rc; }
@@ -375,9 +427,31 @@ extern "C" int hpl_lattice_advance(hpl_lattice *b, int *done) {
             *done = 1;
             return HPL_OK;
         }
+        ++b->stat_fallbacks;
+        if (b->batch > 1) {
+            // a batch outgrew a bound: it is rebuilt on the fused path under the default bounds (16 x the batch's points per
+            // level), in the same arena if it fits; else HPL_ENOMEM, and the caller begins again with those bounds
+            bool tight = false;
+            for (int L = 0; L < b->spec.n_levels; ++L) tight = tight || b->bounds[L] > 0;
+            if (!tight) {
+                b->active = false;
+                set_error("hpl_lattice_advance: the batch outgrew the default vertex bounds; build its pairs one at a time");
+                return HPL_EINVAL;
+            }
+            fused::Plan tmp;
+            const int64_t need = fused::layout(b->spec, b->n[0], b->n[1], nullptr, nullptr, nullptr, nullptr, tmp, b->batch);
+            if (need < 0 || need > b->end - b->arena) {
+                b->active = false;
+                set_error("hpl_lattice_advance: the batch outgrew its bounds and its rebuild under the default bounds needs %lld bytes of "
+                          "arena: set the bounds to 0 and begin again", (long long)need);
+                return HPL_ENOMEM;
+            }
+            const int rc = fused_begin(b, true);
+            if (rc) b->active = false;
+            return rc;
+        }
         // a level outgrew its bound: the pair is rebuilt level by level with exact sizes in the same arena (the fused
         // launches still in flight on this stream only touch memory the staged build rewrites behind them)
-        ++b->stat_fallbacks;
         b->last_fused = false;
         b->fused_run = false;
         b->cur = b->arena;

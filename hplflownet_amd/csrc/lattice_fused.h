@@ -13,6 +13,14 @@ constexpr int D_H0 = 0, D_H1 = 1;  // vertices per cloud (written by the id stag
 constexpr int D_MM = 2;            // [8]: per-coordinate key minima [4] and maxima [4] over both clouds
 // header record
 constexpr int HDR_OVERFLOW = 0;    // a level produced more vertices than its bound: the build is void
+constexpr int HDR_RANGE = 1;       // batch: a pair's key range does not fit the bits below its pair digit: the build is void
+// A batch of B pairs is built as ONE pair of clouds (pair-major rows).  Its read-back is the dims block (padded to 256 bytes)
+// followed by the pair block: per level and cloud the first vertex of every pair and the vertex count behind the last
+// ([B + 1] ints in a slot of MAX_BATCH + 1).
+constexpr int MAX_BATCH = 64;
+constexpr int PAIR_INTS = 2 * (MAX_BATCH + 1);    // ints per level of the pair block
+constexpr int64_t DIMS_BYTES = ((int64_t)sizeof(int32_t) * DIM_INTS * (1 + HPL_MAX_LEVELS) + 255) / 256 * 256;
+constexpr int64_t READBACK_INTS = DIMS_BYTES / 4 + (int64_t)HPL_MAX_LEVELS * PAIR_INTS;
 
 struct SortJob {
     int32_t kind;        // 1: rows of the pair table (M = H0 + H1), 2: its cloud-1 columns (M = H0)
@@ -60,6 +68,12 @@ struct Level {
     float *csr_w, *norm;
     int32_t n_jobs, pad_;
     SortJob job[MAX_JOBS];
+    // batch (batch > 1): level 0 reads (B, 3, n_pair[c]) clouds; every vertex carries its pair (vpair), every pair its own
+    // key range (pmm: [B][8] minima / maxima over both clouds of the pair) and its first vertex id (voff, the pair block)
+    int32_t batch, n_pair[2];
+    int32_t pair_shift;           // packed key of a batch: pair << pair_shift | key within the pair's range (63 - bits of batch - 1)
+    const int32_t *prev_vpair[2];
+    int32_t *vpair[2], *voff[2], *pmm;
 };
 
 struct Plan {
@@ -69,22 +83,27 @@ struct Plan {
     int32_t *d_dims = nullptr;    // in the arena: (1 + n_levels) records
     int64_t bytes = 0;            // arena bytes in use
     int launches = 0;             // kernel launches of the last enqueue
+    int batch = 1;                // pairs in the build
+    int32_t *d_pairs = nullptr;   // in the arena, right behind the dims block (batch > 1): HPL_MAX_LEVELS x PAIR_INTS
+    int32_t *d_pmm = nullptr;     // in the arena (batch > 1): n_levels x MAX_BATCH x 8 per-pair key ranges
 };
 
 // default per-cloud bound on a level's vertex count: min(4 x the bound of its input points, row_cap)
 int64_t default_row_cap(int64_t n0, int64_t n1);
 
 // Lay the build out in `arena` (nullptr: size query only).  bounds[L] > 0 overrides the vertex bound of level L (per
-// cloud).  Returns the bytes needed, or -1 (plan.bytes is set either way).
+// cloud; a batch scales it by its pairs).  n0, n1: points per cloud of the whole build (a batch: batch x its pairs' points).
+// Returns the bytes needed, or -1 (plan.bytes is set either way).
 int64_t layout(const hpl_lattice_spec &spec, int64_t n0, int64_t n1, const int64_t *bounds, const float *pc1,
-               const float *pc2, char *arena, Plan &plan);
+               const float *pc2, char *arena, Plan &plan, int batch = 1);
 
 // true if this spec can be built by the fused path (radius-1 stencils, corr1 sharing the blur table, <= 4 groups)
 bool supported(const hpl_lattice_spec &spec);
 
 // Enqueue the whole build.  lv_stage: pinned host memory of sizeof(Level) * HPL_MAX_LEVELS the level array is copied
-// from (must stay untouched until the copy has run).  dims_host (pinned, (1 + HPL_MAX_LEVELS) * DIM_INTS ints) receives the
-// dims block as soon as the last level's vertex counts exist; counts_ev is recorded behind that copy.
+// from (must stay untouched until the copy has run).  dims_host (pinned, READBACK_INTS ints) receives the
+// dims block (a batch: the pair block too) as soon as the last level's vertex counts exist; counts_ev is
+// recorded behind that copy.
 int enqueue(Plan &plan, Level *lv_stage, int32_t *dims_host, hipEvent_t counts_ev, hipStream_t s);
 
 }  // namespace fused

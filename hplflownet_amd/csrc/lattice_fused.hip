@@ -57,6 +57,35 @@ __device__ __forceinline__ int dcdiv(int a, int b) { return (a + b - 1) / b; }
 // hash slot {key lo, key hi, first, id}
 __device__ __forceinline__ int64_t slot_key(const int4 &s) { return (int64_t)(((uint64_t)(uint32_t)s.y << 32) | (uint32_t)s.x); }
 
+// ------------------------------------------------------------------------------------------------ batches
+// A batch of B pairs is one pair of clouds whose rows are pair-major.  Keys never match across pairs: a key is packed over
+// its PAIR's own range (the range its single-pair build uses) below a pair digit, so each pair's vertices are numbered in
+// first-appearance order behind the previous pair's -- exactly its single-pair ids plus an offset -- and no table links two
+// pairs.  The pair of a point: level 0 from its row, deeper levels from the vertex of the level above it is (vpair).
+__device__ __forceinline__ int point_pair(const Level &L, int c, int p) {
+    return L.prev_dims ? L.prev_vpair[c][p] : p / L.n_pair[c];
+}
+
+// number of packed keys in a pair's range; 0 if they do not fit below the pair digit (the build is refused, HDR_RANGE)
+__device__ __forceinline__ int64_t pair_range(const int32_t *__restrict__ mm, int shift) {
+    double rd = 1.0;
+    int64_t R = 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int64_t r = (int64_t)mm[4 + i] - mm[i] + 1;
+        rd *= (double)r;
+        R *= r;
+    }
+    return rd < 0.999999 * (double)(1ll << shift) ? R : 0;
+}
+
+// key k of pair pr: pr << shift | key2int over the pair's range -- the single-pair build's packed key, its aliasing of
+// out-of-range neighbour keys included.  -1 outside [0, R): the single-pair build finds nothing there either.
+__device__ __forceinline__ int64_t pair_key(const int k[4], const int32_t *__restrict__ mm, int64_t R, int pr, int shift) {
+    const int64_t local = pack_key(k, mm);
+    return (local < 0 || local >= R) ? -1 : (((int64_t)pr << shift) | local);
+}
+
 // rows of a sort job for this pair, 0 if the job does not run (the same rules as lattice_builder.hip level_tail)
 __device__ __forceinline__ int job_rows(const Level &L, const SortJob &J) {
     const int H0 = L.dims[D_H0], H1 = L.dims[D_H1];
@@ -99,13 +128,68 @@ __device__ __forceinline__ int block_sum(int v, int *scr) {
 // ------------------------------------------------------------------------------------------------ phase 1: keys
 // keys + barycentric + el_minus_gr of both clouds (transforms.py:300-353), the joint key range (:384-385), and the
 // clearing of everything the later phases of this level accumulate into
+template <bool BT>
 __device__ void task_keys(const Level &L, int b, int nblk, const Elev &E, int *scr) {
     const int n0 = npts(L, 0), n1 = npts(L, 1);
     const int t0 = b * 256 + threadIdx.x, nth = nblk * 256;
     // the points go to the first few workgroups (4 per lane): every workgroup that has points ends in 8 atomics on the
     // SAME 8 words of the dims block, and a thousand of them would be a chain longer than the rest of the phase
     const int pblk = min(nblk, max(1, dcdiv(n0 + n1, 1024)));
-    if (b < pblk) {
+    if (BT && b < pblk) {
+        // a batch: the key range of every pair.  A wave's 64 points nearly always belong to one pair (pairs are contiguous
+        // runs of rows): it reduces them and one lane updates that pair's 8 words; a wave across a pair boundary updates per lane
+        const int lane = threadIdx.x & 63;
+        for (int i0 = b * 256 + (threadIdx.x & ~63); i0 < n0 + n1; i0 += pblk * 256) {
+            const int i = i0 + lane;
+            int lo[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX}, hi[4] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN};
+            int pr = -1;
+            if (i < n0 + n1) {
+                const int c = i >= n0 ? 1 : 0;
+                const int p = c ? i - n0 : i, N = c ? n1 : n0;
+                pr = point_pair(L, c, p);
+                float q[3];
+                if (L.pc[0]) {       // (B, 3, n_pair) clouds, read in place
+                    const int np = L.n_pair[c], pp = p - pr * np;
+                    const float *pc = L.pc[c] + (int64_t)pr * 3 * np;
+                    q[0] = pc[pp]; q[1] = pc[np + pp]; q[2] = pc[2 * np + pp];
+                } else {
+                    const int32_t *vk = L.prev_vk[c];
+                    const int64_t vs = L.prev_vstride[c];
+                    float v[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[j] = (float)vk[j * vs + p] / L.prev_div;
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        float acc = E.e[0 * 3 + k] * v[0];
+                        acc = fmaf(E.e[1 * 3 + k], v[1], acc);
+                        acc = fmaf(E.e[2 * 3 + k], v[2], acc);
+                        acc = fmaf(E.e[3 * 3 + k], v[3], acc);
+                        q[k] = acc;
+                    }
+                }
+                lattice_point(q[0], q[1], q[2], p, N, L.scale, E, L.keys[c], L.bary[c], L.emg + (c ? 4 * (int64_t)n0 : 0), 4, lo, hi);
+            }
+            const unsigned long long has = __ballot(pr >= 0);
+            const int lead = __ffsll((long long)has) - 1;
+            const int pr0 = __shfl(pr, lead < 0 ? 0 : lead);
+            if (__all(pr < 0 || pr == pr0)) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) {
+                        lo[j] = min(lo[j], __shfl_xor(lo[j], o));
+                        hi[j] = max(hi[j], __shfl_xor(hi[j], o));
+                    }
+                if (lane == lead) pr = pr0;
+                else pr = -1;
+            }
+            if (pr >= 0) {
+                int32_t *mm = L.pmm + pr * 8;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { atomicMin(&mm[j], lo[j]); atomicMax(&mm[4 + j], hi[j]); }
+            }
+        }
+    } else if (b < pblk) {
         int lo[4] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX}, hi[4] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN};
         for (int i = t0; i < n0 + n1; i += pblk * 256) {
             const int c = i >= n0 ? 1 : 0;
@@ -170,6 +254,7 @@ __device__ void task_keys(const Level &L, int b, int nblk, const Elev &E, int *s
 // j into the slot (the owner = first appearance).  The staged builder deduplicates 1024 keys in LDS first, which saves
 // global atomics; here the build is bound by the LENGTH of its dependency chains, not by atomic throughput (<= 2^18 keys),
 // and the direct form is two dependent global operations per lane instead of a workgroup-serial LDS round.
+template <bool BT>
 __device__ void task_insert(const Level &L, int b, int nblk) {
     const int n0 = npts(L, 0), n1 = npts(L, 1);
     const int32_t *mm = L.dims + D_MM;
@@ -185,7 +270,19 @@ __device__ void task_insert(const Level &L, int b, int nblk) {
         int k[4];
 #pragma unroll
         for (int x = 0; x < 4; ++x) k[x] = keys[((int64_t)x * n + p) * 4 + r];
-        const unsigned long long packed = (unsigned long long)pack_key(k, mm);
+        unsigned long long packed;
+        if (BT) {
+            const int pr = point_pair(L, c, p);
+            const int64_t R = pair_range(L.pmm + pr * 8, L.pair_shift);
+            if (R == 0) {           // the pair's keys cannot be packed below its pair digit: refuse the build, never alias
+                L.hdr[HDR_RANGE] = 1;
+                L.slot[c][j] = 0;
+                continue;
+            }
+            packed = (unsigned long long)pair_key(k, L.pmm + pr * 8, R, pr, L.pair_shift);
+        } else {
+            packed = (unsigned long long)pack_key(k, mm);
+        }
         uint64_t sl = mix64(packed) & mask;
         while (true) {
             const unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long *>(&ts[sl]),
@@ -221,6 +318,7 @@ __device__ void task_flags(const Level &L, int b, int nblk, int *scr) {
     }
 }
 
+template <bool BT>
 __device__ void task_ids(const Level &L, int b, int nblk, int *scr) {
     const int n0 = npts(L, 0), n1 = npts(L, 1);
     const int ch0 = dcdiv(4 * n0, SCAN_CHUNK), ch1 = dcdiv(4 * n1, SCAN_CHUNK);
@@ -254,12 +352,19 @@ __device__ void task_ids(const Level &L, int b, int nblk, int *scr) {
                 const int p = j >> 2, r = j & 3;
 #pragma unroll
                 for (int x = 0; x < 4; ++x) L.vk[c][x * vs + id] = keys[((int64_t)x * n + p) * 4 + r];
+                if (BT) {
+                    // the pair's first entry always owns its vertex (no earlier pair has its keys): that vertex is the pair's first
+                    const int pr = point_pair(L, c, p);
+                    L.vpair[c][id] = pr;
+                    if (r == 0 && (p == 0 || point_pair(L, c, p - 1) != pr)) L.voff[c][pr] = id;
+                }
             }
             ++id;
         }
         if (qc == nch - 1 && threadIdx.x == 0) {
             const int H = before + tot;
             L.dims[D_H0 + c] = H;
+            if (BT) L.voff[c][L.batch] = H;
             if (H > Hb) L.hdr[HDR_OVERFLOW] = 1;
         }
     }
@@ -286,6 +391,7 @@ __device__ __forceinline__ uint32_t gray_rank(uint32_t m) {        // position o
 
 // blur table of the pair [15][H0 + H1] (cloud 2's vertices numbered behind cloud 1's; transforms.py:209-221), one lane
 // per vertex: its 15 probes give the tap-presence mask, hence the sort keys of the row orders and their first digit counts
+template <bool BT>
 __device__ void task_blur(const Level &L, int b, int nblk, const Off15 &o, int *hist) {
     const int H0 = L.dims[D_H0], H1 = L.dims[D_H1], Hp = H0 + H1;
     const int n0 = npts(L, 0), n1 = npts(L, 1);
@@ -316,6 +422,9 @@ __device__ void task_blur(const Level &L, int b, int nblk, const Off15 &o, int *
             int kv[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) kv[j] = vk[j * vs + hh];
+            const int pr = BT ? L.vpair[c][hh] : 0;
+            const int32_t *pmm = BT ? L.pmm + pr * 8 : mm;
+            const int64_t R = BT ? pair_range(pmm, L.pair_shift) : 0;
             // The probes of a vertex are independent: hash, load the first two slots of each (ONE 16-byte word per slot: key +
             // id), decide; only a run of two collisions (rare at load <= 0.5) walks on.  Two batches (8 + 7 probes): one batch's
             // slots are 64 registers -- with all 15 in flight the kernel needed 195 registers (2 waves per SIMD for EVERY task of
@@ -329,7 +438,7 @@ __device__ void task_blur(const Level &L, int b, int nblk, const Off15 &o, int *
                     int k[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) k[j] = kv[j] + o.v[(F0 + u) * 4 + j];
-                    pk[u] = pack_key(k, mm);
+                    pk[u] = BT ? pair_key(k, pmm, R, pr, L.pair_shift) : pack_key(k, mm);
                     sl[u] = (uint32_t)(mix64((uint64_t)pk[u]) & mask);
                 }
                 int4 s0[NF], s1[NF];
@@ -384,6 +493,7 @@ __device__ void task_blur(const Level &L, int b, int nblk, const Off15 &o, int *
 }
 
 // pc2_corr_indices in the kernel-ready layout [15][15 * H0] (transforms.py:223-241)
+template <bool BT>
 __device__ void task_corr2(const Level &L, int b, int nblk, const Off15 &o) {
     const int H0 = L.dims[D_H0];
     const int n1 = npts(L, 1);
@@ -400,7 +510,14 @@ __device__ void task_corr2(const Level &L, int b, int nblk, const Off15 &o) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) k[j] = vk[j * vs + h] + o.v[kc * 4 + j] + o.v[f * 4 + j];
         // (one 16-byte word per probed slot: key and id together)
-        const int64_t packed = pack_key(k, mm);
+        int64_t packed;
+        if (BT) {
+            const int pr = L.vpair[0][h];
+            const int32_t *pmm = L.pmm + pr * 8;
+            packed = pair_key(k, pmm, pair_range(pmm, L.pair_shift), pr, L.pair_shift);
+        } else {
+            packed = pack_key(k, mm);
+        }
         int32_t id = -1;
         if (packed >= 0) {
             uint64_t x = mix64((uint64_t)packed) & mask;
@@ -717,6 +834,8 @@ __device__ void task_tile_rank(const Level &L, const SortJob &J, int *sm) {
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
+// BT: a batch of pairs (the per-pair key ranges and pair digits); false: the single-pair build as it always was
+template <bool BT>
 __global__ void __launch_bounds__(256) k_lattice_fused(const Level *__restrict__ levels, const Launch l, const Elev E,
                                                        const Off15 o) {
     __shared__ __attribute__((aligned(16))) char smem[9216];        // the sort's digit bases and per-wave counts; scan scratch; csr_rank's segments
@@ -724,17 +843,17 @@ __global__ void __launch_bounds__(256) k_lattice_fused(const Level *__restrict__
     for (int i = 1; i < l.n; ++i) ti = ((int)blockIdx.x >= l.t[i].blk0) ? i : ti;
     const Task t = l.t[ti];
     const Level &L = levels[t.level];
-    if (L.hdr[HDR_OVERFLOW]) return;
+    if (L.hdr[HDR_OVERFLOW] || (BT && L.hdr[HDR_RANGE])) return;
     const int b = (int)blockIdx.x - t.blk0;
     int *ism = reinterpret_cast<int *>(smem);
     switch (t.kind) {
-    case T_KEYS: task_keys(L, b, t.nblk, E, ism); break;
-    case T_INSERT: task_insert(L, b, t.nblk); break;
+    case T_KEYS: task_keys<BT>(L, b, t.nblk, E, ism); break;
+    case T_INSERT: task_insert<BT>(L, b, t.nblk); break;
     case T_FLAGS: task_flags(L, b, t.nblk, ism); break;
-    case T_IDS: task_ids(L, b, t.nblk, ism); break;
+    case T_IDS: task_ids<BT>(L, b, t.nblk, ism); break;
     case T_OFF: task_off(L, b, t.nblk); break;
-    case T_BLUR: task_blur(L, b, t.nblk, o, ism); break;
-    case T_CORR2: task_corr2(L, b, t.nblk, o); break;
+    case T_BLUR: task_blur<BT>(L, b, t.nblk, o, ism); break;
+    case T_CORR2: task_corr2<BT>(L, b, t.nblk, o); break;
     case T_CSR_SUMS: task_csr_sums(L, b, t.nblk, ism); break;
     case T_SORT1: task_sort(L, L.job[t.job], 1, b, t.nblk, smem); break;
     case T_CSR_SCAN: task_csr_scan(L, b, t.nblk, ism); break;
@@ -748,8 +867,9 @@ __global__ void __launch_bounds__(256) k_lattice_fused(const Level *__restrict__
     }
 }
 
-__global__ void k_fused_begin(int32_t *dims, int n_levels) {
+__global__ void k_fused_begin(int32_t *dims, int n_levels, int32_t *pmm, int n_pmm) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_pmm) pmm[i] = (i & 7) < 4 ? INT_MAX : INT_MIN;      // per-pair key ranges of a batch: empty
     if (i >= (1 + n_levels) * DIM_INTS) return;
     const int rec = i / DIM_INTS, k = i - rec * DIM_INTS;
     int v = 0;
@@ -784,7 +904,7 @@ bool supported(const hpl_lattice_spec &sp) {
 }
 
 int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t *bounds, const float *pc1,
-               const float *pc2, char *arena, Plan &plan) {
+               const float *pc2, char *arena, Plan &plan, int batch) {
     int64_t used = 0;
     auto take = [&](int64_t bytes) -> char * {
         char *r = arena ? arena + used : nullptr;
@@ -793,7 +913,13 @@ int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t
     };
     plan.n_levels = sp.n_levels;
     plan.d_levels = reinterpret_cast<Level *>(take(sizeof(Level) * HPL_MAX_LEVELS));
-    plan.d_dims = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * DIM_INTS * (1 + HPL_MAX_LEVELS)));
+    plan.d_dims = reinterpret_cast<int32_t *>(take(DIMS_BYTES));
+    plan.batch = batch;
+    plan.d_pairs = plan.d_pmm = nullptr;
+    if (batch > 1) {       // (the pair block right behind the dims block: one read-back covers both)
+        plan.d_pairs = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * HPL_MAX_LEVELS * PAIR_INTS));
+        plan.d_pmm = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * sp.n_levels * MAX_BATCH * 8));
+    }
     const int64_t cap = default_row_cap(n0, n1);
     int64_t nb[2] = {n0, n1};
     for (int Li = 0; Li < sp.n_levels; ++Li) {
@@ -804,7 +930,7 @@ int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t
         int64_t Hb[2];
         for (int c = 0; c < 2; ++c) {
             Hb[c] = imin(4 * nb[c], cap);
-            if (bounds && bounds[Li] > 0) Hb[c] = imin(4 * nb[c], bounds[Li]);
+            if (bounds && bounds[Li] > 0) Hb[c] = imin(4 * nb[c], bounds[Li] * batch);
             L.nb[c] = (int32_t)nb[c];
             L.Hb[c] = (int32_t)Hb[c];
         }
@@ -822,9 +948,15 @@ int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t
         L.hdr = plan.d_dims;
         L.dims = plan.d_dims ? plan.d_dims + DIM_INTS * (1 + Li) : nullptr;
         L.prev_dims = (Li && plan.d_dims) ? plan.d_dims + DIM_INTS * Li : nullptr;
+        L.batch = batch;
+        L.pair_shift = 63;
+        while ((1 << (63 - L.pair_shift)) < batch) --L.pair_shift;        // B = 2: 62 bits per pair, B = 64: 57
+        L.n_pair[0] = (int32_t)(n0 / batch); L.n_pair[1] = (int32_t)(n1 / batch);
+        L.pmm = plan.d_pmm ? plan.d_pmm + (int64_t)Li * MAX_BATCH * 8 : nullptr;
         if (Li == 0) { L.pc[0] = pc1; L.pc[1] = pc2; }
         else {
             const Level &P = plan.lv[Li - 1];
+            L.prev_vpair[0] = P.vpair[0]; L.prev_vpair[1] = P.vpair[1];
             L.prev_vk[0] = P.vk[0]; L.prev_vk[1] = P.vk[1];
             L.prev_vstride[0] = P.vstride[0]; L.prev_vstride[1] = P.vstride[1];
         }
@@ -835,6 +967,10 @@ int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t
             L.off[c] = reinterpret_cast<int32_t *>(take(nb[c] * 16));
             L.vstride[c] = (int32_t)Hb[c];
             L.vk[c] = reinterpret_cast<int32_t *>(take(Hb[c] * 16));
+            if (batch > 1) {
+                L.vpair[c] = reinterpret_cast<int32_t *>(take(Hb[c] * 4));
+                L.voff[c] = plan.d_pairs ? plan.d_pairs + (int64_t)Li * PAIR_INTS + c * (MAX_BATCH + 1) : nullptr;
+            }
             const int64_t capb = pow2_at_least(8 * nb[c]);
             L.tslot[c] = reinterpret_cast<int4 *>(take(capb * 16));
             L.slot[c] = reinterpret_cast<int32_t *>(take(nb[c] * 16));
@@ -889,11 +1025,17 @@ int enqueue(Plan &plan, Level *lv_stage, int32_t *dims_host, hipEvent_t counts_e
         set_error("hpl_lattice (fused): copy of the level descriptors failed");
         return HPL_EHIP;
     }
-    k_fused_begin<<<cdiv((1 + nlev) * DIM_INTS, 256), 256, 0, s>>>(plan.d_dims, nlev);
+    const int n_pmm = plan.batch > 1 ? nlev * MAX_BATCH * 8 : 0;
+    k_fused_begin<<<cdiv(imax((1 + nlev) * DIM_INTS, n_pmm), 256), 256, 0, s>>>(plan.d_dims, nlev, plan.d_pmm, n_pmm);
+    const bool bt = plan.batch > 1;
     const Elev E = make_elev();
     const Offsets full = make_offsets(1);
     Off15 o;
     for (int i = 0; i < 60; ++i) o.v[i] = full.v[i];
+    auto kernel = [&](int grid, const Launch &ll) {
+        if (bt) k_lattice_fused<true><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
+        else k_lattice_fused<false><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
+    };
     const int n_launches = 4 * (nlev - 1) + 10;
     plan.launches = 1;
     for (int t = 0; t < n_launches; ++t) {
@@ -971,17 +1113,20 @@ int enqueue(Plan &plan, Level *lv_stage, int32_t *dims_host, hipEvent_t counts_e
                 one.n = 1;
                 one.t[0] = l.t[i];
                 one.t[0].blk0 = 0;
-                k_lattice_fused<<<l.t[i].nblk, 256, 0, s>>>(plan.d_levels, one, E, o);
+                kernel(l.t[i].nblk, one);
                 if (split > 1) fprintf(stderr, "launch %d task %s level %d job %d blocks %d\n", t, names[l.t[i].kind], l.t[i].level, l.t[i].job, l.t[i].nblk);
             }
             ++plan.launches;
             goto after_launch;
         }
-        k_lattice_fused<<<blk, 256, 0, s>>>(plan.d_levels, l, E, o);
+        kernel(blk, l);
         ++plan.launches;
     after_launch:
         if (t == 4 * (nlev - 1) + 3) {        // every level's vertex counts exist: start the one read-back of the build
-            if (hipMemcpyAsync(dims_host, plan.d_dims, sizeof(int32_t) * DIM_INTS * (1 + nlev), hipMemcpyDeviceToHost, s) !=
+            // (a batch: through the end of the pair block, which follows the dims block in the arena)
+            const int64_t rb = bt ? (reinterpret_cast<char *>(plan.d_pairs + (int64_t)nlev * PAIR_INTS) - reinterpret_cast<char *>(plan.d_dims))
+                                  : (int64_t)sizeof(int32_t) * DIM_INTS * (1 + nlev);
+            if (hipMemcpyAsync(dims_host, plan.d_dims, rb, hipMemcpyDeviceToHost, s) !=
                     hipSuccess ||
                 hipEventRecord(counts_ev, s) != hipSuccess) {
                 set_error("hpl_lattice (fused): read-back of the vertex counts failed");

@@ -40,6 +40,7 @@ import torch
 
 from . import data as data_mod
 from . import ops, parallel
+from ._lib import HplError
 from .flownet import HPLFlowNet, HPLFlowNetShallow, load_reference_checkpoint
 from .lattice import GenerateDataUnsymmetric, LatticePipeline
 from .synthetic import SCALES_FILTER_MAP, fill_module_, synthetic_pair
@@ -148,6 +149,8 @@ class Trainer(object):
 
     def train_step(self, pc1, pc2, sf, lat):
         """One optimiser step on one pair (main.py:203-217) -> the loss (device tensor, not synchronised)."""
+        if getattr(lat, 'batch', 1) > 1:
+            raise HplError('train_step takes one pair: a lattice of %d pairs is for batched inference (validate)' % lat.batch)
         if self.native_step and self.tplan is None:
             from .train_plan import TrainPlan
             if self.reducer is None:
@@ -214,19 +217,47 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data):
+    def validate(self, data, batch_size=1):
+        """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
+        point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
+        differ from its neighbours' forms a batch of its own."""
         self.model.eval()
         agg = collections.OrderedDict()
-        for (pc1, pc2, sf), lat in self._lattices(data, list(range(len(data))), False):
-            flow = self.model(pc1[None], pc2[None], lat)
-            for k, v in flow_metrics(flow[0].t(), sf.t()).items():
+
+        def add(flow, sf):
+            for k, v in flow_metrics(flow.t(), sf.t()).items():
                 agg[k] = agg.get(k, 0.0) + v
+        if batch_size > 1:
+            for group in self._batches(data, batch_size):
+                p1 = torch.stack([g[0] for g in group])
+                p2 = torch.stack([g[1] for g in group])
+                lat = self.gen.build_native_batch(p1, p2) if len(group) > 1 else self.gen.build_native(p1[0], p2[0])
+                flow = self.model(p1, p2, lat)
+                for b, g in enumerate(group):
+                    add(flow[b], g[2])
+        else:
+            for (pc1, pc2, sf), lat in self._lattices(data, list(range(len(data))), False):
+                flow = self.model(pc1[None], pc2[None], lat)
+                add(flow[0], sf)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
         # added over the ranks, so all ranks return the metrics of the WHOLE split (and agree on `best` in fit())
         keys = list(agg) if agg else ['EPE3D', 'Acc3DS', 'Acc3DR', 'Outliers']
         tot = parallel.sum_over_ranks([agg.get(k, 0.0) for k in keys] + [float(len(data))], device=self.device)
         self.val_samples = int(tot[-1])         # over all ranks: 0 = no rank had a validation sample
         return {k: v / max(1.0, tot[-1]) for k, v in zip(keys, tot[:-1])}
+
+    @staticmethod
+    def _batches(data, batch_size):
+        """Consecutive samples of `data` (each fetched once) in groups of <= batch_size with equal point counts."""
+        group = []
+        for i in range(len(data)):
+            s_ = data[i]
+            if group and (len(group) == batch_size or not same_counts(group[0], s_)):
+                yield group
+                group = []
+            group.append(s_)
+        if group:
+            yield group
 
     # ------------------------------------------------------------------ checkpoints
     def state(self):
@@ -279,6 +310,23 @@ class Trainer(object):
         return self.min_loss
 
 
+def same_counts(a, b):
+    """True if samples a and b ((pc1, pc2, sf), (3, N) each) have the same point counts: they can share a batch."""
+    return a[0].shape[-1] == b[0].shape[-1] and a[1].shape[-1] == b[1].shape[-1]
+
+
+def batch_groups(counts, batch_size):
+    """Index groups validate(batch_size=...) forms from per-sample point counts [(n1, n2), ...]: consecutive, equal
+    counts, at most batch_size each."""
+    out = []
+    for i, c in enumerate(counts):
+        if out and len(out[-1]) < batch_size and counts[out[-1][0]] == c:
+            out[-1].append(i)
+        else:
+            out.append([i])
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--arch', default='HPLFlowNet', choices=sorted(ARCHS))
@@ -293,10 +341,15 @@ def main(argv=None):
     ap.add_argument('--ckpt-dir', default=None)
     ap.add_argument('--resume', default=None)
     ap.add_argument('--evaluate', action='store_true')
+    ap.add_argument('--batch-size', type=int, default=1,
+                    help='--evaluate: pairs per batched lattice build and forward (1 .. 64); consecutive pairs with equal point '
+                         'counts are batched (default 1: one pair at a time)')
     ap.add_argument('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI'])
     ap.add_argument('--data-root', default=None)
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
+    if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
+        ap.error('--batch-size takes 1 .. 64 and applies to --evaluate (training takes one pair per step)')
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
     if a.val_pairs is None:
@@ -310,7 +363,7 @@ def main(argv=None):
     if a.dataset != 'synthetic':
         return _real_data(a, tr, dev, rank, world)
     if a.evaluate:
-        res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs))
+        res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size)
         if rank == 0:
             print(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
@@ -371,7 +424,7 @@ def _real_data(a, tr, dev, rank, world):
         log('note: training on the first %d samples of each rank\'s shard only (--pairs)' % a.pairs)
     val = _Shard(val, rank, world, cap)
     if train is None:
-        res = tr.validate(val)
+        res = tr.validate(val, a.batch_size)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True)

@@ -311,6 +311,7 @@ class _FlowNetBase(nn.Module):
 
     def forward(self, pc1, pc2, generated_data):
         dev = pc1.device
+        B = batch_of(pc1, pc2, generated_data, torch.is_grad_enabled(), self.pair_batched)
         if not pc1.is_cuda:
             raise _lib.HplError('the HIP path needs device tensors (no CPU fallback)')
         native_lat = getattr(generated_data, 'device_lattice', None)       # lattice.NativeLattice
@@ -362,13 +363,17 @@ class _FlowNetBase(nn.Module):
             feat_c = self.conv1[-1].conv.out_channels
             n0 = lat.levels[0].pair.N
             xin = torch.empty((n0, pc1.shape[1]), dtype=torch.float32, device=dev)
-            if lat.levels[0].clouds[0].N != pc1.shape[2] or lat.levels[0].clouds[1].N != pc2.shape[2]:
+            if lat.levels[0].clouds[0].N != B * pc1.shape[2] or lat.levels[0].clouds[1].N != B * pc2.shape[2]:
                 raise _lib.HplError('lattice was built for %d / %d points, got %d / %d'
-                                    % (lat.levels[0].clouds[0].N, lat.levels[0].clouds[1].N, pc1.shape[2],
-                                       pc2.shape[2]))
+                                    % (lat.levels[0].clouds[0].N, lat.levels[0].clouds[1].N, B * pc1.shape[2],
+                                       B * pc2.shape[2]))
             h = pc1.shape[2]
-            xin[:h].copy_(to_channel_last(pc1))
-            xin[h:].copy_(to_channel_last(pc2))
+            if B > 1:           # a batch: pair-major rows, cloud 1 of every pair, then cloud 2 of every pair
+                xin[:B * h].view(B, h, 3).copy_(pc1.transpose(1, 2))
+                xin[B * h:].view(B, pc2.shape[2], 3).copy_(pc2.transpose(1, 2))
+            else:
+                xin[:h].copy_(to_channel_last(pc1))
+                xin[h:].copy_(to_channel_last(pc2))
             x = torch.empty((n0, 4 + feat_c), dtype=torch.float32, device=dev)
             self._stack(xin, self.conv1, out=x[:, 4:])
             for L in range(nlev):
@@ -418,7 +423,26 @@ class _FlowNetBase(nn.Module):
         y = pointwise_conv(y, self.conv2.conv, True, self.use_leaky)
         y = pointwise_conv(y, self.conv3.conv, True, self.use_leaky)
         y = pointwise_conv(y, self.conv4, False, self.use_leaky)
+        if B > 1:
+            return y.view(B, -1, y.shape[1]).transpose(1, 2)              # (B, 3, N1)
         return to_channel_first(y)
+
+
+def batch_of(pc1, pc2, lat, grad, pair_batched=True):
+    """Pairs of a forward (no launch): (1, 3, N) / (3, N) inputs take a single-pair lattice; (B, 3, N) inputs a lattice of
+    lattice.GenerateDataUnsymmetric.build_native_batch with the same B, inference only (no autograd)."""
+    lb = int(getattr(lat, 'batch', 1) or 1)
+    b1 = int(pc1.shape[0]) if pc1.dim() == 3 else 1
+    b2 = int(pc2.shape[0]) if pc2.dim() == 3 else 1
+    if b1 != b2:
+        raise _lib.HplError('pc1 holds %d clouds, pc2 %d' % (b1, b2))
+    if b1 != lb:
+        raise _lib.HplError('%d pairs of clouds, but the lattice was built for %d (build_native_batch builds a batch)' % (b1, lb))
+    if b1 > 1 and grad:
+        raise _lib.HplError('batched lattices are for inference: run the forward under torch.no_grad() (training takes one pair)')
+    if b1 > 1 and not pair_batched:
+        raise _lib.HplError('batched inference needs the pair-batched forward')
+    return b1
 
 
 class HPLFlowNet(_FlowNetBase):

@@ -68,6 +68,14 @@ class GenerateDataUnsymmetric(object):
         """The same lattice from the native builder (one arena, one C call per level half): -> NativeLattice."""
         return NativeLatticeBuild(self, pc1, pc2).finish()
 
+    def build_native_batch(self, pc1, pc2):
+        """B pairs in one fused build: pc1 (B, 3, N1), pc2 (B, 3, N2) float32 device tensors -> NativeLattice with
+        `batch` = B and `pair_counts` ([levels][2][B] vertices).  Its tables are those of one pair of clouds of B x N1 /
+        B x N2 pair-major points (pair b's slice of every table is pair b's build_native plus offsets); the models take
+        it with the same (B, 3, N) tensors.  B = 1 is build_native of pc1[0], pc2[0]."""
+        check_batch(pc1, pc2)
+        return NativeLatticeBuild(self, pc1, pc2).finish()
+
     def build(self, pc1, pc2):
         """pc1, pc2: (3, N) float32 device tensors -> DeviceLattice (blocks on every read-back)."""
         steps = self.build_steps(pc1, pc2)
@@ -82,6 +90,9 @@ class GenerateDataUnsymmetric(object):
         (an asynchronous copy into pinned memory), yields the event that marks its arrival and must be
         resumed -- on the same stream -- only after that event has completed; returns the DeviceLattice
         (StopIteration.value)."""
+        if pc1.dim() != 2 or pc2.dim() != 2:
+            raise _lib.HplError('the staged lattice driver builds one pair of (3, N) clouds, got %s / %s: batches are built '
+                                'by build_native_batch' % (tuple(pc1.shape), tuple(pc2.shape)))
         L = _lib.load()
         dev = pc1.device
         pts = [pc1.contiguous().float(), pc2.contiguous().float()]     # level 0: the clouds themselves
@@ -221,12 +232,28 @@ class LatticePipeline(object):
 
     `source(i)` -> (pc1, pc2) device tensors (3, N) of pair i; pairs first .. first+count-1 are built,
     each exactly once, and handed out in order by get() as ((i, source(i)), DeviceLattice, event); the
+    `batch` = B > 1 (native builder): B consecutive pairs are stacked into (B, 3, N) clouds and built at once
+    (build_native_batch); get() hands out ((i, (pc1, pc2)), NativeLattice, event) per batch, i its first pair, the
+    last batch holding what is left; every pair of a batch must have the same point counts.  The
     consumer's stream must wait for `event`, and must keep the pair and the lattice referenced until its
     own work on them is done (they were allocated on the lattice stream).  get() resumes, round robin, each
     pair whose counts have already landed until the oldest is complete, and blocks only when no pair can
     move."""
 
-    def __init__(self, gen, source, first, count, depth=2, stream=None, for_training=False, native=False, threaded=False):
+    def __init__(self, gen, source, first, count, depth=2, stream=None, for_training=False, native=False, threaded=False,
+                 batch=1):
+        self.batch = int(batch)
+        if not 1 <= self.batch <= MAX_BATCH:
+            raise _lib.HplError('LatticePipeline: batch %d (1 .. %d)' % (self.batch, MAX_BATCH))
+        if self.batch > 1:
+            if not native or for_training:
+                raise _lib.HplError('LatticePipeline: batches need the native builder and are for inference only')
+            one, end = source, first + count
+
+            def source(i):              # pairs i .. i + B - 1 (fewer at the end) stacked into (B, 3, N) clouds
+                items = [one(k) for k in range(i, min(i + self.batch, end))]
+                return torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items])
+            count = (count + self.batch - 1) // self.batch        # builds; _next / _end count them from `first` on
         self.native = native            # builds driven by csrc/lattice_builder.hip (NativeLatticeBuild)
         self.gen, self.source, self.depth = gen, source, max(1, int(depth))
         # `stream` may be a list: consecutive pairs are built on alternating streams, so the launch-latency chains of
@@ -297,10 +324,11 @@ class LatticePipeline(object):
                 depth = 1
         while len(self._inflight) < depth and self._next < self._end:
             st = self.streams[self._next % len(self.streams)]
+            i = self._first + (self._next - self._first) * self.batch        # first pair of the build
             with torch.cuda.stream(st):                 # a reader's host-to-device copies belong to this stream too
-                item = self.source(self._next)
+                item = self.source(i)
             cls = NativeLatticeBuild if self.native else LatticeBuild
-            b = cls(self.gen, item[0], item[1], st, self.for_training, tag=(self._next, item))
+            b = cls(self.gen, item[0], item[1], st, self.for_training, tag=(i, item))
             if not self.native:
                 b.advance()
             self._inflight.append(b)
@@ -345,6 +373,8 @@ class LatticePipeline(object):
 def to_reference_format(lat):
     """DeviceLattice -> the reference's generated_data (transforms.py:471-483): list of dicts of
     int64 / float32 tensors (on the device), absent tables as zeros(1)."""
+    if getattr(lat, 'batch', 1) > 1:
+        raise _lib.HplError('to_reference_format: the lattice holds a batch of %d pairs; the wire format is one pair' % lat.batch)
     out = []
     for lv in lat.levels:
         d = {}
@@ -372,6 +402,21 @@ def to_reference_format(lat):
 
 # ----------------------------------------------------------------------------- native builder
 HPL_ENOMEM = -4
+MAX_BATCH = 64          # pairs per batched build (csrc/lattice_fused.h MAX_BATCH)
+
+
+def check_batch(pc1, pc2):
+    """Argument checks of a batched build (no launch): pc1 (B, 3, N1), pc2 (B, 3, N2) with the same 1 <= B <= 64 -> B."""
+    if pc1.dim() != 3 or pc2.dim() != 3 or pc1.shape[1] != 3 or pc2.shape[1] != 3:
+        raise _lib.HplError('a batch is two (B, 3, N) tensors, got %s / %s' % (tuple(pc1.shape), tuple(pc2.shape)))
+    B = int(pc1.shape[0])
+    if int(pc2.shape[0]) != B:
+        raise _lib.HplError('pc1 holds %d clouds, pc2 %d: a batch pairs them one to one' % (B, int(pc2.shape[0])))
+    if not 1 <= B <= MAX_BATCH:
+        raise _lib.HplError('a batch holds 1 .. %d pairs, got %d' % (MAX_BATCH, B))
+    if pc1.shape[2] < 1 or pc2.shape[2] < 1:
+        raise _lib.HplError('empty clouds in a batch')
+    return B
 
 
 class NativeLattice(object):
@@ -379,6 +424,10 @@ class NativeLattice(object):
     level, all pointing into ONE device arena.  The native forward (plan.ForwardPlan) consumes `tables` as is;
     `.levels` / `.prepare()` materialise the DeviceLattice view of the same memory (zero-copy tensors over the
     arena) for everything else -- training, the reference wire format, the parity tests."""
+
+    #: pairs of the build (build_native_batch) and their vertex counts [levels][2][batch] (None for a single pair)
+    batch = 1
+    pair_counts = None
 
     def __init__(self, arena, tables, n_levels, extras, wide_up):
         self.arena, self.tables, self.n_levels, self.extras, self.wide_up = arena, tables, n_levels, extras, wide_up
@@ -461,6 +510,7 @@ class NativeLattice(object):
                 lv.corr1 = lv.corr2 = None
             levels.append(lv)
         self._view = DeviceLattice(levels, wide_up=self.wide_up)
+        self._view.batch = self.batch
         self._view._native_tables = self._native_tables
         self._view._arena = self.arena
         return self._view
@@ -555,28 +605,42 @@ class NativeLatticeBuild(object):
         self.gen, self.tag = gen, tag
         self.nb = gen.native_builder()
         self.stream = stream if stream is not None else torch.cuda.current_stream(pc1.device)
+        self.batch = check_batch(pc1, pc2) if pc1.dim() == 3 else 1
+        if self.batch > 1 and (for_training or not self.nb.fused):
+            raise _lib.HplError('batched lattices are built by the fused driver, for inference only')
+        if pc1.dim() == 3 and self.batch == 1:
+            pc1, pc2 = pc1[0], pc2[0]           # B = 1: the single-pair build as it always was
         self.pc = (pc1.contiguous().float(), pc2.contiguous().float())
         self.for_training = for_training
         self.done = False
         self.result = self.event = None
         self.handle = self.nb.acquire()
+        self._loose = False             # a batch that outgrew the bounds is begun again under the default bounds
+        st = (ctypes.c_int32 * 3)()
+        self.nb.lib.hpl_lattice_stats(self.handle, st)
+        self._fallbacks0 = int(st[2])
         self._begin()
 
     def _begin(self):
-        n0, n1 = int(self.pc[0].shape[1]), int(self.pc[1].shape[1])
+        n0, n1 = int(self.pc[0].shape[-1]), int(self.pc[1].shape[-1])
+        B = self.batch
         lib = self.nb.lib
         if self.nb.fused:
-            arr = (ctypes.c_int64 * 8)(*self.nb.bounds)
+            arr = (ctypes.c_int64 * 8)(*([0] * 8 if self._loose else self.nb.bounds))
             check(lib.hpl_lattice_set_bounds(self.handle, arr), 'hpl_lattice_set_bounds')
         while True:
-            nbytes = (32 << 20) + self.nb.bytes_per_point * (n0 + n1)
+            nbytes = (32 << 20) + self.nb.bytes_per_point * B * (n0 + n1)
             if self.nb.fused:
                 # the fused layout is known up front; the staged fallback (a pair that outgrew a bound) reuses the arena
-                nbytes = max(nbytes, int(lib.hpl_lattice_arena_bytes(self.handle, n0, n1)) + 4096)
+                nbytes = max(nbytes, int(lib.hpl_lattice_arena_bytes_batch(self.handle, B, n0, n1)) + 4096)
             with torch.cuda.stream(self.stream):
                 self.arena = torch.empty(nbytes, dtype=torch.uint8, device=self.pc[0].device)
-                rc = self.nb.lib.hpl_lattice_begin(self.handle, ptr(self.pc[0]), ptr(self.pc[1]), n0, n1,
-                                                   self.arena.data_ptr(), nbytes, stream())
+                if B > 1:
+                    rc = lib.hpl_lattice_begin_batch(self.handle, ptr(self.pc[0]), ptr(self.pc[1]), B, n0, n1,
+                                                     self.arena.data_ptr(), nbytes, stream())
+                else:
+                    rc = lib.hpl_lattice_begin(self.handle, ptr(self.pc[0]), ptr(self.pc[1]), n0, n1,
+                                               self.arena.data_ptr(), nbytes, stream())
             if rc != HPL_ENOMEM:
                 check(rc, 'hpl_lattice_begin')
                 return
@@ -591,6 +655,10 @@ class NativeLatticeBuild(object):
         d = ctypes.c_int(0)
         with torch.cuda.stream(self.stream), torch.no_grad():
             rc = self.nb.lib.hpl_lattice_advance(self.handle, ctypes.byref(d))
+            if rc == HPL_ENOMEM and self.batch > 1:     # a batch outgrew its bounds, its rebuild needs a bigger arena
+                self._loose = True
+                self._begin()
+                return False
             if rc == HPL_ENOMEM:               # the arena overflowed at this level: start over with a bigger one
                 self.nb.bytes_per_point *= 2
                 self._begin()
@@ -605,19 +673,32 @@ class NativeLatticeBuild(object):
                 extras = (ctypes.c_void_p * (2 * n))()
                 used = ctypes.c_int64(0)
                 check(self.nb.lib.hpl_lattice_extras(self.handle, extras, ctypes.byref(used)), 'hpl_lattice_extras')
+                pair_counts = None
+                if self.batch > 1:
+                    pc = (ctypes.c_int64 * (n * 2 * self.batch))()
+                    check(self.nb.lib.hpl_lattice_pair_counts(self.handle, pc), 'hpl_lattice_pair_counts')
+                    pair_counts = np.frombuffer(pc, dtype=np.int64).reshape(n, 2, self.batch).copy()
                 if self.nb.fused:
                     st = (ctypes.c_int32 * 3)()
                     self.nb.lib.hpl_lattice_stats(self.handle, st)
                     self.nb.launches = int(st[0])
-                    self.nb.fallbacks += 0 if st[1] else 1
+                    if self.batch > 1:
+                        self.nb.fallbacks += int(st[2]) - self._fallbacks0      # (rebuilt on the fused path: counted by the library)
+                    else:
+                        self.nb.fallbacks += 0 if st[1] else 1
                     first = not any(self.nb.seen)
-                    self.nb.observe([(int(arr[L].H0), int(arr[L].H1)) for L in range(n)])
+                    if pair_counts is not None:       # bounds are per pair: the largest pair of the batch
+                        self.nb.observe([(int(pair_counts[L, 0].max()), int(pair_counts[L, 1].max())) for L in range(n)])
+                    else:
+                        self.nb.observe([(int(arr[L].H0), int(arr[L].H1)) for L in range(n)])
                     if first:
                         torch.cuda.empty_cache()       # (the loose first arena's block would otherwise stay reserved beside the tight ones)
                 self.nb.release(self.handle)
                 self.handle = None
                 lat = NativeLattice(self.arena, arr, n, [int(e or 0) for e in extras], self.gen.wide_up)
                 lat.arena_used = used.value
+                if self.batch > 1:
+                    lat.batch, lat.pair_counts = self.batch, pair_counts
                 if self.for_training:
                     lat = lat.device_lattice().prepare(True)        # tap lists, symmetry verdicts: the Python tables
                 self.result, self.done = lat, True

@@ -561,7 +561,11 @@ class ForwardPlan(object):
         return slot, ws
 
     def __call__(self, pc1, pc2, lat):
-        """pc1, pc2 (1, 3, N) or (3, N) device tensors -> flow (1, 3, N0) (a transposed view of an [N0, 3] matrix)."""
+        """pc1, pc2 (1, 3, N) or (3, N) device tensors -> flow (1, 3, N0) (a transposed view of an [N0, 3] matrix);
+        (B, 3, N) tensors and a lattice of build_native_batch with the same B -> flow (B, 3, N0) (hpl_plan_run_batch)."""
+        B = int(getattr(lat, 'batch', 1) or 1)
+        if B > 1 or (pc1.dim() == 3 and pc1.shape[0] > 1):
+            return self._run_batch(pc1, pc2, lat, B)
         p1 = pc1[0] if pc1.dim() == 3 else pc1
         p2 = pc2[0] if pc2.dim() == 3 else pc2
         if not (p1.is_contiguous() and p2.is_contiguous() and p1.dtype == torch.float32):
@@ -583,6 +587,29 @@ class ForwardPlan(object):
         ev.record()
         self._fence[slot] = ev
         return out.t().unsqueeze(0)
+
+    def _run_batch(self, pc1, pc2, lat, B):
+        if pc1.dim() != 3 or pc2.dim() != 3 or pc1.shape[0] != B or pc2.shape[0] != B:
+            raise _lib.HplError('a lattice of %d pairs takes (%d, 3, N) clouds, got %s / %s'
+                                % (B, B, tuple(pc1.shape), tuple(pc2.shape)))
+        p1, p2 = pc1.contiguous().float(), pc2.contiguous().float()
+        arr, n, _ = level_tables(lat, self.hint)
+        if arr[0].n0 != B * p1.shape[2] or arr[0].n1 != B * p2.shape[2]:
+            raise _lib.HplError('lattice was built for %d / %d points, got %d x %d / %d x %d'
+                                % (arr[0].n0, arr[0].n1, B, p1.shape[2], B, p2.shape[2]))
+        nlev = self.NLEV
+        need = self._lib.hpl_plan_workspace_bytes(self.handle, arr, nlev)
+        if need < 0:
+            raise _lib.HplError('hpl_plan_workspace_bytes: %s' % self._lib.hpl_last_error().decode())
+        slot, ws = self.workspace(need + self._lib.hpl_plan_batch_extra_bytes(arr, nlev), p1.device)
+        self._wait_images()
+        out = torch.empty((B, p1.shape[2], 3), dtype=torch.float32, device=p1.device)
+        check(self._lib.hpl_plan_run_batch(self.handle, arr, nlev, B, ptr(p1), ptr(p2), ptr(out), ws.data_ptr(), ws.numel(),
+                                           stream()), 'hpl_plan_run_batch')
+        ev = torch.cuda.Event()
+        ev.record()
+        self._fence[slot] = ev
+        return out.transpose(1, 2)
 
     # ---- profiling of the dominant launches (bench.py)
     def profile(self, tag):

@@ -512,6 +512,8 @@ class TrainPlan(ForwardPlan):
     def step(self, pc1, pc2, sf, lat):
         """Enqueue one training step on the current stream: -> (flow (1, 3, N0), loss tensor [1]) or None when the lattice needs the
         autograd path.  The gradients are complete (and, with several ranks, averaged) once `finish()` has been called."""
+        if getattr(lat, 'batch', 1) > 1:
+            raise _lib.HplError('the native training step takes one pair: a lattice of %d pairs is for batched inference' % lat.batch)
         tb = self.tables(lat)
         if tb is False:
             return None

@@ -657,6 +657,15 @@ int hpl_plan_guard_trips(hpl_plan *plan, int64_t *count);
  * (hpl_gconv_desc.clock_probe): they accumulate their samples there. */
 int hpl_plan_clock_probe(hpl_plan *plan, int64_t *clock_probe);
 int hpl_plan_profile_read(hpl_plan *plan, int *launches, float *total_ms);
+/* Batched inference (the reference's forward takes one pair: README.md:57, models/HPLFlowNet.py:238-430).  `levels` are
+ * the tables of a batch of `batch` pairs built by hpl_lattice_begin_batch: one pair of clouds whose rows are pair-major
+ * and whose tables link no two pairs, so the program runs unchanged on the summed row counts.  pc1 (batch, 3, n0 / batch),
+ * pc2 (batch, 3, n1 / batch) DEVICE float32; out (DEVICE) receives the flow as (batch, n0 / batch, 3) rows.  One launch
+ * lays the clouds out pair-major in the workspace's tail: workspace_bytes >= hpl_plan_workspace_bytes +
+ * hpl_plan_batch_extra_bytes.  batch = 1 is hpl_plan_run. */
+int64_t hpl_plan_batch_extra_bytes(const hpl_level_tables *levels /* HOST */, int n_levels);
+int hpl_plan_run_batch(hpl_plan *plan, const hpl_level_tables *levels /* HOST */, int n_levels, int batch, const float *pc1,
+                       const float *pc2, float *out, void *workspace, int64_t workspace_bytes, hplStream stream);
 
 
 /* ------------------------------------------------------------------------ *
@@ -703,6 +712,21 @@ int hpl_lattice_stats(const hpl_lattice *b, int32_t *out /* HOST, 3 */);
 /* pc1 (3, n0), pc2 (3, n1) float32 DEVICE, must stay valid until the build is complete */
 int hpl_lattice_begin(hpl_lattice *b, const float *pc1, const float *pc2, int64_t n0, int64_t n1, void *arena,
                       int64_t arena_bytes, hplStream stream);
+/* A batch of `batch` pairs (1 .. 64) in ONE fused build (transforms/transforms.py:358-485 per pair; the reference builds one
+ * pair per call, README.md:57): pc1 (batch, 3, n0), pc2 (batch, 3, n1) float32 DEVICE, contiguous, read in place.  The
+ * tables are those of one pair of clouds of batch x n0 / batch x n1 pair-major points: pair b's vertices follow pair
+ * b - 1's at every level and no table links two pairs; pair b's slice of every table is its single-pair build's plus the
+ * offsets.  Same enqueue (about 33 launches) and ONE read-back whatever `batch` is.  Bounds (hpl_lattice_set_bounds) are per
+ * pair; a batch that outgrows them is rebuilt on the fused path under the default bounds (hpl_lattice_stats out[2] counts
+ * it; HPL_ENOMEM from hpl_lattice_advance if that needs a bigger arena: set the bounds to 0 and begin again).  A pair whose
+ * key range at some level does not fit below the pair digit (63 - ceil(log2 batch) bits) fails the build with HPL_EINVAL.  batch = 1 is hpl_lattice_begin.
+ * Fused builders only. */
+int hpl_lattice_begin_batch(hpl_lattice *b, const float *pc1, const float *pc2, int64_t batch, int64_t n0, int64_t n1,
+                            void *arena, int64_t arena_bytes, hplStream stream);
+/* the arena hpl_lattice_begin_batch needs for `batch` pairs of (n0, n1) points under the current bounds (-1: bad arguments) */
+int64_t hpl_lattice_arena_bytes_batch(const hpl_lattice *b, int64_t batch, int64_t n0, int64_t n1);
+/* vertices of every pair of the finished build: out[(L * 2 + cloud) * batch + pair], n_levels x 2 x batch entries */
+int hpl_lattice_pair_counts(const hpl_lattice *b, int64_t *out /* HOST */);
 /* 1 if hpl_lattice_advance would not block (the pending read-back has landed, or the build is done), else 0 */
 int hpl_lattice_ready(hpl_lattice *b);
 /* *done = 1 once every launch of the build has been enqueued (the tables are valid for work ordered behind them
