@@ -623,7 +623,9 @@ class ForwardPlan(object):
 
     def guard_trips(self):
         """Launches of this plan's runs that took the second pass of the fp16-pair form's range guard (hpl_plan_guard_trips;
-        synchronises with the device)."""
+        synchronises with the device first: the library's read-back does not order against the non-blocking streams the runs
+        were issued on)."""
+        torch.cuda.synchronize()
         n = ctypes.c_int64(0)
         check(self._lib.hpl_plan_guard_trips(self.handle, ctypes.byref(n)), 'hpl_plan_guard_trips')
         return int(n.value)

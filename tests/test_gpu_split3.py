@@ -5,6 +5,8 @@ the error against the exact result is of the fp32 rounding class -- triples: not
 largest error not larger than the fp32 kernel's, mean error within 1.4 x of it (a sequential fp32 dot product measures
 1.4 x) -- on dense and gathered launches, with and without row orders / tile tables, including the tails (partial tiles,
 partial slices, absent rows, taps straddling slices)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -336,3 +338,294 @@ def test_range_guard_word_from_the_epilogue_is_conservative():
             assert got == true_min
         else:
             assert true_min * 2.0 ** -8 <= got <= true_min, (got, true_min)
+
+
+# --------------------------------------------------------------------------- the range guard's second launch, form by form
+# Every launch below has an operand whose rows span 10 decades (the 'quiet_rows' construction above), so the first launch defers
+# and the second (GUARD = true) finishes -- or, in the 'channels' construction, has nothing to guard.  Columns: shape, table
+# density, row order, split over K, and what the epilogue carries (b: bias, r: residual, w: residual wrapped at res_mod < M,
+# a: LeakyReLU, 2: second destination, s: strided destination with ldy % 4 != 0).  The comment names the instance it reaches.
+GUARD_CASES = {
+    'splitk_finish4':     (9433, 388, 15, 256, 0.8, None, True, ''),        # second partial set; k_gconv_finish4 adds 2 x 3 sets
+    'splitk_finish_ldy':  (8200, 132, 15, 256, 0.6, None, True, 'as'),      # the same into Y with ldy = 257: scalar k_gconv_finish
+    'splitk_epilogue':    (9433, 388, 15, 256, 0.8, None, True, 'bra2'),    # the finish applies bias, residual, act, Y2 once
+    'epilogue_256':       (16600, 64, 8, 512, 0.8, 'tiles', False, 'bra2'),  # k_gconv3w<8,4,2,true>: defer, then res = Y, no bias
+    'wrapped_res':        (16437, 128, 1, 256, 1.0, None, False, 'bwa2'),   # k_gconv3w<1,4,2,true>: M = 2 res_mod + 37
+    'taps15_tiles':       (16500, 64, 15, 256, 0.5, 'tiles', False, 'ba'),  # k_gconv3w<15,4,2,true>
+    'tile128_dense':      (8192, 256, 1, 320, 1.0, None, False, 'bra'),     # k_gconv3<2,1,2,3,true>
+    'tile128_gathered':   (16500, 128, 8, 580, 0.45, 'perm', False, 'a2'),  # k_gconv3<2,8,2,3,true>
+    'tile128_taps15':     (16500, 64, 15, 320, 0.5, 'tiles', False, 'ba'),  # k_gconv3<2,15,2,3,true>
+}
+RES_MOD = 8200
+
+
+def _skip_unless_pairs():
+    from hplflownet_amd import ops
+    if ops.SPLIT_PLANES != 2 or not ops.SPLIT3:
+        pytest.skip('the range guard belongs to the fp16-pair form (HPL_MATH=f16x2, the default)')
+
+
+def _bits(x):
+    return int(np.float32(float(x)).view(np.uint32))
+
+
+def _word_trips(amax, word):
+    """gconv_common.h guard_tripped on host values: the matrix's largest magnitude 2^18 or more above the smallest row maximum"""
+    am = _bits(amax)
+    rmin = (~int(word) & 0xffffffff) if int(word) else am
+    return (am >> 23) >= (rmin >> 23) + 18 and (am >> 23) < 255
+
+
+def _quiet_blocks(rows_a, M, F, density, seed):
+    """row scales from 1e-7 to 1e3 in blocks of 128 rows, and a table whose taps stay inside the block of their output row: an
+    output row of a quiet block sums quiet rows only (with sources anywhere, the loudest of a row's ~10 taps would hide it)"""
+    g = torch.Generator(device='cpu').manual_seed(seed)
+    scale = 10.0 ** (10 * torch.rand((rows_a + 127) // 128, 1, generator=g, dtype=torch.float64) - 7)
+    scale = scale.repeat_interleave(128, dim=0)[:rows_a].float().to(DEV)
+    if F == 1:
+        return scale, None
+    m = torch.arange(M, dtype=torch.int64)
+    nbr = ((m // 128) * 128 + torch.randint(0, 128, (F, M), generator=g)).clamp(max=rows_a - 1).int()
+    nbr[torch.rand((F, M), generator=g) > density] = -1
+    nbr[0] = m.int()
+    return scale, nbr.to(DEV)
+
+
+def _word_value(word):
+    return float(np.uint32(~int(word) & 0x7fffffff).view(np.float32))
+
+
+def _guard_operands(name, quiet, seed=21):
+    """operands of GUARD_CASES[name]: A with quiet rows (or loud channels), the weight image, table and row order, and an
+    epilogue on the scale of each output row -- a bias 1e-2 of the quietest row's magnitude sum and a residual half of each
+    row's own -- so that every row's result stays dominated by its own products (quiet rows stay quiet)."""
+    from hplflownet_amd import ops
+    M, C, F, N, density, order, splitk, epi = GUARD_CASES[name]
+    torch.manual_seed(seed)
+    rows_a = M if F == 1 else M + 37
+    A = torch.randn(rows_a, C, device=DEV)
+    if quiet:
+        scale, nbr = _quiet_blocks(rows_a, M, F, density, seed)
+        A *= scale if F > 1 else 10.0 ** (10 * torch.rand(rows_a, 1, device=DEV) - 7)      # rows from 1e-7 to 1e3
+        A[50:60] = 0
+    else:
+        A *= torch.exp(4 * torch.randn(1, C, device=DEV))
+        A[:, 37] *= 1e6
+        nbr = _table(M, rows_a, F, density, seed) if F > 1 else None
+    Wt = torch.zeros(ops.round_up(F * C, 32), ops.round_up(N, 4), device=DEV)
+    Wt[:F * C, :N] = torch.randn(F * C, N, device=DEV) / (F * C) ** 0.5
+    perm = tiles = None
+    if order is not None:
+        perm = ops.tap_order(nbr)
+        if order == 'tiles':
+            tiles = ops.tile_index(nbr, perm, BM=128)
+    mag = _ref64(A.abs(), nbr, M, C, F, Wt.abs(), N)
+    rowmag = mag.max(dim=1).values
+    kw = dict(row_perm=perm, tiles=tiles, split_k=splitk)
+    bias = res = None
+    if 'b' in epi:
+        kw['bias'] = bias = (torch.randn(N, device=DEV, dtype=torch.float64) * 1e-2 * float(rowmag[rowmag > 0].min())).float()
+    if 'r' in epi or 'w' in epi:
+        R = RES_MOD if 'w' in epi else M
+        rs = torch.full((R,), float('inf'), dtype=torch.float64, device=DEV)
+        rs = rs.scatter_reduce(0, torch.arange(M, device=DEV) % R, rowmag, 'amin')
+        kw['res'] = res = (torch.randn(R, N, device=DEV, dtype=torch.float64) * 0.5 * rs[:, None]).float()
+        if 'w' in epi:
+            assert M == 2 * R + 37
+            kw['res_mod'] = R
+    if 'a' in epi:
+        kw['act'] = ops.ACT_LEAKY
+    ref = _ref64(A, nbr, M, C, F, Wt, N)
+    if bias is not None:
+        ref += bias.double()
+        mag += bias.abs().double()
+    if res is not None:
+        rr = res.double()[torch.arange(M, device=DEV) % res.shape[0]]
+        ref += rr
+        mag += rr.abs()
+    if 'a' in epi:
+        ref = torch.where(ref > 0, ref, ops.LEAKY_RATE * ref)
+    return dict(A=A, nbr=nbr, M=M, C=C, F=F, Wt=Wt, N=N, kw=kw, ref=ref, mag=mag, epi=epi, splitk=splitk)
+
+
+def _launch(o, Wt3, guard=True, trips=None, slots=None):
+    """one gconv_raw launch of the case; -> (Y, the second destination or None, the parent of a strided Y or None)"""
+    from hplflownet_amd import ops
+    M, N = o['M'], o['N']
+    kw = dict(o['kw'])
+    out = parent = out2 = None
+    if 's' in o['epi']:
+        parent = torch.full((M, N + 1), 7.0, device=DEV)
+        out = parent[:, :N]
+    if '2' in o['epi']:
+        out2 = torch.full((M // 2 + 3 + 5, N), 7.0, device=DEV)          # rows2 = M // 2 + 3; the five rows below stay untouched
+        kw.update(out2=out2, rows2=M // 2 + 3)
+    if slots is not None:
+        kw.update(y_amax=slots[0], y_guard=slots[1])
+    y = ops.gconv_raw(o['A'], o['nbr'], M, o['C'], o['F'], o['Wt'], N, out=out, Wt3=Wt3, guard=guard, guard_trips=trips, **kw)
+    return y, out2, parent
+
+
+def _check_destinations(o, y, out2, parent):
+    M, N = o['M'], o['N']
+    if out2 is not None:
+        assert torch.equal(out2[:M // 2 + 3], y[:M // 2 + 3]) and bool((out2[M // 2 + 3:] == 7.0).all())
+    if parent is not None:
+        assert bool((parent[:, N] == 7.0).all())
+
+
+def _written_sets(ws, M, N):
+    """partial sets of M x N the launch left in the (NaN-filled) split-K scratch: they are written from its start, whole"""
+    done = int((~torch.isnan(ws)).sum())
+    assert done % (M * N) == 0 and bool((~torch.isnan(ws[:done])).all()), done
+    return done // (M * N)
+
+
+@pytest.mark.parametrize('name', list(GUARD_CASES))
+def test_range_guard_second_launch_in_every_form(name):
+    """A tripped guard in every form its second launch finishes (GUARD_CASES): the result against float64 at the bars of
+    test_range_guard_keeps_quiet_rows_fp32_class -- row-wise error <= 4 x the fp32-MFMA kernel's and < 2e-6, the unguarded
+    pair form > 100 x worse -- with the epilogue (bias, residual, LeakyReLU, second destination) applied exactly once.  The
+    published magnitudes are those of the FINAL Y: y_amax exact, the guard word between 2^-8 of the smallest row maximum and
+    it (exact behind split-K), and it trips the next launch's guard where hpl_amax_rows' word does.  Split-K launches leave
+    exactly two sets of partial tiles per share (scratch filled with NaN beforehand)."""
+    from hplflownet_amd import ops
+    _skip_unless_pairs()
+    o = _guard_operands(name, quiet=True)
+    M, N = o['M'], o['N']
+    W3 = ops.weight_split3(o['Wt'], planes=2)
+    trips = torch.zeros(1, dtype=torch.int32, device=DEV)
+    slots = (torch.zeros(1, device=DEV), torch.zeros(1, dtype=torch.int32, device=DEV))
+    ws = ops._splitk_workspace(o['A'].device, ops.stream())
+    ws.fill_(float('nan'))
+    y, out2, parent = _launch(o, W3, trips=trips, slots=slots)
+    torch.cuda.synchronize()
+    if o['splitk']:
+        s2 = _written_sets(ws, M, N)
+        assert s2 >= 4 and s2 % 2 == 0, s2                 # splits >= 2, and the second set of the residual pass behind the first
+    _check_destinations(o, y, out2, parent)
+    y_off, _, _ = _launch(o, W3, guard=False)
+    y32, _, _ = _launch(o, None)
+    assert int(trips) == 1, 'the guard did not trip'
+    assert not torch.equal(y, y32), 'the pair form did not take this launch'
+    live = o['mag'].max(dim=1).values > 0
+    e, e_off, e32 = [float(_rowwise(x, o['ref'], o['mag'])[live].max()) for x in (y, y_off, y32)]
+    print('%s: row-wise err / sum|a||w|: guarded pairs %.3g, unguarded %.3g, fp32 MFMA %.3g' % (name, e, e_off, e32))
+    assert torch.isfinite(y).all()
+    assert e <= 4 * e32 and e < 2e-6
+    assert e_off > 100 * e
+    # the magnitudes the launch publishes are those of what it stored last
+    assert float(slots[0]) == float(y.abs().max())
+    rm = y.abs().max(dim=1).values
+    true_min = float(rm[rm > 0].min())
+    got = _word_value(slots[1])
+    assert true_min * 2.0 ** -8 <= got <= true_min, (got, true_min)
+    if o['splitk']:
+        assert got == true_min
+    a_exact, g_exact = ops.amax_rows(y)
+    assert float(a_exact) == float(slots[0]) and _word_trips(a_exact, g_exact)
+    assert _word_trips(slots[0], slots[1])                # the words the executor hands the next launch trip its guard too
+
+
+@pytest.mark.parametrize('name', ['splitk_finish4', 'splitk_finish_ldy', 'splitk_epilogue', 'epilogue_256', 'wrapped_res',
+                                  'tile128_dense'])
+def test_range_guard_that_does_not_trip_changes_nothing(name):
+    """The same forms with nothing to guard (the 'channels' construction): the guarded launch is the unguarded one bit for bit,
+    second destination included, and a split-K launch leaves ONE set of partial tiles -- the finish does not add the second set
+    (the scratch is NaN before the guarded launch: a finish that read it would show)."""
+    from hplflownet_amd import ops
+    _skip_unless_pairs()
+    o = _guard_operands(name, quiet=False)
+    M, N = o['M'], o['N']
+    W3 = ops.weight_split3(o['Wt'], planes=2)
+    y_off, out2_off, _ = _launch(o, W3, guard=False)
+    trips = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ws = ops._splitk_workspace(o['A'].device, ops.stream())
+    ws.fill_(float('nan'))
+    y, out2, parent = _launch(o, W3, trips=trips)
+    torch.cuda.synchronize()
+    if o['splitk']:
+        assert _written_sets(ws, M, N) >= 2
+    assert int(trips) == 0
+    assert torch.isfinite(y).all() and torch.equal(y, y_off)
+    if out2 is not None:
+        assert torch.equal(out2, out2_off)
+    _check_destinations(o, y, out2, parent)
+    assert not torch.equal(y, _launch(o, None)[0]), 'the pair form did not take this launch'
+
+
+def _passes(A, nbr, M, C, F, Wt, N, bias, W3, guard=True, trips=None):
+    """ops.gconv_passes' loop over tap ranges of 15 with the split image given (None: the fp32-MFMA kernel)"""
+    from hplflownet_amd import ops
+    y = None
+    for i, f0 in enumerate(range(0, F, ops.MAX_TAPS_PER_PASS)):
+        f1 = min(F, f0 + ops.MAX_TAPS_PER_PASS)
+        y = ops.gconv_raw(A, nbr[f0:f1], M, C, f1 - f0, Wt[f0 * C:], N, bias=bias if i == 0 else None,
+                          act=ops.ACT_LEAKY if f1 == F else ops.ACT_NONE, res=None if i == 0 else y, out=y,
+                          Wt3=W3.rows_from(f0 * C, Wt.shape[1]) if W3 is not None else None, guard=guard, guard_trips=trips)
+    return y
+
+
+def test_range_guard_in_every_pass_of_a_wide_stencil():
+    """gconv_passes over 33 taps: three passes, each tripping on the same operand; pass i adds pass i-1's Y in place (the second
+    launch of pass i then reads Y that its own first launch deferred).  Bias in the first pass, LeakyReLU in the last.
+    Same bars as test_range_guard_second_launch_in_every_form; ops.gconv_passes gives the same bits."""
+    from hplflownet_amd import ops
+    _skip_unless_pairs()
+    torch.manual_seed(23)
+    M, C, F, N = 16500, 64, 33, 256
+    scale, nbr = _quiet_blocks(M + 37, M, F, 0.6, 23)
+    A = torch.randn(M + 37, C, device=DEV) * scale
+    Wt = torch.zeros(ops.round_up(F * C, 32), N, device=DEV)
+    Wt[:F * C] = torch.randn(F * C, N, device=DEV) / (F * C) ** 0.5
+    mag = _ref64(A.abs(), nbr, M, C, F, Wt.abs(), N)
+    rowmag = mag.max(dim=1).values
+    bias = torch.randn(N, device=DEV) * 1e-2 * float(rowmag[rowmag > 0].min())
+    mag += bias.abs().double()
+    ref = _ref64(A, nbr, M, C, F, Wt, N, bias, ops.LEAKY_RATE)
+    W3 = ops.weight_split3(Wt, planes=2)
+    trips = torch.zeros(1, dtype=torch.int32, device=DEV)
+    y = _passes(A, nbr, M, C, F, Wt, N, bias, W3, trips=trips)
+    y_off = _passes(A, nbr, M, C, F, Wt, N, bias, W3, guard=False)
+    y32 = _passes(A, nbr, M, C, F, Wt, N, bias, None)
+    assert torch.equal(ops.gconv_passes(A, nbr, M, C, F, Wt, N, bias=bias, act=ops.ACT_LEAKY), y)
+    assert int(trips) == 3 and not torch.equal(y, y32)
+    live = mag.max(dim=1).values > 0
+    e, e_off, e32 = [float(_rowwise(x, ref, mag)[live].max()) for x in (y, y_off, y32)]
+    print('passes F=%d: row-wise err / sum|a||w|: guarded pairs %.3g, unguarded %.3g, fp32 MFMA %.3g' % (F, e, e_off, e32))
+    assert e <= 4 * e32 and e < 2e-6
+    assert e_off > 100 * e
+
+
+def test_generic_epilogue_is_bit_identical_behind_a_tripped_guard():
+    """HPL_SPLIT3_EPILOGUE=0 (the generic epilogue) against the fast one on launches whose guard trips: bias, residual,
+    LeakyReLU and a second destination on a 256-wide tile; a split-K launch with the same epilogue -- same bits, one trip each."""
+    _skip_unless_pairs()
+    import subprocess
+    import sys
+    import tempfile
+    code = (
+        "import sys, torch\n"
+        "sys.path.insert(0, %r)\n"
+        "sys.path.insert(0, %r)\n"
+        "import test_gpu_split3 as T\n"
+        "from hplflownet_amd import ops\n"
+        "outs = []\n"
+        "for name in ('epilogue_256', 'splitk_epilogue'):\n"
+        "    o = T._guard_operands(name, quiet=True)\n"
+        "    trips = torch.zeros(1, dtype=torch.int32, device='cuda')\n"
+        "    y, out2, _ = T._launch(o, ops.weight_split3(o['Wt'], planes=2), trips=trips)\n"
+        "    outs.append((y.cpu(), out2.cpu(), int(trips)))\n"
+        "torch.save(outs, sys.argv[1])\n" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                             os.path.dirname(os.path.abspath(__file__))))
+    outs = []
+    with tempfile.TemporaryDirectory() as d:
+        for mode in ('1', '0'):
+            f = os.path.join(d, 'y%s.pt' % mode)
+            r = subprocess.run([sys.executable, '-c', code, f], env=dict(os.environ, HPL_SPLIT3_EPILOGUE=mode), capture_output=True,
+                               text=True, timeout=600)
+            assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+            outs.append(torch.load(f))
+    for fast, generic in zip(*outs):
+        assert fast[2] == 1 and generic[2] == 1
+        assert torch.equal(fast[0], generic[0]) and torch.equal(fast[1], generic[1])
