@@ -175,6 +175,8 @@ _SIGNATURES = {
     'hpl_plan_run_batch': (ctypes.c_int, [c_vp, ctypes.POINTER(LevelTables), ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64,
                                           c_vp]),
     'hpl_plan_batch_extra_bytes': (c_i64, [ctypes.POINTER(LevelTables), ctypes.c_int]),
+    'hpl_batch_stage': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'hpl_epe3d_pairs': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_vp]),
     'hpl_plan_set_unlayout': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.c_int]),
     'hpl_plan_profile': (ctypes.c_int, [c_vp, ctypes.c_int]),
     'hpl_plan_guard_trips': (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64)]),

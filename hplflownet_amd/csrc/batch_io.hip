@@ -1,4 +1,5 @@
-// batch_io.hip -- batched inference around the native forward (include/hpl_bcl.h hpl_plan_run_batch).  A batch of B pairs is
+// batch_io.hip -- batched inference and training around the native program (include/hpl_bcl.h hpl_plan_run_batch,
+// hpl_batch_stage).  A batch of B pairs is
 // one pair of clouds whose rows are pair-major (csrc/lattice_fused.hip); the forward program runs on it unchanged.  Its point
 // load reads a (3, n) matrix per cloud, so the (B, 3, N) clouds are laid out as (3, B x N) in the workspace's tail first:
 // one launch over 3 x B x (N1 + N2) floats.  The flow it writes, an [B x N1][3] matrix, IS the (B, N1, 3) output.
@@ -17,6 +18,23 @@ __global__ void k_pair_major(const float *__restrict__ pc1, int64_t np1, const f
         const int64_t j = two ? i - n1 : i, np = two ? np2 : np1, rows = batch * np;
         const int64_t k = j / rows, r = j - k * rows, b = r / np, p = r - b * np;      // dst[k][r], r = b * np + p
         (two ? dst2 : dst1)[j] = (two ? pc2 : pc1)[(b * 3 + k) * np + p];
+    }
+}
+
+// (B, 3, np_a) -> (3, B * np_a) for up to three arrays a in one launch; V = float4 moves four consecutive points of a row
+// (every np_a % 4 == 0, every pointer 16-byte aligned), np_a counted in V.  Grid-stride, lanes walk the destination in order.
+template <typename V>
+__global__ void __launch_bounds__(256) k_batch_stage(const V *__restrict__ s0, const V *__restrict__ s1, const V *__restrict__ s2,
+                                                     int64_t np0, int64_t np1, int64_t np2, int batch, V *__restrict__ d0,
+                                                     V *__restrict__ d1, V *__restrict__ d2) {
+    const int64_t t0 = 3 * batch * np0, t1 = t0 + 3 * batch * np1, total = t1 + (s2 ? 3 * batch * np2 : 0);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int a = i < t0 ? 0 : (i < t1 ? 1 : 2);
+        const int64_t j = i - (a == 0 ? 0 : (a == 1 ? t0 : t1)), np = a == 0 ? np0 : (a == 1 ? np1 : np2), rows = batch * np;
+        const int64_t k = j / rows, r = j - k * rows, b = r / np, p = r - b * np;      // dst[k][r], r = b * np + p
+        const V *src = a == 0 ? s0 : (a == 1 ? s1 : s2);
+        V *dst = a == 0 ? d0 : (a == 1 ? d1 : d2);
+        dst[j] = src[(b * 3 + k) * np + p];
     }
 }
 
@@ -49,4 +67,27 @@ extern "C" int hpl_plan_run_batch(hpl_plan *plan, const hpl_level_tables *levels
     k_pair_major<<<(unsigned)imin(cdiv(total, 256), 2048), 256, 0, to_stream(stream)>>>(pc1, n0 / batch, pc2, n1 / batch, batch, s1, s2);
     HPL_CHECK_LAUNCH("hpl_plan_run_batch (pair-major clouds)");
     return hpl_plan_run(plan, levels, n_levels, s1, s2, out, workspace, need, stream);
+}
+
+extern "C" int hpl_batch_stage(int batch, int64_t n1, int64_t n2, const float *pc1, const float *pc2, const float *sf, float *dst1,
+                               float *dst2, float *dst_sf, hplStream stream) {
+    HPL_REQUIRE(pc1 && pc2 && dst1 && dst2 && (!sf || dst_sf), "hpl_batch_stage: null argument");
+    HPL_REQUIRE(batch >= 1 && batch <= 64 && n1 >= 1 && n2 >= 1, "hpl_batch_stage: %d pairs of %lld / %lld points (1 .. 64 pairs)",
+                batch, (long long)n1, (long long)n2);
+    const int64_t total = 3 * batch * (n1 + n2 + (sf ? n1 : 0));
+    const bool vec = n1 % 4 == 0 && n2 % 4 == 0 && aligned16(pc1) && aligned16(pc2) && aligned16(dst1) && aligned16(dst2) &&
+                     (!sf || (aligned16(sf) && aligned16(dst_sf)));
+    hipStream_t s = to_stream(stream);
+    if (vec) {
+        const int grid = (int)imin(cdiv(total / 4, 256), 2048);
+        k_batch_stage<float4><<<grid, 256, 0, s>>>(reinterpret_cast<const float4 *>(pc1), reinterpret_cast<const float4 *>(pc2),
+                                                   reinterpret_cast<const float4 *>(sf), n1 / 4, n2 / 4, n1 / 4, batch,
+                                                   reinterpret_cast<float4 *>(dst1), reinterpret_cast<float4 *>(dst2),
+                                                   reinterpret_cast<float4 *>(dst_sf));
+    } else {
+        const int grid = (int)imin(cdiv(total, 256), 2048);
+        k_batch_stage<float><<<grid, 256, 0, s>>>(pc1, pc2, sf, n1, n2, n1, batch, dst1, dst2, dst_sf);
+    }
+    HPL_CHECK_LAUNCH("hpl_batch_stage");
+    return HPL_OK;
 }

@@ -59,14 +59,14 @@ __global__ void __launch_bounds__(256) k_regroup(const float *__restrict__ G, in
 }
 
 // One workgroup: thread t owns points t, t + 1024, ...; per-thread partial sums in ascending point order, then a fixed
-// tree over the 1024 threads -- the loss is the same number on every run.
-__global__ void __launch_bounds__(1024) k_epe3d(const float *__restrict__ pred, const float *__restrict__ sf, int64_t N,
-                                                float *__restrict__ grad, float *__restrict__ loss) {
-    __shared__ float part[1024];
+// tree over the 1024 threads -- the loss is the same number on every run.  sf holds the N points' three components at
+// sf[0], sf[ld], sf[2 ld] (ld = N for a lone pair, B x N for a pair of a batch's pair-major matrix).
+__device__ __forceinline__ void epe3d_block(const float *__restrict__ pred, const float *__restrict__ sf, int64_t ld, int64_t N,
+                                            float *__restrict__ grad, float *__restrict__ loss, float *part) {
     const float inv_n = 1.0f / (float)N;
     float acc = 0.f;
     for (int64_t n = threadIdx.x; n < N; n += 1024) {
-        const float dx = pred[n * 3 + 0] - sf[n], dy = pred[n * 3 + 1] - sf[N + n], dz = pred[n * 3 + 2] - sf[2 * N + n];
+        const float dx = pred[n * 3 + 0] - sf[n], dy = pred[n * 3 + 1] - sf[ld + n], dz = pred[n * 3 + 2] - sf[2 * ld + n];
         const float r = sqrtf(dx * dx + dy * dy + dz * dz);
         acc += r;
         const float s = r > 0.f ? inv_n / r : 0.f;
@@ -83,6 +83,21 @@ __global__ void __launch_bounds__(1024) k_epe3d(const float *__restrict__ pred, 
         __syncthreads();
     }
     if (threadIdx.x == 0 && loss) *loss = part[0] * inv_n;
+}
+
+__global__ void __launch_bounds__(1024) k_epe3d(const float *__restrict__ pred, const float *__restrict__ sf, int64_t N,
+                                                float *__restrict__ grad, float *__restrict__ loss) {
+    __shared__ float part[1024];
+    epe3d_block(pred, sf, N, N, grad, loss, part);
+}
+
+// Workgroup b: pair b of a batch (pred rows b*n .. b*n + n - 1, sf columns likewise) exactly as k_epe3d takes a lone pair --
+// the same rows per thread, the same tree: each pair's loss is the bits hpl_epe3d returns for that pair alone.
+__global__ void __launch_bounds__(1024) k_epe3d_pairs(const float *__restrict__ pred, const float *__restrict__ sf, int batch,
+                                                      int64_t n, float *__restrict__ pair_loss) {
+    __shared__ float part[1024];
+    const int64_t b = blockIdx.x;
+    epe3d_block(pred + b * n * 3, sf + b * n, (int64_t)batch * n, n, nullptr, pair_loss + b, part);
 }
 
 __global__ void __launch_bounds__(256) k_zero_cols(float *__restrict__ dst, int64_t ldd, int64_t rows, int cols) {
@@ -237,5 +252,14 @@ extern "C" int hpl_epe3d(const float *pred, const float *sf, int64_t N, float *g
     HPL_REQUIRE(pred && sf && N > 0 && (grad || loss), "hpl_epe3d: bad arguments");
     k_epe3d<<<1, 1024, 0, to_stream(stream)>>>(pred, sf, N, grad, loss);
     HPL_CHECK_LAUNCH("hpl_epe3d");
+    return HPL_OK;
+}
+
+extern "C" int hpl_epe3d_pairs(const float *pred, const float *sf, int batch, int64_t n, float *pair_loss, hplStream stream) {
+    HPL_REQUIRE(pred && sf && pair_loss, "hpl_epe3d_pairs: null argument");
+    HPL_REQUIRE(batch >= 1 && batch <= 64 && n >= 1, "hpl_epe3d_pairs: %d pairs of %lld points (1 .. 64 pairs, n >= 1)", batch,
+                (long long)n);
+    k_epe3d_pairs<<<batch, 1024, 0, to_stream(stream)>>>(pred, sf, batch, n, pair_loss);
+    HPL_CHECK_LAUNCH("hpl_epe3d_pairs");
     return HPL_OK;
 }

@@ -144,6 +144,16 @@ class _PairFolder(object):
     def __len__(self):
         return len(self.samples)
 
+    def point_counts(self, index):
+        """(N1, N2) of a sample without loading it, when the transform fixes them (allow_less_points off: every sample it
+        passes has num_points in each cloud -- the training protocol); else the shapes of the loaded sample."""
+        t = self.transform
+        t = getattr(t, 'sampler', t)
+        if t is not None and not getattr(t, 'allow_less_points', True):
+            return (t.num_points, t.num_points)
+        s_ = self[index]
+        return (int(s_[0].shape[-1]), int(s_[1].shape[-1]))
+
     def check_counts(self):
         """None if the tree has the canonical number of samples, else a message."""
         if self.canonical is not None and self._found != self.canonical:

@@ -42,7 +42,7 @@ from . import data as data_mod
 from . import ops, parallel
 from ._lib import HplError
 from .flownet import HPLFlowNet, HPLFlowNetShallow, load_reference_checkpoint
-from .lattice import GenerateDataUnsymmetric, LatticePipeline
+from .lattice import GenerateDataUnsymmetric, LatticePipeline, NativeLatticeBuild
 from .synthetic import SCALES_FILTER_MAP, fill_module_, synthetic_pair
 
 ARCHS = {'HPLFlowNet': (HPLFlowNet, 7), 'HPLFlowNetShallow': (HPLFlowNetShallow, 5)}
@@ -109,6 +109,9 @@ class SyntheticPairs(object):
 
     def __getitem__(self, i):
         return self.items[i]
+
+    def point_counts(self, i):
+        return self.items[i][0].shape[-1], self.items[i][1].shape[-1]
 
 
 class Trainer(object):
@@ -178,20 +181,75 @@ class Trainer(object):
             self.opt.step()
         return loss.detach()
 
+    def train_step_batch(self, pc1, pc2, sf, lat):
+        """One optimiser step over B pairs: pc1, sf (B, 3, N1), pc2 (B, 3, N2) and their lattice of
+        build_native_batch(..., for_training=True) -> the B per-pair losses (device tensor, not synchronised).  The gradient is
+        the mean over the pairs (what W ranks of one pair each average); one Adam step per batch.  B = 1 is train_step."""
+        from .train_plan import check_batch_step
+        B = check_batch_step(pc1, pc2, sf, lat)
+        if B == 1:
+            return self.train_step(pc1[0], pc2[0], sf[0], lat).reshape(1)
+        if self.native_step and self.tplan is None:
+            from .train_plan import TrainPlan
+            if self.reducer is None:
+                self.reducer = parallel.GradAllReducer(self.model.parameters(), overlap=False)
+            self.tplan = TrainPlan(self.model, reducer=self.reducer)
+        if self.tplan is not None:
+            r = self.tplan.step_batch(pc1, pc2, sf, lat)
+            if r is not None:
+                self.tplan.finish()
+                if not self.tplan.adam_step(self.opt):
+                    self.opt.step()
+                self.native_steps += 1
+                return r[2]
+            self.tplan.gflat.zero_()                 # the native program refuses the batch: autograd adds into the same arena
+        else:
+            self.opt.zero_grad(set_to_none=True)
+        # pair by pair on single-pair training lattices, each loss scaled by 1 / B: the same mean-over-pairs gradient, then ONE
+        # all-reduce (in the native program's bucket order) and ONE optimiser step -- ranks keep posting the same collectives
+        losses = []
+        for b in range(B):
+            lb = self._single_lattice(pc1[b], pc2[b])
+            flow = self.model(pc1[b][None], pc2[b][None], lb)
+            loss = epe3d_loss(flow, sf[b][None])
+            (loss / B).backward()
+            losses.append(loss.detach())
+        if self.tplan is not None:
+            self.tplan.reduce_fallback()
+        elif self.reducer is not None:
+            self.reducer()
+        if self.tplan is None or not self.tplan.adam_step(self.opt):
+            self.opt.step()
+        return torch.stack(losses)
+
+    def _single_lattice(self, pc1, pc2):
+        """One pair's training lattice (tables of the backward included), built on the current stream."""
+        if self.gen.native_supported():
+            return NativeLatticeBuild(self.gen, pc1, pc2, for_training=True).finish()
+        return self.gen.build(pc1.contiguous(), pc2.contiguous()).prepare(True)
+
     # ------------------------------------------------------------------ lattice pipeline
-    def _lattices(self, data, order, training, depth=2):
+    def _lattices(self, data, order, training, depth=2, batch_size=1):
         """Yield (sample, lattice) for `order`.  Each sample is fetched once (readers may sample randomly);
         the lattices of the next `depth` samples are under construction on the side stream while the
-        current one is consumed, and the host never blocks on their vertex-count read-backs."""
+        current one is consumed, and the host never blocks on their vertex-count read-backs.  batch_size = B > 1
+        (native builder): consecutive samples of `order` with equal point counts (batch_groups) come as one stacked
+        sample ((B, 3, N) each) with one batched lattice."""
         main = torch.cuda.current_stream(self.device)
+        native = self.gen.native_supported()
         # the native (fused) builder drives both; in training it also adds the tables of the backward (tap lists, symmetry
         # verdicts) -- on a producer thread, off the thread that issues the step's launches
+        groups = None
+        if batch_size > 1:
+            if not native:
+                raise HplError('batches of %d pairs need the native lattice builder' % batch_size)
+            groups = batch_groups([point_counts(data, k) for k in order], batch_size)
         pipe = LatticePipeline(self.gen, lambda k: data[order[k]], 0, len(order), depth=depth, stream=self._side,
-                               for_training=training, native=self.gen.native_supported(),
-                               threaded=training and self.gen.native_supported())
+                               for_training=training, native=native, threaded=training and native,
+                               batch=batch_size, groups=groups)
         keep = collections.deque()
         try:
-            for _ in range(len(order)):
+            for _ in range(len(order) if groups is None else len(groups)):
                 (_, sample), lat, ev = pipe.get()
                 main.wait_event(ev)
                 yield sample, lat
@@ -206,12 +264,18 @@ class Trainer(object):
                 fin.synchronize()
 
     # ------------------------------------------------------------------ loops
-    def train_epoch(self, data, order=None):
+    def train_epoch(self, data, order=None, batch_size=1):
+        """One pass over `order`; batch_size = B > 1: one step per group of <= B consecutive samples with equal point counts
+        (train_step_batch).  -> the mean loss over the pairs of all ranks."""
         self.model.train()
         order = list(range(len(data))) if order is None else list(order)
         total = torch.zeros((), device=self.device)
-        for (pc1, pc2, sf), lat in self._lattices(data, order, True):
-            total += self.train_step(pc1, pc2, sf, lat)
+        if batch_size > 1:
+            for (pc1, pc2, sf), lat in self._lattices(data, order, True, batch_size=batch_size):
+                total += self.train_step_batch(pc1, pc2, sf, lat).sum()
+        else:
+            for (pc1, pc2, sf), lat in self._lattices(data, order, True):
+                total += self.train_step(pc1, pc2, sf, lat)
         self.epoch += 1
         tot = parallel.sum_over_ranks([float(total), float(len(order))], device=self.device)
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
@@ -290,9 +354,9 @@ class Trainer(object):
                 self.opt.load_state_dict(ck['optimizer'])
         return ck
 
-    def fit(self, train_data, val_data, epochs, ckpt_dir=None, log=print, shuffle=False):
+    def fit(self, train_data, val_data, epochs, ckpt_dir=None, log=print, shuffle=False, batch_size=1):
         for _ in range(self.epoch, epochs):
-            tr = self.train_epoch(train_data, self.shuffle.permutation(len(train_data)) if shuffle else None)
+            tr = self.train_epoch(train_data, self.shuffle.permutation(len(train_data)) if shuffle else None, batch_size)
             # validate() ends in a collective: every rank calls it whenever the split exists, also with an empty shard
             # (fewer validation samples than ranks); the decision to fall back to the train loss is taken on the
             # globally reduced sample count so that all ranks agree
@@ -313,6 +377,15 @@ class Trainer(object):
 def same_counts(a, b):
     """True if samples a and b ((pc1, pc2, sf), (3, N) each) have the same point counts: they can share a batch."""
     return a[0].shape[-1] == b[0].shape[-1] and a[1].shape[-1] == b[1].shape[-1]
+
+
+def point_counts(data, i):
+    """(N1, N2) of sample i of a reader: its point_counts(i) if it has one (no fetch), else the shapes of data[i]."""
+    f = getattr(data, 'point_counts', None)
+    if f is not None:
+        return tuple(f(i))
+    s_ = data[i]
+    return (int(s_[0].shape[-1]), int(s_[1].shape[-1]))
 
 
 def batch_groups(counts, batch_size):
@@ -344,12 +417,19 @@ def main(argv=None):
     ap.add_argument('--batch-size', type=int, default=1,
                     help='--evaluate: pairs per batched lattice build and forward (1 .. 64); consecutive pairs with equal point '
                          'counts are batched (default 1: one pair at a time)')
+    ap.add_argument('--train-batch-size', type=int, default=None,
+                    help='training: pairs per native step (1 .. 64, default 1); consecutive pairs with equal point counts share '
+                         'one batched lattice build and one step, whose gradient is the mean over them.  With W ranks the global '
+                         'batch is W x B pairs')
     ap.add_argument('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI'])
     ap.add_argument('--data-root', default=None)
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
         ap.error('--batch-size takes 1 .. 64 and applies to --evaluate (training takes one pair per step)')
+    if a.train_batch_size is not None and (a.evaluate or not 1 <= a.train_batch_size <= 64):
+        ap.error('--train-batch-size takes 1 .. 64 and applies to training (--evaluate batches with --batch-size)')
+    a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
     if a.val_pairs is None:
@@ -369,7 +449,7 @@ def main(argv=None):
         return res
     train = SyntheticPairs(a.pairs, a.points, dev, first_seed=rank * a.pairs)
     val = SyntheticPairs(a.val_pairs, a.points, dev, first_seed=1000)
-    return tr.fit(train, val, a.epochs, a.ckpt_dir, log=print if rank == 0 else (lambda *_: None))
+    return tr.fit(train, val, a.epochs, a.ckpt_dir, log=print if rank == 0 else (lambda *_: None), batch_size=a.train_batch_size)
 
 
 class _Shard(object):
@@ -396,6 +476,9 @@ class _Shard(object):
 
     def __getitem__(self, i):
         return self.reader[self.ids[i]]
+
+    def point_counts(self, i):
+        return point_counts(self.reader, self.ids[i])
 
 
 def _real_data(a, tr, dev, rank, world):
@@ -427,7 +510,8 @@ def _real_data(a, tr, dev, rank, world):
         res = tr.validate(val, a.batch_size)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
-    return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True)
+    return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,
+                  batch_size=a.train_batch_size)
 
 
 if __name__ == '__main__':

@@ -68,13 +68,15 @@ class GenerateDataUnsymmetric(object):
         """The same lattice from the native builder (one arena, one C call per level half): -> NativeLattice."""
         return NativeLatticeBuild(self, pc1, pc2).finish()
 
-    def build_native_batch(self, pc1, pc2):
+    def build_native_batch(self, pc1, pc2, for_training=False):
         """B pairs in one fused build: pc1 (B, 3, N1), pc2 (B, 3, N2) float32 device tensors -> NativeLattice with
         `batch` = B and `pair_counts` ([levels][2][B] vertices).  Its tables are those of one pair of clouds of B x N1 /
         B x N2 pair-major points (pair b's slice of every table is pair b's build_native plus offsets); the models take
-        it with the same (B, 3, N) tensors.  B = 1 is build_native of pc1[0], pc2[0]."""
+        it with the same (B, 3, N) tensors.  B = 1 is build_native of pc1[0], pc2[0].  for_training: the prepared
+        DeviceLattice view with the backward's extras on the union tables (tap lists, symmetry verdicts, bary1 / off1),
+        what train_plan.TrainPlan.step_batch takes."""
         check_batch(pc1, pc2)
-        return NativeLatticeBuild(self, pc1, pc2).finish()
+        return NativeLatticeBuild(self, pc1, pc2, for_training=for_training).finish()
 
     def build(self, pc1, pc2):
         """pc1, pc2: (3, N) float32 device tensors -> DeviceLattice (blocks on every read-back)."""
@@ -234,26 +236,36 @@ class LatticePipeline(object):
     each exactly once, and handed out in order by get() as ((i, source(i)), DeviceLattice, event); the
     `batch` = B > 1 (native builder): B consecutive pairs are stacked into (B, 3, N) clouds and built at once
     (build_native_batch); get() hands out ((i, (pc1, pc2)), NativeLattice, event) per batch, i its first pair, the
-    last batch holding what is left; every pair of a batch must have the same point counts.  The
+    last batch holding what is left; every pair of a batch must have the same point counts.  A source that returns
+    (pc1, pc2, sf) triples (training) gets stacked (pc1, pc2, sf) back.  The
     consumer's stream must wait for `event`, and must keep the pair and the lattice referenced until its
     own work on them is done (they were allocated on the lattice stream).  get() resumes, round robin, each
     pair whose counts have already landed until the oldest is complete, and blocks only when no pair can
     move."""
 
     def __init__(self, gen, source, first, count, depth=2, stream=None, for_training=False, native=False, threaded=False,
-                 batch=1):
+                 batch=1, groups=None):
         self.batch = int(batch)
         if not 1 <= self.batch <= MAX_BATCH:
             raise _lib.HplError('LatticePipeline: batch %d (1 .. %d)' % (self.batch, MAX_BATCH))
+        self._groups = None
         if self.batch > 1:
-            if not native or for_training:
-                raise _lib.HplError('LatticePipeline: batches need the native builder and are for inference only')
+            if not native:
+                raise _lib.HplError('LatticePipeline: batches need the native builder')
             one, end = source, first + count
+            # groups: the pairs of every build (lists of pair indices, each of <= B pairs with equal point counts, e.g.
+            # engine.batch_groups); by default B consecutive pairs, the last build holding what is left
+            if groups is None:
+                groups = [list(range(i, min(i + self.batch, end))) for i in range(first, end, self.batch)]
+            groups = [list(g) for g in groups]
+            if any(not 1 <= len(g) <= self.batch for g in groups):
+                raise _lib.HplError('LatticePipeline: every group holds 1 .. %d pairs' % self.batch)
+            self._groups = groups
 
-            def source(i):              # pairs i .. i + B - 1 (fewer at the end) stacked into (B, 3, N) clouds
-                items = [one(k) for k in range(i, min(i + self.batch, end))]
-                return torch.stack([it[0] for it in items]), torch.stack([it[1] for it in items])
-            count = (count + self.batch - 1) // self.batch        # builds; _next / _end count them from `first` on
+            def source(k):              # the pairs of build k stacked into (B, 3, N) clouds
+                items = [one(j) for j in groups[k]]
+                return tuple(torch.stack([it[j] for it in items]) for j in range(len(items[0])))
+            first, count = 0, len(groups)        # builds; _next / _end count them
         self.native = native            # builds driven by csrc/lattice_builder.hip (NativeLatticeBuild)
         self.gen, self.source, self.depth = gen, source, max(1, int(depth))
         # `stream` may be a list: consecutive pairs are built on alternating streams, so the launch-latency chains of
@@ -324,9 +336,10 @@ class LatticePipeline(object):
                 depth = 1
         while len(self._inflight) < depth and self._next < self._end:
             st = self.streams[self._next % len(self.streams)]
-            i = self._first + (self._next - self._first) * self.batch        # first pair of the build
+            k = self._next
+            i = self._groups[k][0] if self._groups is not None else k        # first pair of the build
             with torch.cuda.stream(st):                 # a reader's host-to-device copies belong to this stream too
-                item = self.source(i)
+                item = self.source(k)
             cls = NativeLatticeBuild if self.native else LatticeBuild
             b = cls(self.gen, item[0], item[1], st, self.for_training, tag=(i, item))
             if not self.native:
@@ -606,8 +619,8 @@ class NativeLatticeBuild(object):
         self.nb = gen.native_builder()
         self.stream = stream if stream is not None else torch.cuda.current_stream(pc1.device)
         self.batch = check_batch(pc1, pc2) if pc1.dim() == 3 else 1
-        if self.batch > 1 and (for_training or not self.nb.fused):
-            raise _lib.HplError('batched lattices are built by the fused driver, for inference only')
+        if self.batch > 1 and not self.nb.fused:
+            raise _lib.HplError('batched lattices are built by the fused driver')
         if pc1.dim() == 3 and self.batch == 1:
             pc1, pc2 = pc1[0], pc2[0]           # B = 1: the single-pair build as it always was
         self.pc = (pc1.contiguous().float(), pc2.contiguous().float())

@@ -291,6 +291,23 @@ class _Backward(object):
             self._stores(b)
 
 
+def check_batch_step(pc1, pc2, sf, lat):
+    """Argument checks of a batched training step (host only, nothing launched): pc1, sf (B, 3, N1), pc2 (B, 3, N2) and a
+    lattice built for the same B -> B."""
+    if any(getattr(x, 'dim', lambda: 0)() != 3 for x in (pc1, pc2, sf)) or pc1.shape[1] != 3 or pc2.shape[1] != 3:
+        raise _lib.HplError('a training batch is (B, 3, N) clouds and flow, got %s / %s / %s'
+                            % tuple(tuple(getattr(x, 'shape', ())) for x in (pc1, pc2, sf)))
+    B = int(pc1.shape[0])
+    if int(pc2.shape[0]) != B or tuple(sf.shape) != tuple(pc1.shape):
+        raise _lib.HplError('training batch: pc1 %s, pc2 %s and sf %s do not pair up' % (tuple(pc1.shape), tuple(pc2.shape), tuple(sf.shape)))
+    if not 1 <= B <= 64:
+        raise _lib.HplError('a training batch holds 1 .. 64 pairs, got %d' % B)
+    lb = int(getattr(lat, 'batch', 1) or 1)
+    if lb != B:
+        raise _lib.HplError('training batch of %d pairs, but the lattice was built for %d' % (B, lb))
+    return B
+
+
 class TrainPlan(ForwardPlan):
     """One model's training step as a native program.  `step(pc1, pc2, sf, lattice)` enqueues forward, loss, backward and the
     un-layout of every weight gradient; the parameters' `.grad` are views of `self.gflat` (do NOT call zero_grad(set_to_none=True)
@@ -525,6 +542,13 @@ class TrainPlan(ForwardPlan):
             p1, p2, s = p1.contiguous(), p2.contiguous(), s.contiguous()
         if arr[0].n0 != p1.shape[1] or arr[0].n1 != p2.shape[1] or s.shape[1] != p1.shape[1]:
             raise _lib.HplError('lattice was built for %d / %d points, got %d / %d' % (arr[0].n0, arr[0].n1, p1.shape[1], p2.shape[1]))
+        out = self._enqueue(arr, n, p1, p2, s, p1.shape[1])
+        self._keep = (p1, p2, s, lat)
+        return out.t().unsqueeze(0), self.loss
+
+    def _enqueue(self, arr, n, p1, p2, s, rows, after_forward=None):
+        """Forward, loss and backward of one (3, rows) pair of clouds -- a lone pair, or a batch staged pair-major -- on the
+        current stream -> the flow [rows][3]; after_forward(flow) is issued between the forward range and the backward."""
         need = self._lib.hpl_plan_workspace_bytes(self.handle, arr, n)
         if need < 0:
             raise _lib.HplError('hpl_plan_workspace_bytes: %s' % self._lib.hpl_last_error().decode())
@@ -536,7 +560,7 @@ class TrainPlan(ForwardPlan):
             del ws
             ws = self._ws['train'] = torch.empty(int(need * 1.3), dtype=torch.uint8, device=p1.device)
         self.refresh_weights()
-        out = torch.empty((p1.shape[1], 3), dtype=torch.float32, device=p1.device)
+        out = torch.empty((rows, 3), dtype=torch.float32, device=p1.device)
         st = stream()
         side = self._side.cuda_stream if self._side is not None else None
         lo = 0
@@ -546,6 +570,8 @@ class TrainPlan(ForwardPlan):
             check(self._lib.hpl_plan_run_range(self.handle, arr, n, ptr(p1), ptr(p2), ptr(s), ptr(out), ptr(self.loss), ws.data_ptr(),
                                                ws.numel(), st, side, lo, hi, join), 'hpl_plan_run_range')
         run(0, self.n_fwd, 0)
+        if after_forward is not None:
+            after_forward(out)
         torch.cuda.current_stream().wait_event(self._bwd_ready)          # the backward's weight images, the zeroed gradient arenas
         if not self.reducer._active():
             run(self.n_fwd, n_ops, 1)
@@ -563,8 +589,66 @@ class TrainPlan(ForwardPlan):
                     self.reducer.launch_flat(self.bucket_order[k])
                 lo = hi
             run(lo, n_ops, 1)
-        self._keep = (p1, p2, s, lat)
-        return out.t().unsqueeze(0), self.loss
+        return out
+
+    #: every matrix of the program stays below 2 GiB: the gather-GEMMs address their operands and epilogues, the weight-gradient
+    #: kernels their A / dY through 32-bit buffer offsets, the splat / slice launches count elements in 32 bits
+    MAX_MATRIX_BYTES = (1 << 31) - 1
+
+    def largest_matrix(self, arr, n):
+        """-> (bytes, rows, cols) of the program's largest matrix (activations, gradients, inverse tables) at the row counts
+        of the tables `arr` -- host arithmetic only."""
+        v = {SYM_N0: int(arr[0].n0), SYM_N1: int(arr[0].n1), SYM_NP: int(arr[0].n0) + int(arr[0].n1)}
+        for L in range(n):
+            t = arr[L]
+            h0, h1, m0, m1 = int(t.H0), int(t.H1), int(t.n0), int(t.n1)
+            for k, x in ((S_H0, h0), (S_H1, h1), (S_HP, h0 + h1), (S_FH0, 15 * h0), (S_IN0, m0), (S_INP, m0 + m1), (S_FH1, 15 * h1)):
+                v[lsym(L, k)] = x
+        best = (0, 0, 0)
+        for rows_sym, cols in self.prog.bufs:
+            rows = v.get(rows_sym, 0)
+            best = max(best, (rows * ops.round_up(cols, 4) * 4, rows, cols))
+        return best
+
+    @torch.no_grad()
+    def step_batch(self, pc1, pc2, sf, lat):
+        """One training step over B pairs: pc1, sf (B, 3, N1), pc2 (B, 3, N2) device tensors and a lattice of
+        lattice.GenerateDataUnsymmetric.build_native_batch(..., for_training=True) with the same B -> (flow (B, 3, N1), loss
+        tensor [1] = the mean of the pairs' EPE3D, pair_losses [B]), or None when the lattice needs the autograd path.
+
+        The batch is one pair of pair-major clouds whose tables link no two pairs: the program of step() runs
+        on it unchanged.  Its HPL_OP_EPE3D takes the mean over all B x N1 rows, which for pairs of equal N1 is the mean of the
+        per-pair losses, and its row gradient 1 / B of each pair's own: the gradients are the mean over the pairs, as W ranks of
+        one pair each average them.  hpl_epe3d_pairs reports the per-pair losses.  B = 1 is step()."""
+        B = check_batch_step(pc1, pc2, sf, lat)
+        if B == 1:
+            r = self.step(pc1, pc2, sf, lat)
+            return None if r is None else (r[0], r[1], r[1].clone())
+        tb = self.tables(lat)
+        if tb is False:
+            return None
+        arr, n, _ = tb
+        n1, n2 = int(pc1.shape[2]), int(pc2.shape[2])
+        if arr[0].n0 != B * n1 or arr[0].n1 != B * n2:
+            raise _lib.HplError('lattice was built for %d / %d points, got %d x %d / %d x %d' % (arr[0].n0, arr[0].n1, B, n1, B, n2))
+        size, rows, cols = self.largest_matrix(arr, n)
+        if size > self.MAX_MATRIX_BYTES:
+            raise _lib.HplError('step_batch: %d pairs of %d points make a %d x %d matrix of %.2f GiB; the kernels address matrices '
+                                'below 2 GiB (32-bit offsets): use fewer pairs per batch' % (B, n1, rows, cols, size / 2.0 ** 30))
+        p1, p2, s = (x if x.is_contiguous() and x.dtype == torch.float32 else x.contiguous().float() for x in (pc1, pc2, sf))
+        key = (B, n1, n2)
+        if getattr(self, '_stage', None) is None or self._stage[0] != key:
+            # (a batch of another shape gets buffers of its own; the old ones stay alive in _keep while a step may still read them)
+            self._stage = (key, tuple(torch.empty((3, B * m), dtype=torch.float32, device=p1.device) for m in (n1, n2, n1)))
+        s1, s2, ssf = self._stage[1]
+        check(self._lib.hpl_batch_stage(B, n1, n2, ptr(p1), ptr(p2), ptr(s), ptr(s1), ptr(s2), ptr(ssf), stream()), 'hpl_batch_stage')
+        pair_loss = torch.empty(B, dtype=torch.float32, device=p1.device)
+
+        def losses(out):
+            check(self._lib.hpl_epe3d_pairs(ptr(out), ptr(ssf), B, n1, ptr(pair_loss), stream()), 'hpl_epe3d_pairs')
+        out = self._enqueue(arr, n, s1, s2, ssf, B * n1, losses)
+        self._keep = (p1, p2, s, s1, s2, ssf, lat)
+        return out.view(B, n1, 3).transpose(1, 2), self.loss, pair_loss
 
     def finish(self):
         """Wait for the all-reduces (several ranks) and divide: after this the .grad views hold the step's gradients."""

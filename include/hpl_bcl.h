@@ -368,6 +368,10 @@ int hpl_regroup(const float *G, int64_t ldg, int64_t M, int F, int C, float *out
  * flow hpl_plan_run writes), sf (3, N); *loss = mean_n ||pred_n - sf_n||_2 (one workgroup, fixed-order sum:
  * deterministic), grad[n][c] = (pred - sf) / (N * ||.||) (0 where the norm is 0). */
 int hpl_epe3d(const float *pred, const float *sf, int64_t N, float *grad, float *loss, hplStream stream);
+/* The per-pair losses of a batch (reporting only: the training program's HPL_OP_EPE3D keeps the batch mean and its gradient):
+ * pred [batch x n][3] and sf (3, batch x n) pair-major; pair_loss[b] (DEVICE, batch floats) = hpl_epe3d of pair b's rows alone,
+ * bit for bit (one workgroup per pair, the same rows per thread, the same tree).  1 <= batch <= 64. */
+int hpl_epe3d_pairs(const float *pred, const float *sf, int batch, int64_t n, float *pair_loss, hplStream stream);
 /* optimizer.step() of main.py:216 for the Adam of main.py:138-140 (lr 1e-4, weight_decay 0, no amsgrad) over FLAT fp32 arrays,
  * step >= 1 counting this one: m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g^2;
  * p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps) -- torch's fused Adam operation by operation, the
@@ -666,6 +670,11 @@ int hpl_plan_profile_read(hpl_plan *plan, int *launches, float *total_ms);
 int64_t hpl_plan_batch_extra_bytes(const hpl_level_tables *levels /* HOST */, int n_levels);
 int hpl_plan_run_batch(hpl_plan *plan, const hpl_level_tables *levels /* HOST */, int n_levels, int batch, const float *pc1,
                        const float *pc2, float *out, void *workspace, int64_t workspace_bytes, hplStream stream);
+/* Batched training: pc1 (batch, 3, n1), pc2 (batch, 3, n2) and, if not NULL, sf (batch, 3, n1), all DEVICE float32, laid out
+ * as (3, batch x n) pair-major matrices dst1 / dst2 / dst_sf in one launch (16-byte accesses when n1 and n2 are multiples of 4
+ * and every pointer is 16-byte aligned).  The training plan then runs hpl_plan_run_range on them unchanged. */
+int hpl_batch_stage(int batch, int64_t n1, int64_t n2, const float *pc1, const float *pc2, const float *sf, float *dst1,
+                    float *dst2, float *dst_sf, hplStream stream);
 
 
 /* ------------------------------------------------------------------------ *

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
 """GPU: the native training step (train_plan.TrainPlan) beside the autograd step on one N-point pair: ms per step (steady state,
-same lattice), host enqueue time of a step, launches per step (count of executed ops)."""
+same lattice), host enqueue time of a step, launches per step (count of executed ops).
+    python tools/train_native_probe.py [N] [B]      B > 1: the batched step (TrainPlan.step_batch) over B pairs, native leg only"""
 import os, sys, time, types, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,6 +10,7 @@ from hplflownet_amd import ops
 from hplflownet_amd.synthetic import SCALES_FILTER_MAP, fill_module_, synthetic_pair
 from hplflownet_amd.train_plan import TrainPlan
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 8192
+BATCH = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 dev = 'cuda'
 a = types.SimpleNamespace(dim=3, scales_filter_map=SCALES_FILTER_MAP, evaluate=False, use_leaky=True, bcn_use_bias=True,
                           bcn_use_norm=True, last_relu=False, DEVICE='cuda')
@@ -17,6 +19,10 @@ gen = H.GenerateDataUnsymmetric(a, device=dev, wide_up=model.lattice_hint())
 pc1, pc2, sf = synthetic_pair(N, 0)
 t1, t2, tsf = [torch.from_numpy(x.T.copy()).to(dev) for x in (pc1, pc2, sf)]
 lat = gen.build_native(t1, t2).device_lattice().prepare(True)
+if BATCH > 1:
+    trios = [synthetic_pair(N, s) for s in range(BATCH)]
+    t1, t2, tsf = [torch.stack([torch.from_numpy(tr[j].T.copy()) for tr in trios]).to(dev) for j in range(3)]
+    lat = gen.build_native_batch(t1, t2, for_training=True)
 opt = torch.optim.Adam(model.parameters(), lr=1e-4, fused=not os.environ.get('PROBE_UNFUSED_ADAM'))      # (engine.Trainer and bench.py use the fused optimizer)
 
 def timed(fn, n=10, warm=3):
@@ -28,7 +34,7 @@ def timed(fn, n=10, warm=3):
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) * 1e3 / n, host * 1e3 / n
 
-ONLY = os.environ.get('PROBE_ONLY')          # 'native': skip the autograd leg (kernel traces of the native step alone)
+ONLY = os.environ.get('PROBE_ONLY') or ('native' if BATCH > 1 else None)    # 'native': skip the autograd leg (kernel traces of the native step alone)
 ops.enable_weight_bank(True)
 def auto():
     flow = model(t1[None], t2[None], lat)
@@ -42,8 +48,9 @@ if ONLY != 'native':
 ops.enable_weight_bank(False)
 for side in ((True,) if ONLY == 'native' else (False, True)):
     plan = TrainPlan(model, side_stream=side)
+    step = plan.step_batch if BATCH > 1 else plan.step
     def nat():
-        plan.step(t1, t2, tsf, lat); plan.finish()
+        step(t1, t2, tsf, lat); plan.finish()
         if not plan.adam_step(opt):              # one launch over the flat arrays, as engine.Trainer does
             opt.step()
     ms, host = timed(nat)
@@ -55,10 +62,10 @@ for side in ((True,) if ONLY == 'native' else (False, True)):
         torch.cuda.current_stream().wait_stream(hi)
         print('native step on a high-priority stream (side stream at normal priority): %.2f ms (host %.2f)' % (msh, hosth))
     nfwd = plan.n_fwd
-    print('native step (side stream %s): %.2f ms (host enqueue %.2f ms); program: %d forward + %d backward ops, %d un-layout buckets'
-          % (side, ms, host, nfwd, len(plan.prog.ops) - nfwd, len(plan.cuts)))
+    print('native step (side stream %s, %d pairs): %.2f ms = %.2f ms per pair (host enqueue %.2f ms); program: %d forward + %d backward ops, '
+          '%d un-layout buckets' % (side, BATCH, ms, ms / BATCH, host, nfwd, len(plan.prog.ops) - nfwd, len(plan.cuts)))
     torch.cuda.synchronize()
-    h0 = time.perf_counter(); plan.step(t1, t2, tsf, lat); h1 = time.perf_counter(); plan.finish(); plan.adam_step(opt) or opt.step(); h2 = time.perf_counter()
+    h0 = time.perf_counter(); step(t1, t2, tsf, lat); h1 = time.perf_counter(); plan.finish(); plan.adam_step(opt) or opt.step(); h2 = time.perf_counter()
     torch.cuda.synchronize()
     print('   host time of one step issued to an idle GPU: program %.2f ms, Adam %.2f ms' % ((h1 - h0) * 1e3, (h2 - h1) * 1e3))
     def fwd_only():
