@@ -160,6 +160,9 @@ _SIGNATURES = {
     'hpl_lattice_begin': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     'hpl_lattice_begin_batch': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp]),
     'hpl_lattice_arena_bytes_batch': (c_i64, [c_vp, c_i64, c_i64, c_i64]),
+    'hpl_lattice_begin_ragged': (ctypes.c_int, [c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_vp, c_i64,
+                                                c_vp]),
+    'hpl_lattice_arena_bytes_ragged': (c_i64, [c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     'hpl_lattice_pair_counts': (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64)]),
     'hpl_lattice_ready': (ctypes.c_int, [c_vp]),
     'hpl_lattice_advance': (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_int)]),
@@ -176,6 +179,9 @@ _SIGNATURES = {
                                           c_vp]),
     'hpl_plan_batch_extra_bytes': (c_i64, [ctypes.POINTER(LevelTables), ctypes.c_int]),
     'hpl_batch_stage': (ctypes.c_int, [ctypes.c_int, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    'hpl_ragged_stage': (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                        ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp),
+                                        ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp]),
     'hpl_epe3d_pairs': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_vp]),
     'hpl_plan_set_unlayout': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.c_int]),
     'hpl_plan_profile': (ctypes.c_int, [c_vp, ctypes.c_int]),

@@ -15,6 +15,7 @@
 
 #include <new>
 #include <stdlib.h>
+#include <string.h>
 
 using namespace hpl;
 
@@ -58,6 +59,8 @@ struct hpl_lattice {
     int64_t bounds[HPL_MAX_LEVELS] = {0};
     int32_t stat_launches = 0, stat_fallbacks = 0, stat_fused = 0;
     int batch = 1;                    // pairs of the build in progress (> 1: hpl_lattice_begin_batch, fused driver only)
+    bool ragged = false;              // the batch in progress came from hpl_lattice_begin_ragged: its pairs' point prefixes
+    int32_t pt_off[2][fused::MAX_BATCH + 1] = {};
     bool last_fused = false;          // the last finished build came from the fused driver
 
     template <class T> T *take(int64_t count) {
@@ -266,13 +269,45 @@ int fused_finish(hpl_lattice *b) {
 
 int fused_begin(hpl_lattice *b, bool default_bounds = false) {
     const int64_t need = fused::layout(b->spec, b->n[0], b->n[1], default_bounds ? nullptr : b->bounds, b->pc[0], b->pc[1], b->arena,
-                                       b->plan, b->batch);
+                                       b->plan, b->batch, b->ragged ? b->pt_off : nullptr);
     if (need < 0) { set_error("hpl_lattice (fused): clouds too large"); return HPL_EINVAL; }
     if (need > b->end - b->arena) return HPL_ENOMEM;
     b->cur = b->arena + need;
     const int rc = fused::enqueue(b->plan, b->lv_stage, b->dims_host, b->counts_ev, b->s);
     b->stat_launches = b->plan.launches;
     return rc;
+}
+
+// the per-pair point counts of a ragged batch -> the prefixes of both clouds and the totals; false (the error set) if an
+// argument is out of range: 1 .. MAX_BATCH pairs, every count >= 1, every side's total <= MAX_RAGGED_POINTS
+bool ragged_prefixes(const char *who, int64_t batch, const int64_t *n0, const int64_t *n1, int32_t (*off)[fused::MAX_BATCH + 1],
+                     int64_t *tot) {
+    if (!n0 || !n1 || batch < 1 || batch > fused::MAX_BATCH) {
+        set_error("%s: %lld pairs (1 .. %d) or no counts", who, (long long)batch, fused::MAX_BATCH);
+        return false;
+    }
+    for (int c = 0; c < 2; ++c) {
+        const int64_t *n = c ? n1 : n0;
+        int64_t t = 0;
+        off[c][0] = 0;
+        for (int64_t p = 0; p < batch; ++p) {
+            if (n[p] < 1 || n[p] > fused::MAX_RAGGED_POINTS) {
+                set_error("%s: pair %lld has %lld points in cloud %d (1 .. %lld)", who, (long long)p, (long long)n[p], c + 1,
+                          (long long)fused::MAX_RAGGED_POINTS);
+                return false;
+            }
+            t += n[p];
+            if (t > fused::MAX_RAGGED_POINTS) {
+                set_error("%s: cloud %d of the batch holds more than %lld points (32-bit limits of the forward, DESIGN.md §13)",
+                          who, c + 1, (long long)fused::MAX_RAGGED_POINTS);
+                return false;
+            }
+            off[c][p + 1] = (int32_t)t;
+        }
+        for (int64_t p = batch; p < fused::MAX_BATCH; ++p) off[c][p + 1] = (int32_t)t;
+        tot[c] = t;
+    }
+    return true;
 }
 
 }  // namespace
@@ -330,6 +365,7 @@ extern "C" int hpl_lattice_begin(hpl_lattice *b, const float *pc1, const float *
     b->n[0] = n0; b->n[1] = n1; b->pc[0] = pc1; b->pc[1] = pc2;
     b->n_start[0] = n0; b->n_start[1] = n1;
     b->batch = 1;
+    b->ragged = false;
     b->fused_run = b->spec.fused != 0;
     b->last_fused = false;
     const int rc = b->fused_run ? fused_begin(b) : level_head(b);
@@ -352,11 +388,47 @@ extern "C" int hpl_lattice_begin_batch(hpl_lattice *b, const float *pc1, const f
     b->n[0] = batch * n0; b->n[1] = batch * n1; b->pc[0] = pc1; b->pc[1] = pc2;
     b->n_start[0] = b->n[0]; b->n_start[1] = b->n[1];
     b->batch = (int)batch;
+    b->ragged = false;
     b->fused_run = true;
     b->last_fused = false;
     const int rc = fused_begin(b);
     if (rc) b->active = false;
     return rc;
+}
+
+extern "C" int hpl_lattice_begin_ragged(hpl_lattice *b, const float *pc1, const float *pc2, int64_t batch, const int64_t *n0,
+                                        const int64_t *n1, void *arena, int64_t arena_bytes, hplStream stream) {
+    HPL_REQUIRE(b && pc1 && pc2 && arena && arena_bytes > 0, "hpl_lattice_begin_ragged: bad arguments");
+    int32_t off[2][fused::MAX_BATCH + 1];
+    int64_t tot[2];
+    if (!ragged_prefixes("hpl_lattice_begin_ragged", batch, n0, n1, off, tot)) return HPL_EINVAL;
+    if (batch == 1) return hpl_lattice_begin(b, pc1, pc2, n0[0], n1[0], arena, arena_bytes, stream);      // the single-pair build
+    HPL_REQUIRE(b->spec.fused, "hpl_lattice_begin_ragged: batches need the fused driver (spec.fused != 0)");
+    HPL_REQUIRE((reinterpret_cast<uintptr_t>(arena) & 255u) == 0, "hpl_lattice_begin_ragged: the arena must be 256-byte aligned");
+    b->arena = b->cur = reinterpret_cast<char *>(arena);
+    b->end = b->arena + arena_bytes;
+    b->hs = stream; b->s = to_stream(stream);
+    b->level = 0; b->active = true; b->done = false; b->overflow = false;
+    b->n[0] = tot[0]; b->n[1] = tot[1]; b->pc[0] = pc1; b->pc[1] = pc2;
+    b->n_start[0] = b->n[0]; b->n_start[1] = b->n[1];
+    b->batch = (int)batch;
+    b->ragged = true;
+    memcpy(b->pt_off, off, sizeof(off));
+    b->fused_run = true;
+    b->last_fused = false;
+    const int rc = fused_begin(b);
+    if (rc) b->active = false;
+    return rc;
+}
+
+extern "C" int64_t hpl_lattice_arena_bytes_ragged(const hpl_lattice *b, int64_t batch, const int64_t *n0, const int64_t *n1) {
+    int32_t off[2][fused::MAX_BATCH + 1];
+    int64_t tot[2];
+    if (!b || !ragged_prefixes("hpl_lattice_arena_bytes_ragged", batch, n0, n1, off, tot)) return -1;
+    if (batch == 1) return hpl_lattice_arena_bytes(b, n0[0], n1[0]);
+    if (!b->spec.fused) return -1;
+    fused::Plan tmp;
+    return fused::layout(b->spec, tot[0], tot[1], b->bounds, nullptr, nullptr, nullptr, tmp, (int)batch, off);
 }
 
 extern "C" int64_t hpl_lattice_arena_bytes_batch(const hpl_lattice *b, int64_t batch, int64_t n0, int64_t n1) {

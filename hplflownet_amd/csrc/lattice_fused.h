@@ -18,6 +18,9 @@ constexpr int HDR_RANGE = 1;       // batch: a pair's key range does not fit the
 // followed by the pair block: per level and cloud the first vertex of every pair and the vertex count behind the last
 // ([B + 1] ints in a slot of MAX_BATCH + 1).
 constexpr int MAX_BATCH = 64;
+// a ragged batch's points per cloud: the forward addresses its largest matrix (the level-0 pair-vertex activation, ~3.2 rows
+// per point at 1024 columns) through 32-bit offsets, which reach 2 GiB near 165 k points per cloud (DESIGN.md §12 "Size limit")
+constexpr int64_t MAX_RAGGED_POINTS = 160 * 1024;
 constexpr int PAIR_INTS = 2 * (MAX_BATCH + 1);    // ints per level of the pair block
 constexpr int64_t DIMS_BYTES = ((int64_t)sizeof(int32_t) * DIM_INTS * (1 + HPL_MAX_LEVELS) + 255) / 256 * 256;
 constexpr int64_t READBACK_INTS = DIMS_BYTES / 4 + (int64_t)HPL_MAX_LEVELS * PAIR_INTS;
@@ -74,6 +77,10 @@ struct Level {
     int32_t pair_shift;           // packed key of a batch: pair << pair_shift | key within the pair's range (63 - bits of batch - 1)
     const int32_t *prev_vpair[2];
     int32_t *vpair[2], *voff[2], *pmm;
+    // ragged batch (pairs of their own point counts): level 0 reads packed (3, n_host[c]) clouds, pair b's points are rows
+    // [pt_off[c][b], pt_off[c][b + 1]) (level 0 only; deeper levels take the pair from vpair as for equal batches)
+    int32_t ragged, pad1_;
+    int32_t pt_off[2][MAX_BATCH + 1];
 };
 
 struct Plan {
@@ -86,6 +93,7 @@ struct Plan {
     int batch = 1;                // pairs in the build
     int32_t *d_pairs = nullptr;   // in the arena, right behind the dims block (batch > 1): HPL_MAX_LEVELS x PAIR_INTS
     int32_t *d_pmm = nullptr;     // in the arena (batch > 1): n_levels x MAX_BATCH x 8 per-pair key ranges
+    bool ragged = false;          // level 0 carries per-pair point prefixes (k_lattice_fused<true, true>)
 };
 
 // default per-cloud bound on a level's vertex count: min(4 x the bound of its input points, row_cap)
@@ -93,9 +101,10 @@ int64_t default_row_cap(int64_t n0, int64_t n1);
 
 // Lay the build out in `arena` (nullptr: size query only).  bounds[L] > 0 overrides the vertex bound of level L (per
 // cloud; a batch scales it by its pairs).  n0, n1: points per cloud of the whole build (a batch: batch x its pairs' points).
+// pt_off (ragged batches, else nullptr): per cloud the batch + 1 point prefixes of the pairs, [2][MAX_BATCH + 1].
 // Returns the bytes needed, or -1 (plan.bytes is set either way).
 int64_t layout(const hpl_lattice_spec &spec, int64_t n0, int64_t n1, const int64_t *bounds, const float *pc1,
-               const float *pc2, char *arena, Plan &plan, int batch = 1);
+               const float *pc2, char *arena, Plan &plan, int batch = 1, const int32_t (*pt_off)[MAX_BATCH + 1] = nullptr);
 
 // true if this spec can be built by the fused path (radius-1 stencils, corr1 sharing the blur table, <= 4 groups)
 bool supported(const hpl_lattice_spec &spec);

@@ -62,8 +62,18 @@ __device__ __forceinline__ int64_t slot_key(const int4 &s) { return (int64_t)(((
 // its PAIR's own range (the range its single-pair build uses) below a pair digit, so each pair's vertices are numbered in
 // first-appearance order behind the previous pair's -- exactly its single-pair ids plus an offset -- and no table links two
 // pairs.  The pair of a point: level 0 from its row, deeper levels from the vertex of the level above it is (vpair).
+// RG (a ragged batch: pairs of their own point counts): level 0 searches the pairs' point prefixes.  The search is
+// branch-free over <= 64 prefixes of the level record; the lanes of a wave inside one pair (all but the waves across a
+// boundary) load the same words.
+template <bool RG>
 __device__ __forceinline__ int point_pair(const Level &L, int c, int p) {
-    return L.prev_dims ? L.prev_vpair[c][p] : p / L.n_pair[c];
+    if (L.prev_dims) return L.prev_vpair[c][p];
+    if (!RG) return p / L.n_pair[c];
+    const int32_t *o = L.pt_off[c];
+    int b = 0;                                       // the last pair whose first point is <= p (pt_off[c][0] = 0)
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) b = (b + s < L.batch && o[b + s] <= p) ? b + s : b;
+    return b;
 }
 
 // number of packed keys in a pair's range; 0 if they do not fit below the pair digit (the build is refused, HDR_RANGE)
@@ -128,7 +138,7 @@ __device__ __forceinline__ int block_sum(int v, int *scr) {
 // ------------------------------------------------------------------------------------------------ phase 1: keys
 // keys + barycentric + el_minus_gr of both clouds (transforms.py:300-353), the joint key range (:384-385), and the
 // clearing of everything the later phases of this level accumulate into
-template <bool BT>
+template <bool BT, bool RG>
 __device__ void task_keys(const Level &L, int b, int nblk, const Elev &E, int *scr) {
     const int n0 = npts(L, 0), n1 = npts(L, 1);
     const int t0 = b * 256 + threadIdx.x, nth = nblk * 256;
@@ -146,9 +156,12 @@ __device__ void task_keys(const Level &L, int b, int nblk, const Elev &E, int *s
             if (i < n0 + n1) {
                 const int c = i >= n0 ? 1 : 0;
                 const int p = c ? i - n0 : i, N = c ? n1 : n0;
-                pr = point_pair(L, c, p);
+                pr = point_pair<RG>(L, c, p);
                 float q[3];
-                if (L.pc[0]) {       // (B, 3, n_pair) clouds, read in place
+                if (RG && L.pc[0]) { // packed (3, N) clouds (hpl_ragged_stage)
+                    const float *pc = L.pc[c];
+                    q[0] = pc[p]; q[1] = pc[N + p]; q[2] = pc[2 * N + p];
+                } else if (L.pc[0]) {       // (B, 3, n_pair) clouds, read in place
                     const int np = L.n_pair[c], pp = p - pr * np;
                     const float *pc = L.pc[c] + (int64_t)pr * 3 * np;
                     q[0] = pc[pp]; q[1] = pc[np + pp]; q[2] = pc[2 * np + pp];
@@ -254,7 +267,7 @@ __device__ void task_keys(const Level &L, int b, int nblk, const Elev &E, int *s
 // j into the slot (the owner = first appearance).  The staged builder deduplicates 1024 keys in LDS first, which saves
 // global atomics; here the build is bound by the LENGTH of its dependency chains, not by atomic throughput (<= 2^18 keys),
 // and the direct form is two dependent global operations per lane instead of a workgroup-serial LDS round.
-template <bool BT>
+template <bool BT, bool RG>
 __device__ void task_insert(const Level &L, int b, int nblk) {
     const int n0 = npts(L, 0), n1 = npts(L, 1);
     const int32_t *mm = L.dims + D_MM;
@@ -272,7 +285,7 @@ __device__ void task_insert(const Level &L, int b, int nblk) {
         for (int x = 0; x < 4; ++x) k[x] = keys[((int64_t)x * n + p) * 4 + r];
         unsigned long long packed;
         if (BT) {
-            const int pr = point_pair(L, c, p);
+            const int pr = point_pair<RG>(L, c, p);
             const int64_t R = pair_range(L.pmm + pr * 8, L.pair_shift);
             if (R == 0) {           // the pair's keys cannot be packed below its pair digit: refuse the build, never alias
                 L.hdr[HDR_RANGE] = 1;
@@ -318,7 +331,7 @@ __device__ void task_flags(const Level &L, int b, int nblk, int *scr) {
     }
 }
 
-template <bool BT>
+template <bool BT, bool RG>
 __device__ void task_ids(const Level &L, int b, int nblk, int *scr) {
     const int n0 = npts(L, 0), n1 = npts(L, 1);
     const int ch0 = dcdiv(4 * n0, SCAN_CHUNK), ch1 = dcdiv(4 * n1, SCAN_CHUNK);
@@ -354,9 +367,9 @@ __device__ void task_ids(const Level &L, int b, int nblk, int *scr) {
                 for (int x = 0; x < 4; ++x) L.vk[c][x * vs + id] = keys[((int64_t)x * n + p) * 4 + r];
                 if (BT) {
                     // the pair's first entry always owns its vertex (no earlier pair has its keys): that vertex is the pair's first
-                    const int pr = point_pair(L, c, p);
+                    const int pr = point_pair<RG>(L, c, p);
                     L.vpair[c][id] = pr;
-                    if (r == 0 && (p == 0 || point_pair(L, c, p - 1) != pr)) L.voff[c][pr] = id;
+                    if (r == 0 && (p == 0 || point_pair<RG>(L, c, p - 1) != pr)) L.voff[c][pr] = id;
                 }
             }
             ++id;
@@ -834,8 +847,9 @@ __device__ void task_tile_rank(const Level &L, const SortJob &J, int *sm) {
 }
 
 // ------------------------------------------------------------------------------------------------ the kernel
-// BT: a batch of pairs (the per-pair key ranges and pair digits); false: the single-pair build as it always was
-template <bool BT>
+// BT: a batch of pairs (the per-pair key ranges and pair digits); false: the single-pair build as it always was.
+// RG: a ragged batch (level 0 finds a point's pair among per-pair prefixes); only with BT
+template <bool BT, bool RG>
 __global__ void __launch_bounds__(256) k_lattice_fused(const Level *__restrict__ levels, const Launch l, const Elev E,
                                                        const Off15 o) {
     __shared__ __attribute__((aligned(16))) char smem[9216];        // the sort's digit bases and per-wave counts; scan scratch; csr_rank's segments
@@ -847,10 +861,10 @@ __global__ void __launch_bounds__(256) k_lattice_fused(const Level *__restrict__
     const int b = (int)blockIdx.x - t.blk0;
     int *ism = reinterpret_cast<int *>(smem);
     switch (t.kind) {
-    case T_KEYS: task_keys<BT>(L, b, t.nblk, E, ism); break;
-    case T_INSERT: task_insert<BT>(L, b, t.nblk); break;
+    case T_KEYS: task_keys<BT, RG>(L, b, t.nblk, E, ism); break;
+    case T_INSERT: task_insert<BT, RG>(L, b, t.nblk); break;
     case T_FLAGS: task_flags(L, b, t.nblk, ism); break;
-    case T_IDS: task_ids<BT>(L, b, t.nblk, ism); break;
+    case T_IDS: task_ids<BT, RG>(L, b, t.nblk, ism); break;
     case T_OFF: task_off(L, b, t.nblk); break;
     case T_BLUR: task_blur<BT>(L, b, t.nblk, o, ism); break;
     case T_CORR2: task_corr2<BT>(L, b, t.nblk, o); break;
@@ -904,7 +918,7 @@ bool supported(const hpl_lattice_spec &sp) {
 }
 
 int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t *bounds, const float *pc1,
-               const float *pc2, char *arena, Plan &plan, int batch) {
+               const float *pc2, char *arena, Plan &plan, int batch, const int32_t (*pt_off)[MAX_BATCH + 1]) {
     int64_t used = 0;
     auto take = [&](int64_t bytes) -> char * {
         char *r = arena ? arena + used : nullptr;
@@ -915,6 +929,7 @@ int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t
     plan.d_levels = reinterpret_cast<Level *>(take(sizeof(Level) * HPL_MAX_LEVELS));
     plan.d_dims = reinterpret_cast<int32_t *>(take(DIMS_BYTES));
     plan.batch = batch;
+    plan.ragged = batch > 1 && pt_off != nullptr;
     plan.d_pairs = plan.d_pmm = nullptr;
     if (batch > 1) {       // (the pair block right behind the dims block: one read-back covers both)
         plan.d_pairs = reinterpret_cast<int32_t *>(take(sizeof(int32_t) * HPL_MAX_LEVELS * PAIR_INTS));
@@ -953,7 +968,13 @@ int64_t layout(const hpl_lattice_spec &sp, int64_t n0, int64_t n1, const int64_t
         while ((1 << (63 - L.pair_shift)) < batch) --L.pair_shift;        // B = 2: 62 bits per pair, B = 64: 57
         L.n_pair[0] = (int32_t)(n0 / batch); L.n_pair[1] = (int32_t)(n1 / batch);
         L.pmm = plan.d_pmm ? plan.d_pmm + (int64_t)Li * MAX_BATCH * 8 : nullptr;
-        if (Li == 0) { L.pc[0] = pc1; L.pc[1] = pc2; }
+        if (Li == 0) {
+            L.pc[0] = pc1; L.pc[1] = pc2;
+            if (plan.ragged) {
+                L.ragged = 1;
+                memcpy(L.pt_off, pt_off, sizeof(L.pt_off));
+            }
+        }
         else {
             const Level &P = plan.lv[Li - 1];
             L.prev_vpair[0] = P.vpair[0]; L.prev_vpair[1] = P.vpair[1];
@@ -1027,14 +1048,15 @@ int enqueue(Plan &plan, Level *lv_stage, int32_t *dims_host, hipEvent_t counts_e
     }
     const int n_pmm = plan.batch > 1 ? nlev * MAX_BATCH * 8 : 0;
     k_fused_begin<<<cdiv(imax((1 + nlev) * DIM_INTS, n_pmm), 256), 256, 0, s>>>(plan.d_dims, nlev, plan.d_pmm, n_pmm);
-    const bool bt = plan.batch > 1;
+    const bool bt = plan.batch > 1, rg = bt && plan.ragged;
     const Elev E = make_elev();
     const Offsets full = make_offsets(1);
     Off15 o;
     for (int i = 0; i < 60; ++i) o.v[i] = full.v[i];
     auto kernel = [&](int grid, const Launch &ll) {
-        if (bt) k_lattice_fused<true><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
-        else k_lattice_fused<false><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
+        if (rg) k_lattice_fused<true, true><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
+        else if (bt) k_lattice_fused<true, false><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
+        else k_lattice_fused<false, false><<<grid, 256, 0, s>>>(plan.d_levels, ll, E, o);
     };
     const int n_launches = 4 * (nlev - 1) + 10;
     plan.launches = 1;

@@ -152,7 +152,7 @@ class Trainer(object):
 
     def train_step(self, pc1, pc2, sf, lat):
         """One optimiser step on one pair (main.py:203-217) -> the loss (device tensor, not synchronised)."""
-        if getattr(lat, 'batch', 1) > 1:
+        if getattr(lat, 'batch', 1) > 1 or getattr(lat, 'ragged', False):
             raise HplError('train_step takes one pair: a lattice of %d pairs is for batched inference (validate)' % lat.batch)
         if self.native_step and self.tplan is None:
             from .train_plan import TrainPlan
@@ -281,27 +281,39 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data, batch_size=1):
+    def validate(self, data, batch_size=1, ragged=False):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
-        differ from its neighbours' forms a batch of its own."""
+        differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
+        counts (ragged_groups: <= B pairs and <= RAGGED_POINT_BUDGET points per cloud side a batch).  `val_batches`: the
+        forwards this rank ran."""
         self.model.eval()
         agg = collections.OrderedDict()
+        self.val_batches = 0
 
         def add(flow, sf):
             for k, v in flow_metrics(flow.t(), sf.t()).items():
                 agg[k] = agg.get(k, 0.0) + v
-        if batch_size > 1:
+        if batch_size > 1 and ragged:
+            for group in self._ragged_batches(data, batch_size):
+                p1, p2 = [g[0] for g in group], [g[1] for g in group]
+                flows = self.model(p1, p2, self.gen.build_native_batch(p1, p2))      # (a list of one pair: build_native)
+                self.val_batches += 1
+                for f, g in zip(flows, group):
+                    add(f[0], g[2])
+        elif batch_size > 1:
             for group in self._batches(data, batch_size):
                 p1 = torch.stack([g[0] for g in group])
                 p2 = torch.stack([g[1] for g in group])
                 lat = self.gen.build_native_batch(p1, p2) if len(group) > 1 else self.gen.build_native(p1[0], p2[0])
                 flow = self.model(p1, p2, lat)
+                self.val_batches += 1
                 for b, g in enumerate(group):
                     add(flow[b], g[2])
         else:
             for (pc1, pc2, sf), lat in self._lattices(data, list(range(len(data))), False):
                 flow = self.model(pc1[None], pc2[None], lat)
+                self.val_batches += 1
                 add(flow[0], sf)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
         # added over the ranks, so all ranks return the metrics of the WHOLE split (and agree on `best` in fit())
@@ -320,6 +332,22 @@ class Trainer(object):
                 yield group
                 group = []
             group.append(s_)
+        if group:
+            yield group
+
+    @staticmethod
+    def _ragged_batches(data, batch_size, budget=None):
+        """Consecutive samples of `data` (each fetched once, in order) in the groups of ragged_groups."""
+        budget = RAGGED_POINT_BUDGET if budget is None else budget
+        group, tot = [], (0, 0)
+        for i in range(len(data)):
+            s_ = data[i]
+            c = (int(s_[0].shape[-1]), int(s_[1].shape[-1]))
+            if group and ragged_closes(len(group), tot, c, batch_size, budget):
+                yield group
+                group, tot = [], (0, 0)
+            group.append(s_)
+            tot = (tot[0] + c[0], tot[1] + c[1])
         if group:
             yield group
 
@@ -400,6 +428,29 @@ def batch_groups(counts, batch_size):
     return out
 
 
+#: points per cloud side of a ragged evaluation batch: at most the largest batch DESIGN.md §11 ran (B = 16 x N = 8 192), well
+#: inside the forward's 32-bit limits (lattice.MAX_RAGGED_POINTS)
+RAGGED_POINT_BUDGET = 131072
+
+
+def ragged_closes(n, tot, c, batch_size, budget):
+    """True if a group of n pairs holding tot = (points of cloud 1, of cloud 2) closes before a pair of counts c."""
+    return n >= batch_size or tot[0] + c[0] > budget or tot[1] + c[1] > budget
+
+
+def ragged_groups(counts, batch_size, budget=RAGGED_POINT_BUDGET):
+    """Index groups validate(batch_size=..., ragged=True) forms from per-sample point counts [(n1, n2), ...]: consecutive,
+    whatever the counts, at most batch_size each and at most `budget` points per cloud side (a pair above it alone)."""
+    out, tot = [], (0, 0)
+    for i, c in enumerate(counts):
+        if not out or ragged_closes(len(out[-1]), tot, c, batch_size, budget):
+            out.append([])
+            tot = (0, 0)
+        out[-1].append(i)
+        tot = (tot[0] + c[0], tot[1] + c[1])
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--arch', default='HPLFlowNet', choices=sorted(ARCHS))
@@ -417,6 +468,9 @@ def main(argv=None):
     ap.add_argument('--batch-size', type=int, default=1,
                     help='--evaluate: pairs per batched lattice build and forward (1 .. 64); consecutive pairs with equal point '
                          'counts are batched (default 1: one pair at a time)')
+    ap.add_argument('--ragged', action='store_true',
+                    help='--evaluate --batch-size B: batch consecutive pairs whatever their point counts (<= B pairs and <= %d '
+                         'points per cloud side a batch) instead of runs of equal counts' % RAGGED_POINT_BUDGET)
     ap.add_argument('--train-batch-size', type=int, default=None,
                     help='training: pairs per native step (1 .. 64, default 1); consecutive pairs with equal point counts share '
                          'one batched lattice build and one step, whose gradient is the mean over them.  With W ranks the global '
@@ -429,6 +483,8 @@ def main(argv=None):
         ap.error('--batch-size takes 1 .. 64 and applies to --evaluate (training takes one pair per step)')
     if a.train_batch_size is not None and (a.evaluate or not 1 <= a.train_batch_size <= 64):
         ap.error('--train-batch-size takes 1 .. 64 and applies to training (--evaluate batches with --batch-size)')
+    if a.ragged and (not a.evaluate or a.batch_size < 2):
+        ap.error('--ragged applies to --evaluate with --batch-size >= 2')
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -443,7 +499,7 @@ def main(argv=None):
     if a.dataset != 'synthetic':
         return _real_data(a, tr, dev, rank, world)
     if a.evaluate:
-        res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size)
+        res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size, a.ragged)
         if rank == 0:
             print(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
@@ -507,7 +563,7 @@ def _real_data(a, tr, dev, rank, world):
         log('note: training on the first %d samples of each rank\'s shard only (--pairs)' % a.pairs)
     val = _Shard(val, rank, world, cap)
     if train is None:
-        res = tr.validate(val, a.batch_size)
+        res = tr.validate(val, a.batch_size, a.ragged)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

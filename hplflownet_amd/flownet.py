@@ -310,9 +310,12 @@ class _FlowNetBase(nn.Module):
         return c
 
     def forward(self, pc1, pc2, generated_data):
-        dev = pc1.device
         B = batch_of(pc1, pc2, generated_data, torch.is_grad_enabled(), self.pair_batched)
-        if not pc1.is_cuda:
+        ragged = isinstance(pc1, (list, tuple))          # lists of (3, N_b) clouds -> a list of B (1, 3, N1_b) flows
+        if ragged and B == 1:
+            return [self.forward(pc1[0][None], pc2[0][None], generated_data)]
+        dev = pc1[0].device if ragged else pc1.device
+        if not (pc1[0] if ragged else pc1).is_cuda:
             raise _lib.HplError('the HIP path needs device tensors (no CPU fallback)')
         native_lat = getattr(generated_data, 'device_lattice', None)       # lattice.NativeLattice
         # a natively built lattice lives in one arena, usually allocated on the lattice stream: tell the allocator that this
@@ -362,16 +365,25 @@ class _FlowNetBase(nn.Module):
             # of level L is written straight into columns [4, 4+C) of level L+1's input.
             feat_c = self.conv1[-1].conv.out_channels
             n0 = lat.levels[0].pair.N
-            xin = torch.empty((n0, pc1.shape[1]), dtype=torch.float32, device=dev)
-            if lat.levels[0].clouds[0].N != B * pc1.shape[2] or lat.levels[0].clouds[1].N != B * pc2.shape[2]:
+            xin = torch.empty((n0, 3), dtype=torch.float32, device=dev)
+            if ragged:          # a ragged batch: pair-major rows as well, every pair with its own counts
+                t1 = sum(p.shape[1] for p in pc1)
+                if lat.levels[0].clouds[0].N != t1 or lat.levels[0].clouds[1].N != n0 - t1:
+                    raise _lib.HplError('ragged lattice was built for %d / %d points, got %d / %d'
+                                        % (lat.levels[0].clouds[0].N, lat.levels[0].clouds[1].N, t1,
+                                           sum(p.shape[1] for p in pc2)))
+                torch.cat([p.t() for p in pc1], out=xin[:t1])
+                torch.cat([p.t() for p in pc2], out=xin[t1:])
+            elif lat.levels[0].clouds[0].N != B * pc1.shape[2] or lat.levels[0].clouds[1].N != B * pc2.shape[2]:
                 raise _lib.HplError('lattice was built for %d / %d points, got %d / %d'
                                     % (lat.levels[0].clouds[0].N, lat.levels[0].clouds[1].N, B * pc1.shape[2],
                                        B * pc2.shape[2]))
-            h = pc1.shape[2]
-            if B > 1:           # a batch: pair-major rows, cloud 1 of every pair, then cloud 2 of every pair
+            elif B > 1:           # a batch: pair-major rows, cloud 1 of every pair, then cloud 2 of every pair
+                h = pc1.shape[2]
                 xin[:B * h].view(B, h, 3).copy_(pc1.transpose(1, 2))
                 xin[B * h:].view(B, pc2.shape[2], 3).copy_(pc2.transpose(1, 2))
             else:
+                h = pc1.shape[2]
                 xin[:h].copy_(to_channel_last(pc1))
                 xin[h:].copy_(to_channel_last(pc2))
             x = torch.empty((n0, 4 + feat_c), dtype=torch.float32, device=dev)
@@ -390,6 +402,8 @@ class _FlowNetBase(nn.Module):
                 x = nxt
                 if L >= 2:
                     prev = self._corr(L, lat, feats, prev, corrs, dev)
+        elif ragged:
+            raise _lib.HplError('ragged batches need the pair-batched forward')
         else:
             feats = [self._stack(to_channel_last(pc1), self.conv1), self._stack(to_channel_last(pc2), self.conv1)]
             for L in range(nlev):
@@ -423,15 +437,48 @@ class _FlowNetBase(nn.Module):
         y = pointwise_conv(y, self.conv2.conv, True, self.use_leaky)
         y = pointwise_conv(y, self.conv3.conv, True, self.use_leaky)
         y = pointwise_conv(y, self.conv4, False, self.use_leaky)
+        if ragged:
+            return ragged_flows(y, [p.shape[1] for p in pc1])
         if B > 1:
             return y.view(B, -1, y.shape[1]).transpose(1, 2)              # (B, 3, N1)
         return to_channel_first(y)
 
 
+def ragged_flows(y, n1):
+    """[sum N1_b, 3] flow of a ragged batch -> pair b's (1, 3, N1_b) flow, a view of rows [off_b, off_b + N1_b)."""
+    out, o = [], 0
+    for n in n1:
+        out.append(y[o:o + n].t().unsqueeze(0))
+        o += n
+    return out
+
+
 def batch_of(pc1, pc2, lat, grad, pair_batched=True):
     """Pairs of a forward (no launch): (1, 3, N) / (3, N) inputs take a single-pair lattice; (B, 3, N) inputs a lattice of
-    lattice.GenerateDataUnsymmetric.build_native_batch with the same B, inference only (no autograd)."""
+    lattice.GenerateDataUnsymmetric.build_native_batch with the same B, inference only (no autograd).  Two lists of B
+    (3, N_b) clouds take the ragged lattice build_native_batch made of them (a list of one pair: a single-pair lattice)."""
     lb = int(getattr(lat, 'batch', 1) or 1)
+    ragged = bool(getattr(lat, 'ragged', False))
+    if isinstance(pc1, (list, tuple)) or isinstance(pc2, (list, tuple)):
+        if not isinstance(pc1, (list, tuple)) or not isinstance(pc2, (list, tuple)):
+            raise _lib.HplError('pc1 and pc2 are both lists of (3, N) clouds or both tensors')
+        b = len(pc1)
+        if len(pc2) != b:
+            raise _lib.HplError('pc1 lists %d clouds, pc2 %d' % (b, len(pc2)))
+        if b != lb or (b > 1 and not ragged):
+            raise _lib.HplError('%d pairs of clouds in lists, but the lattice was built for %d%s (build_native_batch of the lists '
+                                'builds a ragged batch)' % (b, lb, '' if ragged else ' of equal counts'))
+        if any(not torch.is_tensor(p) or p.dim() != 2 or p.shape[0] != 3 for p in list(pc1) + list(pc2)):
+            raise _lib.HplError('every cloud of a ragged batch is a (3, N) tensor')
+        if ragged and [(int(p.shape[1]), int(q.shape[1])) for p, q in zip(pc1, pc2)] != [tuple(c) for c in lat.point_counts]:
+            raise _lib.HplError('the ragged lattice was built for the point counts %s, got other clouds' % (lat.point_counts,))
+        if b > 1 and grad:
+            raise _lib.HplError('ragged batches are for inference: run the forward under torch.no_grad()')
+        if b > 1 and not pair_batched:
+            raise _lib.HplError('batched inference needs the pair-batched forward')
+        return b
+    if ragged:
+        raise _lib.HplError('a ragged lattice takes the two lists of (3, N) clouds it was built from')
     b1 = int(pc1.shape[0]) if pc1.dim() == 3 else 1
     b2 = int(pc2.shape[0]) if pc2.dim() == 3 else 1
     if b1 != b2:

@@ -74,7 +74,19 @@ class GenerateDataUnsymmetric(object):
         B x N2 pair-major points (pair b's slice of every table is pair b's build_native plus offsets); the models take
         it with the same (B, 3, N) tensors.  B = 1 is build_native of pc1[0], pc2[0].  for_training: the prepared
         DeviceLattice view with the backward's extras on the union tables (tap lists, symmetry verdicts, bary1 / off1),
-        what train_plan.TrainPlan.step_batch takes."""
+        what train_plan.TrainPlan.step_batch takes.
+
+        pc1, pc2 may also be two LISTS of B (3, N1_b) / (3, N2_b) float32 device tensors, pairs of their own point counts (a
+        ragged batch): -> NativeLattice with `batch` = B, `pair_counts`, `ragged` = True and `point_counts` =
+        [(N1_b, N2_b)]; the models take it with the same lists.  A list of one pair is build_native; ragged lattices are for
+        inference only."""
+        if isinstance(pc1, (list, tuple)) or isinstance(pc2, (list, tuple)):
+            B, _ = check_ragged(pc1, pc2)
+            if for_training:
+                raise _lib.HplError('ragged batches are for inference: training takes (B, 3, N) batches of equal point counts')
+            if B == 1:
+                return self.build_native(pc1[0], pc2[0])
+            return NativeLatticeBuild(self, pc1, pc2).finish()
         check_batch(pc1, pc2)
         return NativeLatticeBuild(self, pc1, pc2, for_training=for_training).finish()
 
@@ -241,14 +253,17 @@ class LatticePipeline(object):
     consumer's stream must wait for `event`, and must keep the pair and the lattice referenced until its
     own work on them is done (they were allocated on the lattice stream).  get() resumes, round robin, each
     pair whose counts have already landed until the oldest is complete, and blocks only when no pair can
-    move."""
+    move.  ragged=True (inference, e.g. engine.ragged_groups): the pairs of a build may differ in point counts; a
+    batch is handed out as LISTS (pc1s, pc2s, ...) of its pairs' tensors with the ragged lattice of build_native_batch."""
 
     def __init__(self, gen, source, first, count, depth=2, stream=None, for_training=False, native=False, threaded=False,
-                 batch=1, groups=None):
+                 batch=1, groups=None, ragged=False):
         self.batch = int(batch)
         if not 1 <= self.batch <= MAX_BATCH:
             raise _lib.HplError('LatticePipeline: batch %d (1 .. %d)' % (self.batch, MAX_BATCH))
         self._groups = None
+        if ragged and (self.batch == 1 or for_training):
+            raise _lib.HplError('LatticePipeline: ragged batches need batch > 1 and are for inference only')
         if self.batch > 1:
             if not native:
                 raise _lib.HplError('LatticePipeline: batches need the native builder')
@@ -262,8 +277,10 @@ class LatticePipeline(object):
                 raise _lib.HplError('LatticePipeline: every group holds 1 .. %d pairs' % self.batch)
             self._groups = groups
 
-            def source(k):              # the pairs of build k stacked into (B, 3, N) clouds
+            def source(k):              # the pairs of build k stacked into (B, 3, N) clouds, or as lists (ragged)
                 items = [one(j) for j in groups[k]]
+                if ragged:
+                    return tuple([it[j] for it in items] for j in range(len(items[0])))
                 return tuple(torch.stack([it[j] for it in items]) for j in range(len(items[0])))
             first, count = 0, len(groups)        # builds; _next / _end count them
         self.native = native            # builds driven by csrc/lattice_builder.hip (NativeLatticeBuild)
@@ -386,7 +403,7 @@ class LatticePipeline(object):
 def to_reference_format(lat):
     """DeviceLattice -> the reference's generated_data (transforms.py:471-483): list of dicts of
     int64 / float32 tensors (on the device), absent tables as zeros(1)."""
-    if getattr(lat, 'batch', 1) > 1:
+    if getattr(lat, 'batch', 1) > 1 or getattr(lat, 'ragged', False):
         raise _lib.HplError('to_reference_format: the lattice holds a batch of %d pairs; the wire format is one pair' % lat.batch)
     out = []
     for lv in lat.levels:
@@ -416,6 +433,7 @@ def to_reference_format(lat):
 # ----------------------------------------------------------------------------- native builder
 HPL_ENOMEM = -4
 MAX_BATCH = 64          # pairs per batched build (csrc/lattice_fused.h MAX_BATCH)
+MAX_RAGGED_POINTS = 160 * 1024      # points per cloud side of a ragged batch (csrc/lattice_fused.h MAX_RAGGED_POINTS)
 
 
 def check_batch(pc1, pc2):
@@ -432,6 +450,34 @@ def check_batch(pc1, pc2):
     return B
 
 
+def check_ragged(pc1s, pc2s):
+    """Argument checks of a ragged batch (no launch): two lists of B (3, N1_b) / (3, N2_b) float32 tensors on one device,
+    1 <= B <= 64, every N >= 1, each side's total <= MAX_RAGGED_POINTS -> (B, [(N1_b, N2_b)])."""
+    if not isinstance(pc1s, (list, tuple)) or not isinstance(pc2s, (list, tuple)):
+        raise _lib.HplError('a ragged batch is two lists of (3, N) clouds, got %s / %s' % (type(pc1s).__name__, type(pc2s).__name__))
+    B = len(pc1s)
+    if len(pc2s) != B:
+        raise _lib.HplError('pc1 lists %d clouds, pc2 %d: a batch pairs them one to one' % (B, len(pc2s)))
+    if not 1 <= B <= MAX_BATCH:
+        raise _lib.HplError('a batch holds 1 .. %d pairs, got %d' % (MAX_BATCH, B))
+    ts = list(pc1s) + list(pc2s)
+    for t in ts:
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != 3:
+            raise _lib.HplError('every cloud of a ragged batch is a (3, N) tensor, got %s' % (tuple(getattr(t, 'shape', ())),))
+        if t.shape[1] < 1:
+            raise _lib.HplError('empty cloud in a ragged batch')
+    if any(t.device != ts[0].device for t in ts) or any(t.dtype != torch.float32 for t in ts):
+        raise _lib.HplError('the clouds of a ragged batch are float32 tensors on one device, got %s'
+                            % sorted(set('%s %s' % (t.dtype, t.device) for t in ts)))
+    counts = [(int(a.shape[1]), int(b.shape[1])) for a, b in zip(pc1s, pc2s)]
+    for c in (0, 1):
+        tot = sum(n[c] for n in counts)
+        if tot > MAX_RAGGED_POINTS:
+            raise _lib.HplError('cloud %d of the ragged batch holds %d points, more than %d (32-bit limits of the forward)'
+                                % (c + 1, tot, MAX_RAGGED_POINTS))
+    return B, counts
+
+
 class NativeLattice(object):
     """A lattice built by the native builder (csrc/lattice_builder.hip): the kernel-ready hpl_level_tables of every
     level, all pointing into ONE device arena.  The native forward (plan.ForwardPlan) consumes `tables` as is;
@@ -441,6 +487,9 @@ class NativeLattice(object):
     #: pairs of the build (build_native_batch) and their vertex counts [levels][2][batch] (None for a single pair)
     batch = 1
     pair_counts = None
+    #: a ragged batch (build_native_batch of lists): True, and the pairs' point counts [(N1_b, N2_b)]
+    ragged = False
+    point_counts = None
 
     def __init__(self, arena, tables, n_levels, extras, wide_up):
         self.arena, self.tables, self.n_levels, self.extras, self.wide_up = arena, tables, n_levels, extras, wide_up
@@ -524,6 +573,7 @@ class NativeLattice(object):
             levels.append(lv)
         self._view = DeviceLattice(levels, wide_up=self.wide_up)
         self._view.batch = self.batch
+        self._view.ragged, self._view.point_counts = self.ragged, self.point_counts
         self._view._native_tables = self._native_tables
         self._view._arena = self.arena
         return self._view
@@ -617,13 +667,27 @@ class NativeLatticeBuild(object):
     def __init__(self, gen, pc1, pc2, stream=None, for_training=False, prepare=True, tag=None):
         self.gen, self.tag = gen, tag
         self.nb = gen.native_builder()
-        self.stream = stream if stream is not None else torch.cuda.current_stream(pc1.device)
-        self.batch = check_batch(pc1, pc2) if pc1.dim() == 3 else 1
-        if self.batch > 1 and not self.nb.fused:
-            raise _lib.HplError('batched lattices are built by the fused driver')
-        if pc1.dim() == 3 and self.batch == 1:
-            pc1, pc2 = pc1[0], pc2[0]           # B = 1: the single-pair build as it always was
-        self.pc = (pc1.contiguous().float(), pc2.contiguous().float())
+        self.counts = None              # a ragged batch: the pairs' point counts [(N1_b, N2_b)]
+        if isinstance(pc1, (list, tuple)):
+            self.batch, counts = check_ragged(pc1, pc2)
+            if self.batch > 1 and (for_training or not self.nb.fused):
+                raise _lib.HplError('ragged batches are built by the fused driver, for inference only')
+            self.stream = stream if stream is not None else torch.cuda.current_stream(pc1[0].device)
+            if self.batch > 1:
+                self.counts = counts
+                with torch.cuda.stream(self.stream):    # the pair-major clouds the build reads (one launch)
+                    self.pc = ops.ragged_stage(pc1, pc2)
+            else:
+                pc1, pc2 = pc1[0], pc2[0]       # one pair: the single-pair build as it always was
+        else:
+            self.stream = stream if stream is not None else torch.cuda.current_stream(pc1.device)
+            self.batch = check_batch(pc1, pc2) if pc1.dim() == 3 else 1
+            if self.batch > 1 and not self.nb.fused:
+                raise _lib.HplError('batched lattices are built by the fused driver')
+            if pc1.dim() == 3 and self.batch == 1:
+                pc1, pc2 = pc1[0], pc2[0]           # B = 1: the single-pair build as it always was
+        if self.counts is None:
+            self.pc = (pc1.contiguous().float(), pc2.contiguous().float())
         self.for_training = for_training
         self.done = False
         self.result = self.event = None
@@ -638,6 +702,8 @@ class NativeLatticeBuild(object):
         n0, n1 = int(self.pc[0].shape[-1]), int(self.pc[1].shape[-1])
         B = self.batch
         lib = self.nb.lib
+        if self.counts is not None:
+            return self._begin_ragged()
         if self.nb.fused:
             arr = (ctypes.c_int64 * 8)(*([0] * 8 if self._loose else self.nb.bounds))
             check(lib.hpl_lattice_set_bounds(self.handle, arr), 'hpl_lattice_set_bounds')
@@ -658,6 +724,22 @@ class NativeLatticeBuild(object):
                 check(rc, 'hpl_lattice_begin')
                 return
             self.nb.bytes_per_point *= 2
+
+    def _begin_ragged(self):
+        lib, B = self.nb.lib, self.batch
+        arr = (ctypes.c_int64 * 8)(*([0] * 8 if self._loose else self.nb.bounds))
+        check(lib.hpl_lattice_set_bounds(self.handle, arr), 'hpl_lattice_set_bounds')
+        n0 = (ctypes.c_int64 * B)(*[c[0] for c in self.counts])
+        n1 = (ctypes.c_int64 * B)(*[c[1] for c in self.counts])
+        need = int(lib.hpl_lattice_arena_bytes_ragged(self.handle, B, n0, n1))
+        if need < 0:
+            raise _lib.HplError('hpl_lattice_arena_bytes_ragged: %s' % lib.hpl_last_error().decode())
+        # (as for equal batches: room for the rebuild under the default bounds in the same arena, usually)
+        nbytes = max((32 << 20) + self.nb.bytes_per_point * sum(c[0] + c[1] for c in self.counts), need + 4096)
+        with torch.cuda.stream(self.stream):
+            self.arena = torch.empty(nbytes, dtype=torch.uint8, device=self.pc[0].device)
+            check(lib.hpl_lattice_begin_ragged(self.handle, ptr(self.pc[0]), ptr(self.pc[1]), B, n0, n1, self.arena.data_ptr(),
+                                               nbytes, stream()), 'hpl_lattice_begin_ragged')
 
     def ready(self):
         return self.done or bool(self.nb.lib.hpl_lattice_ready(self.handle))
@@ -712,6 +794,8 @@ class NativeLatticeBuild(object):
                 lat.arena_used = used.value
                 if self.batch > 1:
                     lat.batch, lat.pair_counts = self.batch, pair_counts
+                if self.counts is not None:
+                    lat.ragged, lat.point_counts = True, list(self.counts)
                 if self.for_training:
                     lat = lat.device_lattice().prepare(True)        # tap lists, symmetry verdicts: the Python tables
                 self.result, self.done = lat, True

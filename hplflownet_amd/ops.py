@@ -263,6 +263,27 @@ def table_invert(tbl, H0, F, H1):
     return inv
 
 
+def ragged_stage(pc1s, pc2s, sfs=None):
+    """A ragged batch's per-pair clouds -> its pair-major matrices in ONE launch (hpl_ragged_stage): pc1s[b], sfs[b] (3, N1_b),
+    pc2s[b] (3, N2_b) float32 device tensors (row slices of a padded (B, 3, Nmax) tensor are read in place) -> (3, sum N1_b),
+    (3, sum N2_b) and, with sfs, (3, sum N1_b) tensors on the current stream."""
+    B = len(pc1s)
+    sides = [pc1s, pc2s] + ([sfs] if sfs is not None else [])
+    keep, descs, outs = [], [], []
+    for ts in sides:
+        # rows of unit stride and a row stride >= the count; anything else is copied first
+        ts = [t if t.stride(1) == 1 and t.stride(0) >= t.shape[1] else t.contiguous() for t in ts]
+        keep.append(ts)
+        descs.append(((ctypes.c_void_p * B)(*[ptr(t) for t in ts]), (ctypes.c_int64 * B)(*[int(t.shape[1]) for t in ts]),
+                      (ctypes.c_int64 * B)(*[int(t.stride(0)) for t in ts])))
+        outs.append(torch.empty((3, sum(int(t.shape[1]) for t in ts)), dtype=torch.float32, device=ts[0].device))
+    d1, d2 = descs[0], descs[1]
+    d3 = descs[2] if sfs is not None else (None, None, None)
+    check(_lib.load().hpl_ragged_stage(B, d1[0], d1[1], d1[2], d2[0], d2[1], d2[2], d3[0], d3[2], ptr(outs[0]), ptr(outs[1]),
+                                       ptr(outs[2]) if sfs is not None else None, stream()), 'hpl_ragged_stage')
+    return tuple(outs)
+
+
 def round_up(x, m):
     return (x + m - 1) // m * m
 

@@ -360,6 +360,14 @@ def _corr(P, model, L, f1, f2, prev, sl, dst):
     return (c, mods[-1].conv.out_channels)
 
 
+class _Unbatched(object):
+    """A ragged lattice seen as the one pair of packed clouds its tables describe (what hpl_plan_run runs on)."""
+    batch = 1
+
+    def __init__(self, tables):
+        self._native_tables = tables
+
+
 def level_tables(lat, hint):
     """ctypes array of hpl_level_tables for a device-built lattice (cached on the lattice)."""
     cached = getattr(lat, '_native_tables', None)
@@ -562,8 +570,11 @@ class ForwardPlan(object):
 
     def __call__(self, pc1, pc2, lat):
         """pc1, pc2 (1, 3, N) or (3, N) device tensors -> flow (1, 3, N0) (a transposed view of an [N0, 3] matrix);
-        (B, 3, N) tensors and a lattice of build_native_batch with the same B -> flow (B, 3, N0) (hpl_plan_run_batch)."""
+        (B, 3, N) tensors and a lattice of build_native_batch with the same B -> flow (B, 3, N0) (hpl_plan_run_batch);
+        two lists of B (3, N_b) clouds and their ragged lattice -> a list of B flows (1, 3, N1_b) (_run_ragged)."""
         B = int(getattr(lat, 'batch', 1) or 1)
+        if isinstance(pc1, (list, tuple)):
+            return self._run_ragged(pc1, pc2, lat, B)
         if B > 1 or (pc1.dim() == 3 and pc1.shape[0] > 1):
             return self._run_batch(pc1, pc2, lat, B)
         p1 = pc1[0] if pc1.dim() == 3 else pc1
@@ -610,6 +621,17 @@ class ForwardPlan(object):
         ev.record()
         self._fence[slot] = ev
         return out.transpose(1, 2)
+
+    def _run_ragged(self, pc1, pc2, lat, B):
+        """Lists of B (3, N1_b) / (3, N2_b) clouds and their ragged lattice -> B flows (1, 3, N1_b), views of one [sum N1_b][3]
+        matrix.  One launch stages the clouds pair-major (hpl_ragged_stage), then hpl_plan_run runs on them unchanged."""
+        from .flownet import batch_of, ragged_flows
+        batch_of(pc1, pc2, lat, False)
+        if B == 1:
+            return [self(pc1[0], pc2[0], lat)]
+        p1, p2 = ops.ragged_stage(pc1, pc2)
+        flows = self(p1, p2, _Unbatched(level_tables(lat, self.hint)))
+        return ragged_flows(flows[0].t(), [p.shape[1] for p in pc1])
 
     # ---- profiling of the dominant launches (bench.py)
     def profile(self, tag):

@@ -293,7 +293,10 @@ class _Backward(object):
 
 def check_batch_step(pc1, pc2, sf, lat):
     """Argument checks of a batched training step (host only, nothing launched): pc1, sf (B, 3, N1), pc2 (B, 3, N2) and a
-    lattice built for the same B -> B."""
+    lattice built for the same B -> B.  A ragged lattice (pairs of their own point counts) is refused: HPL_OP_EPE3D is the mean
+    over all rows, which is not the mean over the pairs when their counts differ."""
+    if getattr(lat, 'ragged', False):
+        raise _lib.HplError('ragged batches are for inference: a training batch holds pairs of equal point counts')
     if any(getattr(x, 'dim', lambda: 0)() != 3 for x in (pc1, pc2, sf)) or pc1.shape[1] != 3 or pc2.shape[1] != 3:
         raise _lib.HplError('a training batch is (B, 3, N) clouds and flow, got %s / %s / %s'
                             % tuple(tuple(getattr(x, 'shape', ())) for x in (pc1, pc2, sf)))

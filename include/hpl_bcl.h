@@ -675,6 +675,17 @@ int hpl_plan_run_batch(hpl_plan *plan, const hpl_level_tables *levels /* HOST */
  * and every pointer is 16-byte aligned).  The training plan then runs hpl_plan_run_range on them unchanged. */
 int hpl_batch_stage(int batch, int64_t n1, int64_t n2, const float *pc1, const float *pc2, const float *sf, float *dst1,
                     float *dst2, float *dst_sf, hplStream stream);
+/* Ragged batches (pairs of their own point counts; the reference's KITTI evaluation keeps every point of a short frame,
+ * configs/test_ours_KITTI.yaml allow_less_points, transforms/transforms.py:517-532, and evaluates one pair per forward,
+ * configs/test_ours_KITTI.yaml:15 batch_size 1): B = `batch` (1 .. 64) per-pair clouds per side -- pc1[b] (3, ld1[b]) with n1[b] points, pc2[b] (3, ld2[b])
+ * with n2[b] points and, if sf is not NULL, sf[b] (3, ldsf[b]) with n1[b] points; HOST arrays of DEVICE float32 pointers,
+ * row k of pair b at pc1[b] + k * ld1[b], so pc[b, :, :n_b] slices of a padded (B, 3, Nmax) tensor need no copy -- laid out as
+ * the (3, sum n1) / (3, sum n2) / (3, sum n1) pair-major matrices dst1 / dst2 / dst_sf in ONE launch (the descriptors travel
+ * in its arguments; 16-byte accesses when every count and stride is a multiple of 4 and every pointer 16-byte aligned).
+ * hpl_lattice_begin_ragged builds on them and hpl_plan_run runs on them unchanged. */
+int hpl_ragged_stage(int batch, const float *const *pc1, const int64_t *n1, const int64_t *ld1, const float *const *pc2,
+                     const int64_t *n2, const int64_t *ld2, const float *const *sf, const int64_t *ldsf, float *dst1, float *dst2,
+                     float *dst_sf, hplStream stream);
 
 
 /* ------------------------------------------------------------------------ *
@@ -734,6 +745,19 @@ int hpl_lattice_begin_batch(hpl_lattice *b, const float *pc1, const float *pc2, 
                             void *arena, int64_t arena_bytes, hplStream stream);
 /* the arena hpl_lattice_begin_batch needs for `batch` pairs of (n0, n1) points under the current bounds (-1: bad arguments) */
 int64_t hpl_lattice_arena_bytes_batch(const hpl_lattice *b, int64_t batch, int64_t n0, int64_t n1);
+/* A ragged batch of `batch` pairs (1 .. 64) in ONE fused build (transforms/transforms.py:358-485 per pair, the pairs'
+ * point counts differing as configs/test_ours_KITTI.yaml allow_less_points makes them): pair b has n0[b] / n1[b] >= 1
+ * points (HOST arrays), pc1 (3, sum n0) and pc2 (3, sum n1) float32 DEVICE are the pair-major clouds of hpl_ragged_stage.
+ * Everything else is hpl_lattice_begin_batch's: pair b's slice of every table is its single-pair build's plus the vertex /
+ * point offsets, no table links two pairs, ~33 launches and one read-back, bounds per pair (set them from the largest),
+ * the same overflow rebuild and key-range refusal, hpl_lattice_pair_counts.  HPL_EINVAL before any launch for a batch
+ * outside 1 .. 64, a count < 1, or a side of more than 163 840 points (the forward's 32-bit offsets).
+ * batch = 1 is hpl_lattice_begin.  Fused builders only. */
+int hpl_lattice_begin_ragged(hpl_lattice *b, const float *pc1, const float *pc2, int64_t batch, const int64_t *n0 /* HOST */,
+                             const int64_t *n1 /* HOST */, void *arena, int64_t arena_bytes, hplStream stream);
+/* the arena hpl_lattice_begin_ragged needs under the current bounds (-1: bad arguments) */
+int64_t hpl_lattice_arena_bytes_ragged(const hpl_lattice *b, int64_t batch, const int64_t *n0 /* HOST */,
+                                       const int64_t *n1 /* HOST */);
 /* vertices of every pair of the finished build: out[(L * 2 + cloud) * batch + pair], n_levels x 2 x batch entries */
 int hpl_lattice_pair_counts(const hpl_lattice *b, int64_t *out /* HOST */);
 /* 1 if hpl_lattice_advance would not block (the pending read-back has landed, or the build is done), else 0 */
