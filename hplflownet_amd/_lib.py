@@ -48,6 +48,13 @@ class GConvDesc(ctypes.Structure):
                 ('a_guard', c_vp), ('y_guard', c_vp), ('guard_trips', c_vp)]
 
 
+class MetricsPair(ctypes.Structure):
+    """Mirror of `hpl_metrics_pair`."""
+    _fields_ = [('pred', c_vp), ('gt', c_vp), ('pc1', c_vp), ('n', c_i64), ('pred_sc', c_i64), ('pred_sp', c_i64),
+                ('gt_sc', c_i64), ('gt_sp', c_i64), ('pc1_sc', c_i64), ('pc1_sp', c_i64), ('camera', c_f32 * 6),
+                ('has_camera', c_i32), ('pad_', c_i32)]
+
+
 class Ref(ctypes.Structure):
     """Mirror of `hpl_ref`."""
     _fields_ = [('buf', c_i32), ('row_off_sym', c_i32), ('rows_sym', c_i32), ('col_off', c_i32), ('cols', c_i32)]
@@ -183,6 +190,7 @@ _SIGNATURES = {
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp),
                                         ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp]),
     'hpl_epe3d_pairs': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_vp]),
+    'hpl_flow_metrics': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     'hpl_plan_set_unlayout': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.c_int]),
     'hpl_plan_profile': (ctypes.c_int, [c_vp, ctypes.c_int]),
     'hpl_plan_guard_trips': (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64)]),

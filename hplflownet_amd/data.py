@@ -23,6 +23,12 @@ Own restatement of what feeds the hot path in the reference:
   (:100-105); frames whose line in the mapping file is empty are skipped (:76-83; the mapping file
   ships with the reference's dataset code, pass its path if you have it).
 
+Cameras (the 2D metrics EPE2D / ACC2D, evaluation_utils.py:22-36, project the flow into the image): whether a reader has them
+is a property of the reader (`has_cameras`), and every sample it returns carries the camera of the frame it actually came from
+(`Sample.camera`, a fall-through to the next frame included).  FlyingThings3D has one fixed pinhole (the defaults of
+utils/geometry.py:project_3d_to_2d); KITTI has `P_rect_02` of `calib_cam_to_cam/<frame>.txt` (utils/geometry.py:15-31), read
+from `calib_dir` at construction -- without it the reader has no cameras.
+
 The reference asserts the canonical sample counts (19 640 / 3 824 / 200) and exits; here a
 mismatch is reported by `check_counts()` and left to the caller.  No dataset is available in the
 build environment: the readers are exercised on synthetic directory trees of the same layout
@@ -35,7 +41,27 @@ import os
 import numpy as np
 import torch
 
-__all__ = ['ProcessData', 'Augmentation', 'FlyingThings3DSubset', 'KITTI']
+__all__ = ['ProcessData', 'Augmentation', 'FlyingThings3DSubset', 'KITTI', 'Sample', 'read_kitti_camera']
+
+#: (f, cx, cy, constx, consty, constz) of every FlyingThings3D frame (utils/geometry.py:59 defaults)
+FT3D_CAMERA = (-1050.0, 479.5, 269.5, 0.0, 0.0, 0.0)
+
+
+class Sample(tuple):
+    """(pc1, pc2, sf) of a reader, with `camera`: the (f, cx, cy, constx, consty, constz) of the frame it came from, or None."""
+    camera = None
+
+
+def read_kitti_camera(path):
+    """The camera of a KITTI calib_cam_to_cam file as utils/geometry.py:15-31 reads it: the first line starting with P_rect_02
+    as a float32 (3, 4) matrix P -> (f, cx, cy, constx, consty, constz) = (-P[0,0], P[0,2], P[1,2], P[0,3], P[1,3], P[2,3]),
+    float32 values.  Only that line is parsed (other lines of KITTI's own files can be malformed)."""
+    with open(path) as fd:
+        for line in fd:
+            if line.startswith('P_rect_02'):
+                P = np.array([float(v) for v in line.split()[1:]], dtype=np.float32).reshape(3, 4)
+                return tuple(float(v) for v in (-P[0, 0], P[0, 2], P[1, 2], P[0, 3], P[1, 3], P[2, 3]))
+    raise ValueError('%s has no P_rect_02 line' % path)
 
 
 class ProcessData(object):
@@ -135,6 +161,7 @@ class _PairFolder(object):
     """Common part: list of sample directories, transform, tensors on `device`."""
 
     canonical = None        # expected number of leaf directories, for check_counts()
+    has_cameras = False     # whether samples carry a camera (the 2D metrics need one)
 
     def __init__(self, transform, device='cuda'):
         self.transform = transform
@@ -164,6 +191,10 @@ class _PairFolder(object):
     def load(self, path):
         raise NotImplementedError
 
+    def camera_of(self, path):
+        """The camera of the frame in directory `path`, None if the reader has none."""
+        return None
+
     def __getitem__(self, index):
         """-> (pc1, pc2, sf) float32 device tensors (3, N); falls on to the next sample if the
         transform rejects this one (the reference draws a random replacement, :44-47)."""
@@ -174,12 +205,15 @@ class _PairFolder(object):
                 pc1, pc2 = self.load(path)
                 out = (pc1, pc2, pc2 - pc1)
             if out[0] is not None:
-                return tuple(torch.from_numpy(np.ascontiguousarray(a[:, :3].T, dtype=np.float32)).to(self.device)
-                             for a in out)
+                s_ = Sample(torch.from_numpy(np.ascontiguousarray(a[:, :3].T, dtype=np.float32)).to(self.device) for a in out)
+                s_.camera = self.camera_of(path)
+                return s_
         raise RuntimeError('no usable sample under %s' % self.root)
 
 
 class FlyingThings3DSubset(_PairFolder):
+    has_cameras = True
+
     def __init__(self, train, transform, data_root, full=False, device='cuda'):
         super(FlyingThings3DSubset, self).__init__(transform, device)
         self.train = train
@@ -199,11 +233,14 @@ class FlyingThings3DSubset(_PairFolder):
             pc[..., -1] *= -1
         return pc1, pc2
 
+    def camera_of(self, path):
+        return FT3D_CAMERA
+
 
 class KITTI(_PairFolder):
     canonical = 200
 
-    def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda'):
+    def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None):
         super(KITTI, self).__init__(transform, device)
         self.root = os.path.join(data_root, 'KITTI_processed_occ_final')
         self.remove_ground = remove_ground
@@ -216,6 +253,18 @@ class KITTI(_PairFolder):
         self.samples = dirs
         if not self.samples:
             raise RuntimeError('Found 0 files in subfolders of: ' + self.root)
+        self.cameras = None
+        if calib_dir is not None:
+            names = [os.path.basename(d) for d in dirs]
+            missing = [nm for nm in names if not os.path.isfile(os.path.join(calib_dir, nm + '.txt'))]
+            if missing:
+                raise FileNotFoundError('%s has no calibration for %d frame(s): %s' % (
+                    calib_dir, len(missing), ', '.join(nm + '.txt' for nm in missing[:20]) + (' ...' if len(missing) > 20 else '')))
+            self.cameras = {nm: read_kitti_camera(os.path.join(calib_dir, nm + '.txt')) for nm in names}
+        self.has_cameras = self.cameras is not None
+
+    def camera_of(self, path):
+        return self.cameras[os.path.basename(path)] if self.cameras is not None else None
 
     def load(self, path):
         pc1 = np.load(os.path.join(path, 'pc1.npy'))

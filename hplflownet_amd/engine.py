@@ -12,7 +12,8 @@ Own counterpart of the reference's loops (/root/reference/main.py:95-286) and ch
   model_best.pth.tar when best (main.py:183-189, main_utils.py:54-64).  The reference saves the
   state_dict of a DataParallel wrapper, so keys carry a 'module.' prefix; it is written (and
   accepted on load, see flownet.load_reference_checkpoint) so files are interchangeable;
-* metrics EPE3D / Acc3D strict / Acc3D relax / outliers (evaluation_utils.py:4-19), on the device.
+* metrics EPE3D / Acc3D strict / Acc3D relax / outliers (evaluation_utils.py:4-19) and, when the reader has cameras,
+  EPE2D / Acc2D (:22-36), on the device (ops.flow_metrics_pairs).
 
 What is new relative to the reference: the permutohedral lattice of pair i+1 is built on the GPU
 on a second HIP stream while pair i trains (the reference builds it in DataLoader worker
@@ -103,6 +104,8 @@ class SyntheticPairs(object):
         for s in range(first_seed, first_seed + count):
             pc1, pc2, sf = synthetic_pair(num_points, s)
             self.items.append(tuple(torch.from_numpy(np.ascontiguousarray(a.T)).to(device) for a in (pc1, pc2, sf)))
+
+    has_cameras = False        # (no 2D metrics)
 
     def __len__(self):
         return len(self.items)
@@ -286,21 +289,53 @@ class Trainer(object):
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
         counts (ragged_groups: <= B pairs and <= RAGGED_POINT_BUDGET points per cloud side a batch).  `val_batches`: the
-        forwards this rank ran."""
-        self.model.eval()
-        agg = collections.OrderedDict()
-        self.val_batches = 0
+        forwards this rank ran.
 
-        def add(flow, sf):
-            for k, v in flow_metrics(flow.t(), sf.t()).items():
-                agg[k] = agg.get(k, 0.0) + v
+        The keys are EPE3D / Acc3DS / Acc3DR / Outliers, plus EPE2D / Acc2D when the reader has cameras (`has_cameras`): the
+        reader decides, not the samples, so every rank issues the same collective.  Each forward is followed on its stream by
+        one hpl_flow_metrics launch over its pairs, into a (len(data), 8) device array at the pairs' sample indices; that array
+        is read back once.  `val_pairs`: this rank's [(index into data, {metric: value})] in sample order."""
+        self.model.eval()
+        cams = bool(getattr(data, 'has_cameras', False))
+        keys = metric_keys(data)
+        self.val_batches = 0
+        self.val_pairs = []
+        n = len(data)
+        if n > 0:
+            sums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
+            stage = ops.MetricsStage(n, self.device)     # pinned descriptor rows, one per sample: no row is refilled in a call
+            nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
+
+            def add(preds, samples):
+                cameras = []
+                for s_ in samples:
+                    cam = getattr(s_, 'camera', None) if cams else None
+                    if cams and cam is None:
+                        raise HplError('validate: the reader has cameras, but sample %d came without one' % (nxt[0] + len(cameras)))
+                    cameras.append(cam)
+                ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras, sums, nxt[0], stage)
+                nxt[0] += len(samples)
+            try:
+                self._validate_forwards(data, batch_size, ragged, add)
+                words = sums.cpu().numpy()               # the one read-back (it follows every launch on this stream)
+            finally:
+                torch.cuda.current_stream(self.device).synchronize()     # the stage's copies have run before it is released
+            self.val_pairs = [(i, ops.flow_metrics_fold(words[i], cams)) for i in range(n)]
+        agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
+        # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
+        # added over the ranks, so all ranks return the metrics of the WHOLE split (and agree on `best` in fit())
+        tot = parallel.sum_over_ranks(agg + [float(n)], device=self.device)
+        self.val_samples = int(tot[-1])         # over all ranks: 0 = no rank had a validation sample
+        return {k: v / max(1.0, tot[-1]) for k, v in zip(keys, tot[:-1])}
+
+    def _validate_forwards(self, data, batch_size, ragged, add):
+        """The forwards of validate(): add(preds, samples) after each, preds[b] the (3, N_b) flow view of samples[b]."""
         if batch_size > 1 and ragged:
             for group in self._ragged_batches(data, batch_size):
                 p1, p2 = [g[0] for g in group], [g[1] for g in group]
                 flows = self.model(p1, p2, self.gen.build_native_batch(p1, p2))      # (a list of one pair: build_native)
                 self.val_batches += 1
-                for f, g in zip(flows, group):
-                    add(f[0], g[2])
+                add([f[0] for f in flows], group)
         elif batch_size > 1:
             for group in self._batches(data, batch_size):
                 p1 = torch.stack([g[0] for g in group])
@@ -308,19 +343,12 @@ class Trainer(object):
                 lat = self.gen.build_native_batch(p1, p2) if len(group) > 1 else self.gen.build_native(p1[0], p2[0])
                 flow = self.model(p1, p2, lat)
                 self.val_batches += 1
-                for b, g in enumerate(group):
-                    add(flow[b], g[2])
+                add(list(flow), group)
         else:
-            for (pc1, pc2, sf), lat in self._lattices(data, list(range(len(data))), False):
-                flow = self.model(pc1[None], pc2[None], lat)
+            for s_, lat in self._lattices(data, list(range(len(data))), False):
+                flow = self.model(s_[0][None], s_[1][None], lat)
                 self.val_batches += 1
-                add(flow[0], sf)
-        # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
-        # added over the ranks, so all ranks return the metrics of the WHOLE split (and agree on `best` in fit())
-        keys = list(agg) if agg else ['EPE3D', 'Acc3DS', 'Acc3DR', 'Outliers']
-        tot = parallel.sum_over_ranks([agg.get(k, 0.0) for k in keys] + [float(len(data))], device=self.device)
-        self.val_samples = int(tot[-1])         # over all ranks: 0 = no rank had a validation sample
-        return {k: v / max(1.0, tot[-1]) for k, v in zip(keys, tot[:-1])}
+                add([flow[0]], [s_])
 
     @staticmethod
     def _batches(data, batch_size):
@@ -388,18 +416,25 @@ class Trainer(object):
             # validate() ends in a collective: every rank calls it whenever the split exists, also with an empty shard
             # (fewer validation samples than ranks); the decision to fall back to the train loss is taken on the
             # globally reduced sample count so that all ranks agree
-            val = tr
+            val, metrics = tr, ''
             if val_data is not None:
                 res = self.validate(val_data)
                 if self.val_samples > 0:
                     val = res['EPE3D']
+                    metrics = '  (val %s)' % ' '.join('%s %.4f' % kv for kv in res.items())
             best = self.min_loss is None or val < self.min_loss
             if best:
                 self.min_loss = val
-            log('epoch %d  train EPE3D %.5f  val EPE3D %.5f%s' % (self.epoch, tr, val, '  (best)' if best else ''))
+            log('epoch %d  train EPE3D %.5f  val EPE3D %.5f%s%s' % (self.epoch, tr, val, '  (best)' if best else '', metrics))
             if ckpt_dir and self.rank == 0:
                 self.save_checkpoint(ckpt_dir, best)
         return self.min_loss
+
+
+def metric_keys(data):
+    """The keys validate() reports for a reader: the four 3D metrics, and EPE2D / Acc2D when it has cameras (`has_cameras`).  Decided
+    from the reader alone, never from its samples: a rank with an empty shard reports (and reduces) the same keys."""
+    return list(ops.METRICS_3D) + (list(ops.METRICS_2D) if getattr(data, 'has_cameras', False) else [])
 
 
 def same_counts(a, b):
@@ -451,7 +486,8 @@ def ragged_groups(counts, batch_size, budget=RAGGED_POINT_BUDGET):
     return out
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line of main(), checked (argparse exits with a message on a bad combination)."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--arch', default='HPLFlowNet', choices=sorted(ARCHS))
     ap.add_argument('--points', type=int, default=8192)
@@ -477,6 +513,9 @@ def main(argv=None):
                          'batch is W x B pairs')
     ap.add_argument('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI'])
     ap.add_argument('--data-root', default=None)
+    ap.add_argument('--kitti-calib', default=None, metavar='DIR',
+                    help='--dataset KITTI: directory of KITTI\'s calib_cam_to_cam/<frame>.txt files; the camera (P_rect_02) of each '
+                         'frame gives the 2D metrics EPE2D / Acc2D (without it KITTI evaluation reports the four 3D metrics)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -485,11 +524,18 @@ def main(argv=None):
         ap.error('--train-batch-size takes 1 .. 64 and applies to training (--evaluate batches with --batch-size)')
     if a.ragged and (not a.evaluate or a.batch_size < 2):
         ap.error('--ragged applies to --evaluate with --batch-size >= 2')
+    if a.kitti_calib is not None and (a.dataset != 'KITTI' or not os.path.isdir(a.kitti_calib)):
+        ap.error('--kitti-calib takes an existing directory and applies to --dataset KITTI')
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
     if a.val_pairs is None:
         a.val_pairs = 2 if a.dataset == 'synthetic' else 0
+    return a
+
+
+def main(argv=None):
+    a = parse_args(argv)
     rank, world, local_rank = parallel.init_distributed()
     dev = torch.device('cuda', local_rank)
     torch.cuda.set_device(dev)
@@ -526,6 +572,7 @@ class _Shard(object):
             self.ids = list(range(rank, n, world))
         if limit > 0:
             self.ids = self.ids[:limit]
+        self.has_cameras = bool(getattr(reader, 'has_cameras', False))     # the reader's answer, whatever this shard holds
 
     def __len__(self):
         return len(self.ids)
@@ -544,8 +591,11 @@ def _real_data(a, tr, dev, rank, world):
     # num_points valid points is evaluated on what it has, not replaced by another frame; training
     # (configs/train_ours.yaml:6) rejects such frames
     if a.dataset == 'KITTI':                        # evaluation only in the reference
-        val = data_mod.KITTI(data_mod.ProcessData(DATA_PROCESS, a.points, True, seed=0), a.data_root, device=dev)
+        val = data_mod.KITTI(data_mod.ProcessData(DATA_PROCESS, a.points, True, seed=0), a.data_root, device=dev,
+                             calib_dir=a.kitti_calib)
         train = None
+        if a.kitti_calib is None:
+            log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')
     else:
         val = data_mod.FlyingThings3DSubset(False, data_mod.ProcessData(DATA_PROCESS, a.points, bool(a.evaluate), seed=0),
                                             a.data_root, device=dev)

@@ -284,6 +284,87 @@ def ragged_stage(pc1s, pc2s, sfs=None):
     return tuple(outs)
 
 
+# --------------------------------------------------------------------------- evaluation metrics
+#: the keys of the 3D metrics (evaluation_utils.py:4-19) and of the 2D pair that needs a camera (:22-36)
+METRICS_3D = ('EPE3D', 'Acc3DS', 'Acc3DR', 'Outliers')
+METRICS_2D = ('EPE2D', 'Acc2D')
+
+
+class MetricsStage(object):
+    """Room for `count` hpl_metrics_pair descriptors: pinned host memory (the source of the asynchronous copy) and its device
+    twin.  Row r belongs to one launch; a row must not be refilled before the copy that read it has run on its stream."""
+
+    SIZE = ctypes.sizeof(_lib.MetricsPair)
+
+    def __init__(self, count, device):
+        self.count = count
+        self.host = torch.empty(count * self.SIZE, dtype=torch.uint8, pin_memory=True)
+        self.dev = torch.empty(count * self.SIZE, dtype=torch.uint8, device=device)
+
+
+_metrics_inflight = collections.deque()      # (event, stage) of calls that brought no stage: alive until their copy has run
+
+
+def _metrics_desc(pred, gt, pc1, camera):
+    n = int(gt.shape[-1])
+    for t, what in ((pred, 'pred'), (gt, 'gt'), (pc1, 'pc1')):
+        if t.dim() != 2 or t.shape[0] != 3 or int(t.shape[1]) != n or t.dtype != torch.float32 or not t.is_cuda:
+            raise _lib.HplError('flow_metrics_pairs: %s must be a (3, %d) float32 device view, got shape %s dtype %s device %s'
+                                % (what, n, tuple(t.shape), t.dtype, t.device))
+    d = _lib.MetricsPair(ptr(pred), ptr(gt), ptr(pc1), n, pred.stride(0), pred.stride(1), gt.stride(0), gt.stride(1),
+                         pc1.stride(0), pc1.stride(1))
+    if camera is not None:
+        if len(camera) != 6:
+            raise _lib.HplError('flow_metrics_pairs: a camera is (f, cx, cy, constx, consty, constz), got %r' % (camera,))
+        d.camera[:] = [float(c) for c in camera]        # (ctypes rounds each to float32)
+        d.has_camera = 1
+    return d
+
+
+def flow_metrics_pairs(preds, gts, pc1s, cameras, out, row=0, stage=None):
+    """The per-pair metric sums of B <= 64 pairs in ONE launch (hpl_flow_metrics) on the current stream.  preds[b], gts[b],
+    pc1s[b]: (3, N_b) float32 device views of any strides (the forward's point-major flow as it comes); cameras[b]: a
+    (f, cx, cy, constx, consty, constz) tuple or None (no 2D metrics).  out: (R, 8) float64 device tensor; pair b's sums go to
+    row `row + b` (flow_metrics_fold turns a row into metric values; slots 5 and 6 stay untouched without a camera).  stage: a
+    MetricsStage whose rows row .. row + B - 1 hold the descriptors; without one the call brings its own."""
+    B = len(preds)
+    if not (len(gts) == len(pc1s) == len(cameras) == B):
+        raise _lib.HplError('flow_metrics_pairs: %d preds, %d gts, %d clouds, %d cameras' % (B, len(gts), len(pc1s), len(cameras)))
+    if out.dtype != torch.float64 or out.dim() != 2 or out.shape[1] != 8 or not out.is_contiguous() or not out.is_cuda \
+            or not 0 <= row or row + B > out.shape[0]:
+        raise _lib.HplError('flow_metrics_pairs: out must be a contiguous (>= %d, 8) float64 device tensor, got %s %s'
+                            % (row + B, tuple(out.shape), out.dtype))
+    descs = (_lib.MetricsPair * max(B, 1))(*[_metrics_desc(p, g, c, cam) for p, g, c, cam in zip(preds, gts, pc1s, cameras)])
+    own = stage is None
+    if own:
+        while _metrics_inflight and _metrics_inflight[0][0].query():
+            _metrics_inflight.popleft()
+        stage, srow = MetricsStage(max(B, 1), out.device), 0
+    else:
+        srow = row
+        if srow + B > stage.count:
+            raise _lib.HplError('flow_metrics_pairs: rows %d .. %d outside a stage of %d' % (srow, srow + B - 1, stage.count))
+    off = srow * MetricsStage.SIZE
+    ctypes.memmove(stage.host.data_ptr() + off, descs, B * MetricsStage.SIZE)
+    check(_lib.load().hpl_flow_metrics(stage.host.data_ptr() + off, B, stage.dev.data_ptr() + off, out[row].data_ptr() if B else
+                                       out.data_ptr(), stream()), 'hpl_flow_metrics')
+    if own:
+        ev = torch.cuda.Event()
+        ev.record()
+        _metrics_inflight.append((ev, stage))
+    return out
+
+
+def flow_metrics_fold(words, camera=True):
+    """One pair's 8 words of hpl_flow_metrics (a host sequence) -> {metric: value}: each sum over the pair's point count, the
+    2D pair only when the pair had a camera."""
+    n = float(words[0])
+    r = dict(zip(METRICS_3D, (float(words[k]) / n for k in (1, 2, 3, 4))))
+    if camera:
+        r.update(zip(METRICS_2D, (float(words[5]) / n, float(words[6]) / n)))
+    return r
+
+
 def round_up(x, m):
     return (x + m - 1) // m * m
 

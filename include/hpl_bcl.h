@@ -372,6 +372,31 @@ int hpl_epe3d(const float *pred, const float *sf, int64_t N, float *grad, float 
  * pred [batch x n][3] and sf (3, batch x n) pair-major; pair_loss[b] (DEVICE, batch floats) = hpl_epe3d of pair b's rows alone,
  * bit for bit (one workgroup per pair, the same rows per thread, the same tree).  1 <= batch <= 64. */
 int hpl_epe3d_pairs(const float *pred, const float *sf, int batch, int64_t n, float *pair_loss, hplStream stream);
+/* One pair of hpl_flow_metrics: n points; component k of point p of pred at pred[k * pred_sc + p * pred_sp] (elements), gt and
+ * pc1 likewise -- (3, N) clouds (sc = N, sp = 1), the point-major [N][3] flow the forward writes (sc = 1, sp = 3) and column
+ * slices of wider buffers are all read in place.  camera = (f, cx, cy, constx, consty, constz) of utils/geometry.py:42-65,
+ * used when has_camera != 0. */
+typedef struct hpl_metrics_pair {
+    const float *pred;
+    const float *gt;
+    const float *pc1;
+    int64_t n;
+    int64_t pred_sc, pred_sp, gt_sc, gt_sp, pc1_sc, pc1_sp;
+    float camera[6];
+    int32_t has_camera;
+    int32_t pad_;
+} hpl_metrics_pair;
+/* The evaluation metrics of `batch` (1 .. 64) pairs in ONE launch (evaluation_utils.py:4-36, utils/geometry.py:6-65), one
+ * workgroup per pair.  out (DEVICE) gets 8 doubles per pair, row b for pairs[b]: [0] n, [1] sum of ||gt - pred||, [2] [3] [4]
+ * the counts of the ACC3DS / ACC3DR / Outliers3D predicates, [5] the sum of the 2D end-point error of pc1 + gt against
+ * pc1 + pred projected into the pair's camera, [6] the count of the ACC2D predicate, [7] 0.  Slots 5 and 6 are not written
+ * for a pair without a camera.  Per point the reference's float32 arithmetic in its order (IEEE division and sqrt); sums
+ * in fp64 and counts as integers in a fixed order, so a pair's row is the same bits alone or anywhere in a batch.
+ * `pairs` (HOST) is copied into `stage` (DEVICE, batch entries) with hipMemcpyAsync on `stream`: pass pinned memory and
+ * keep it unchanged until the copy has run.  HPL_EINVAL before any copy or launch for a batch outside 1 .. 64, a count
+ * < 1, a null pointer or a negative stride. */
+int hpl_flow_metrics(const hpl_metrics_pair *pairs /* HOST */, int batch, hpl_metrics_pair *stage, double *out,
+                     hplStream stream);
 /* optimizer.step() of main.py:216 for the Adam of main.py:138-140 (lr 1e-4, weight_decay 0, no amsgrad) over FLAT fp32 arrays,
  * step >= 1 counting this one: m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g^2;
  * p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps) -- torch's fused Adam operation by operation, the
