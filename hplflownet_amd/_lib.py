@@ -55,6 +55,15 @@ class MetricsPair(ctypes.Structure):
                 ('has_camera', c_i32), ('pad_', c_i32)]
 
 
+class TransformParams(ctypes.Structure):
+    """Mirror of `hpl_transform_params`."""
+    _fields_ = [('m', c_f32 * 9), ('shift', c_f32 * 3), ('m2', c_f32 * 9), ('shift2', c_f32 * 3),
+                ('jitter_sigma1', ctypes.c_double), ('jitter_clip1', ctypes.c_double), ('jitter_sigma2', ctypes.c_double),
+                ('jitter_clip2', ctypes.c_double), ('depth_threshold', c_f32), ('no_corr', c_i32), ('num_points', c_i32),
+                ('allow_less_points', c_i32), ('augment', c_i32), ('pad_', c_i32), ('seed', ctypes.c_uint64),
+                ('counter', ctypes.c_uint64)]
+
+
 class Ref(ctypes.Structure):
     """Mirror of `hpl_ref`."""
     _fields_ = [('buf', c_i32), ('row_off_sym', c_i32), ('rows_sym', c_i32), ('col_off', c_i32), ('cols', c_i32)]
@@ -191,6 +200,12 @@ _SIGNATURES = {
                                         ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp]),
     'hpl_epe3d_pairs': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_vp]),
     'hpl_flow_metrics': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    'hpl_transform_pair': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp,
+                                          c_vp, c_i64, c_vp]),
+    'hpl_transform_workspace_bytes': (c_i64, [c_i64]),
+    'hpl_transform_capacity': (ctypes.c_int, [c_i64, ctypes.c_int, ctypes.POINTER(c_i64)]),
+    'hpl_philox4x32_10': (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32),
+                                         ctypes.POINTER(ctypes.c_uint32)]),
     'hpl_plan_set_unlayout': (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(c_i32), ctypes.POINTER(c_i64), ctypes.c_int]),
     'hpl_plan_profile': (ctypes.c_int, [c_vp, ctypes.c_int]),
     'hpl_plan_guard_trips': (ctypes.c_int, [c_vp, ctypes.POINTER(c_i64)]),

@@ -41,7 +41,8 @@ import os
 import numpy as np
 import torch
 
-__all__ = ['ProcessData', 'Augmentation', 'FlyingThings3DSubset', 'KITTI', 'Sample', 'read_kitti_camera']
+__all__ = ['ProcessData', 'Augmentation', 'DeviceProcessData', 'DeviceAugmentation', 'FlyingThings3DSubset', 'KITTI', 'Sample',
+           'read_kitti_camera']
 
 #: (f, cx, cy, constx, consty, constz) of every FlyingThings3D frame (utils/geometry.py:59 defaults)
 FT3D_CAMERA = (-1050.0, 479.5, 269.5, 0.0, 0.0, 0.0)
@@ -151,6 +152,91 @@ class Augmentation(object):
                     self.no_corr, self.sampler.allow_less_points, self.sampler.num_points))
 
 
+class DeviceProcessData(object):
+    """ProcessData on the device: the same arguments plus `device`; the raw numpy clouds go in, a Sample of
+    (3, k) float32 device tensors -- or (None, None, None) on a rejection -- comes out (ops.TransformRunner over
+    hpl_transform_pair, csrc/transforms.hip).  The sampling draws from a counter-based stream (Philox keyed by `seed`, one
+    counter step per call): the same distribution as the host class, not the same sample; deterministic under a seed."""
+
+    on_device = True
+    augment = False
+
+    def __init__(self, data_process_args, num_points, allow_less_points, seed=None, device='cuda'):
+        from . import ops
+        self.DEPTH_THRESHOLD = data_process_args['DEPTH_THRESHOLD']
+        self.no_corr = data_process_args['NO_CORR']
+        self.num_points = num_points
+        self.allow_less_points = allow_less_points
+        self.rng = np.random.RandomState(seed)
+        self.seed = int(seed) & (2 ** 64 - 1) if seed is not None else int(self.rng.randint(0, 2 ** 63, dtype=np.int64))
+        self.calls = 0
+        self.runner = ops.TransformRunner(device)
+
+    def params(self):
+        """The hpl_transform_params of the next call (draws the host scalars of an augmentation)."""
+        from ._lib import TransformParams
+        p = TransformParams()
+        p.depth_threshold = self.DEPTH_THRESHOLD        # (ctypes rounds it to float32, as numpy's comparison does)
+        p.no_corr = int(bool(self.no_corr))
+        p.num_points = int(self.num_points)
+        p.allow_less_points = int(bool(self.allow_less_points))
+        p.augment = int(self.augment)
+        p.seed = self.seed
+        p.counter = self.calls
+        return p
+
+    def __call__(self, data):
+        pc1, pc2 = data
+        if pc1 is None or pc1.shape[0] == 0:
+            return None, None, None
+        p = self.params()
+        self.calls += 1
+        out = self.runner.run(pc1, pc2, p)
+        return Sample(out) if out[0] is not None else out
+
+    def __repr__(self):
+        return ('%s\n(data_process_args: \n\tDEPTH_THRESHOLD: %s\n\tNO_CORR: %s\n\tallow_less_points: %s\n'
+                '\tnum_points: %s\n\tdevice: %s\n)' % (self.__class__.__name__, self.DEPTH_THRESHOLD, self.no_corr,
+                                                       self.allow_less_points, self.num_points, self.runner.device))
+
+
+class DeviceAugmentation(DeviceProcessData):
+    """Augmentation on the device: per call the scalars are drawn on the host from RandomState(seed) in the reference's order
+    without the jitter and the choice (scale x3, angle, shift x3, cloud 2's angle, shift2 x3); the per-point jitter and the
+    sampling come from the device's counter-based stream (see DeviceProcessData)."""
+
+    augment = True
+
+    def __init__(self, aug_together_args, aug_pc2_args, data_process_args, num_points, allow_less_points=False, seed=None,
+                 device='cuda'):
+        super(DeviceAugmentation, self).__init__(data_process_args, num_points, allow_less_points, seed, device)
+        self.together_args = aug_together_args
+        self.pc2_args = aug_pc2_args
+
+    def params(self):
+        p = super(DeviceAugmentation, self).params()
+        tg, p2, rng = self.together_args, self.pc2_args, self.rng
+        scale = np.diag(rng.uniform(tg['scale_low'], tg['scale_high'], 3).astype(np.float32))
+        m = scale.dot(_rot_y(rng.uniform(-tg['degree_range'], tg['degree_range']), np.float32).T)
+        shift = rng.uniform(-tg['shift_range'], tg['shift_range'], (1, 3)).astype(np.float32)
+        m2 = _rot_y(rng.uniform(-p2['degree_range'], p2['degree_range']), np.float32)
+        shift2 = rng.uniform(-p2['shift_range'], p2['shift_range'], (1, 3)).astype(np.float32)
+        p.m[:] = m.ravel().tolist()
+        p.shift[:] = shift.ravel().tolist()
+        p.m2[:] = m2.ravel().tolist()
+        p.shift2[:] = shift2.ravel().tolist()
+        p.jitter_sigma1, p.jitter_clip1 = float(tg['jitter_sigma']), float(tg['jitter_clip'])
+        p.jitter_sigma2, p.jitter_clip2 = float(p2['jitter_sigma']), float(p2['jitter_clip'])
+        return p
+
+    def __repr__(self):
+        fmt = lambda d: ''.join('\t%-10s %s\n' % (k, d[k]) for k in sorted(d))      # noqa: E731
+        return ('%s\n(together_args: \n%s\npc2_args: \n%s\ndata_process_args: \n\tDEPTH_THRESHOLD: %s\n'
+                '\tNO_CORR: %s\n\tallow_less_points: %s\n\tnum_points: %s\n\tdevice: %s\n)' % (
+                    self.__class__.__name__, fmt(self.together_args), fmt(self.pc2_args), self.DEPTH_THRESHOLD,
+                    self.no_corr, self.allow_less_points, self.num_points, self.runner.device))
+
+
 def _leaf_dirs(root):
     """Sorted directories below `root` that contain no sub-directory (the reference's `useful_paths`)."""
     root = os.path.realpath(os.path.expanduser(root))
@@ -198,8 +284,16 @@ class _PairFolder(object):
     def __getitem__(self, index):
         """-> (pc1, pc2, sf) float32 device tensors (3, N); falls on to the next sample if the
         transform rejects this one (the reference draws a random replacement, :44-47)."""
+        on_device = getattr(self.transform, 'on_device', False)
         for k in range(len(self.samples)):
             path = self.samples[(index + k) % len(self.samples)]
+            if on_device:           # a device transform returns the Sample itself, or (None, None, None) on a rejection
+                out = self.transform(self.load(path))
+                if out[0] is not None:
+                    s_ = out if isinstance(out, Sample) else Sample(out)
+                    s_.camera = self.camera_of(path)
+                    return s_
+                continue
             out = self.transform(self.load(path)) if self.transform is not None else None
             if out is None:
                 pc1, pc2 = self.load(path)

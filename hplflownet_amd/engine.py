@@ -26,6 +26,8 @@ On real data (`--dataset FlyingThings3DSubset|KITTI --data-root DIR`) the traini
 visited in a fresh random order every epoch (DataLoader shuffle=True, main.py:67); validation goes
 through `data.ProcessData` in order (main.py:76-90).  `--init xavier` gives the reference's start
 (xavier-normal weights, zero biases: main_utils.py:33-47, main.py:100-101).
+`--device-transforms` runs both transforms on the device instead (data.DeviceAugmentation / DeviceProcessData: the same
+protocol from a counter-based random stream).
 
     python -m hplflownet_amd.engine --arch HPLFlowNet --points 8192 --pairs 8 --epochs 1 --ckpt-dir /tmp/ck
     python -m hplflownet_amd.engine --evaluate --resume /tmp/ck/model_best.pth.tar --pairs 4
@@ -516,6 +518,10 @@ def parse_args(argv=None):
     ap.add_argument('--kitti-calib', default=None, metavar='DIR',
                     help='--dataset KITTI: directory of KITTI\'s calib_cam_to_cam/<frame>.txt files; the camera (P_rect_02) of each '
                          'frame gives the 2D metrics EPE2D / Acc2D (without it KITTI evaluation reports the four 3D metrics)')
+    ap.add_argument('--device-transforms', action='store_true',
+                    help='--dataset FlyingThings3DSubset|KITTI: run the data transforms on the device (data.DeviceAugmentation for '
+                         'training, data.DeviceProcessData for validation and --evaluate): the same protocol from a counter-based '
+                         'random stream, so a different random sample than the host transforms (DESIGN.md §15)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -526,6 +532,8 @@ def parse_args(argv=None):
         ap.error('--ragged applies to --evaluate with --batch-size >= 2')
     if a.kitti_calib is not None and (a.dataset != 'KITTI' or not os.path.isdir(a.kitti_calib)):
         ap.error('--kitti-calib takes an existing directory and applies to --dataset KITTI')
+    if a.device_transforms and a.dataset == 'synthetic':
+        ap.error('--device-transforms applies to --dataset FlyingThings3DSubset|KITTI (synthetic pairs have no transform)')
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -590,18 +598,21 @@ def _real_data(a, tr, dev, rank, world):
     # NO_CORR True (the two clouds are sampled independently) and allow_less_points True -- a frame with fewer than
     # num_points valid points is evaluated on what it has, not replaced by another frame; training
     # (configs/train_ours.yaml:6) rejects such frames
+    if a.device_transforms:             # the same protocol on the device, from its own random stream
+        process = lambda less: data_mod.DeviceProcessData(DATA_PROCESS, a.points, less, seed=0, device=dev)     # noqa: E731
+        augment = lambda: data_mod.DeviceAugmentation(AUG_TOGETHER, AUG_PC2, DATA_PROCESS, a.points, False,     # noqa: E731
+                                                      seed=1 + rank, device=dev)
+    else:
+        process = lambda less: data_mod.ProcessData(DATA_PROCESS, a.points, less, seed=0)                       # noqa: E731
+        augment = lambda: data_mod.Augmentation(AUG_TOGETHER, AUG_PC2, DATA_PROCESS, a.points, False, seed=1 + rank)  # noqa: E731
     if a.dataset == 'KITTI':                        # evaluation only in the reference
-        val = data_mod.KITTI(data_mod.ProcessData(DATA_PROCESS, a.points, True, seed=0), a.data_root, device=dev,
-                             calib_dir=a.kitti_calib)
+        val = data_mod.KITTI(process(True), a.data_root, device=dev, calib_dir=a.kitti_calib)
         train = None
         if a.kitti_calib is None:
             log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')
     else:
-        val = data_mod.FlyingThings3DSubset(False, data_mod.ProcessData(DATA_PROCESS, a.points, bool(a.evaluate), seed=0),
-                                            a.data_root, device=dev)
-        train = None if a.evaluate else data_mod.FlyingThings3DSubset(
-            True, data_mod.Augmentation(AUG_TOGETHER, AUG_PC2, DATA_PROCESS, a.points, False, seed=1 + rank),
-            a.data_root, device=dev)
+        val = data_mod.FlyingThings3DSubset(False, process(bool(a.evaluate)), a.data_root, device=dev)
+        train = None if a.evaluate else data_mod.FlyingThings3DSubset(True, augment(), a.data_root, device=dev)
     for ds in (train, val):
         msg = ds.check_counts() if ds is not None else None
         if msg:

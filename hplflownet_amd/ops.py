@@ -365,6 +365,123 @@ def flow_metrics_fold(words, camera=True):
     return r
 
 
+# --------------------------------------------------------------------------- data transforms
+def transform_capacity(M, num_points):
+    """The most rows hpl_transform_pair emits for M points: min(num_points, M), or M when num_points <= 0."""
+    cap = ctypes.c_int64()
+    check(_lib.load().hpl_transform_capacity(int(M), int(num_points), ctypes.byref(cap)), 'hpl_transform_capacity')
+    return cap.value
+
+
+class TransformRunner(object):
+    """hpl_transform_pair for one transform object (data.DeviceAugmentation / DeviceProcessData).
+
+    The work runs on a stream of its own: the count read-back then waits for this transform's copies and launches only, not
+    for whatever the caller's stream holds (LatticePipeline calls its source under the lattice stream).  The caller's
+    current stream waits on the transform's event, and the outputs are record_stream-ed to it.  Raw numpy clouds reach the
+    device through a grow-only, double-buffered pinned stage (a slot is refilled only after the event of the copy that read
+    it); the parameters through a pinned stage of their own; the device copy of the clouds and the workspace are grow-only
+    and stream-ordered.  `last_counts` = (valid points, emitted rows) of the last call."""
+
+    PSIZE = ctypes.sizeof(_lib.TransformParams)
+
+    def __init__(self, device='cuda'):
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device('cuda', torch.cuda.current_device())
+        self.stream = torch.cuda.Stream(self.device)
+        self._host = [None, None]
+        self._pstage = [torch.empty(self.PSIZE, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
+        self._ev = [None, None]
+        self._slot = 0
+        self._dev_in = None
+        self._ws = None
+        self._counts = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._counts_host = torch.zeros(2, dtype=torch.int32, pin_memory=True)
+        self.last_counts = None
+
+    @staticmethod
+    def _grow(buf, n, make):
+        if buf is None or buf.numel() < n:
+            return make(max(n, int(1.25 * buf.numel()) if buf is not None else n))
+        return buf
+
+    def _stage_numpy(self, pc1, pc2, M, slot):
+        ev = self._ev[slot]
+        if ev is not None:
+            ev.synchronize()                     # the copy that last read this slot has run
+        self._host[slot] = self._grow(self._host[slot], 6 * M,
+                                      lambda n: torch.empty(n, dtype=torch.float32, pin_memory=True))
+        h = self._host[slot][:6 * M].numpy()
+        h[:3 * M].reshape(M, 3)[:] = pc1[:, :3]
+        h[3 * M:].reshape(M, 3)[:] = pc2[:, :3]
+        self._dev_in = self._grow(self._dev_in, 6 * M,
+                                  lambda n: torch.empty(n, dtype=torch.float32, device=self.device))
+        self._dev_in[:6 * M].copy_(self._host[slot][:6 * M], non_blocking=True)
+        if self._ev[slot] is None:
+            self._ev[slot] = torch.cuda.Event()
+        self._ev[slot].record(self.stream)
+        return self._dev_in[:3 * M], self._dev_in[3 * M:6 * M]
+
+    def run(self, pc1, pc2, params, jitter1=None, jitter2=None, sel1=None, sel2=None):
+        """pc1, pc2: the raw clouds, numpy (M, >= 3) arrays or (M, 3) contiguous float32 device tensors; params: a
+        _lib.TransformParams.  jitter1 / jitter2 / sel1 / sel2: the test hook of hpl_transform_pair (device tensors: (M, 3)
+        float32, int32 indices).  -> (pc1, pc2, sf) contiguous (3, k) float32 device tensors, or (None, None, None) when
+        the pair is rejected."""
+        M = int(pc1.shape[0])
+        if int(pc2.shape[0]) != M:
+            raise _lib.HplError('transform: the clouds have %d and %d points (the reference pairs them point by point)'
+                                % (M, int(pc2.shape[0])))
+        lib = _lib.load()
+        caller = torch.cuda.current_stream(self.device)
+        s = self.stream
+        cap = transform_capacity(M, params.num_points)
+        hooks = (jitter1, jitter2, sel1, sel2)
+        for t, dt in zip(hooks, (torch.float32, torch.float32, torch.int32, torch.int32)):
+            if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != self.device):
+                raise _lib.HplError('transform: hook arrays are contiguous %s tensors on %s' % (dt, self.device))
+        for t in (jitter1, jitter2):
+            if t is not None and t.numel() != 3 * M:
+                raise _lib.HplError('transform: a jitter hook holds (M, 3) = %d values, got %d' % (3 * M, t.numel()))
+        if sel1 is not None and (not 1 <= sel1.numel() <= cap or (sel2 is not None and sel2.numel() != sel1.numel())):
+            raise _lib.HplError('transform: selection hooks hold 1 .. %d indices each, got %d and %s'
+                                % (cap, sel1.numel(), None if sel2 is None else sel2.numel()))
+        with torch.cuda.stream(s):
+            if isinstance(pc1, torch.Tensor):
+                for t in (pc1, pc2):
+                    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or t.device != self.device:
+                        raise _lib.HplError('transform: device clouds are contiguous (M, 3) float32 tensors on %s' % self.device)
+                s.wait_stream(caller)            # the caller may have produced them
+                d1, d2 = pc1, pc2
+            else:
+                if pc1.ndim != 2 or pc1.shape[1] < 3 or pc2.ndim != 2 or pc2.shape[1] < 3:
+                    raise _lib.HplError('transform: numpy clouds are (M, >= 3), got %s and %s' % (pc1.shape, pc2.shape))
+                if any(t is not None for t in hooks):
+                    s.wait_stream(caller)
+                self._slot ^= 1
+                d1, d2 = self._stage_numpy(pc1, pc2, M, self._slot)
+            wsb = lib.hpl_transform_workspace_bytes(M)
+            self._ws = self._grow(self._ws, wsb, lambda n: torch.empty(n, dtype=torch.uint8, device=self.device))
+            out = torch.empty(9 * cap, dtype=torch.float32, device=self.device)
+            pstage = self._pstage[self._slot]
+            ctypes.memmove(pstage.data_ptr(), ctypes.byref(params), self.PSIZE)
+            n_sel = int(sel1.numel()) if sel1 is not None else 0
+            check(lib.hpl_transform_pair(ptr(d1), ptr(d2), M, pstage.data_ptr(), ptr(jitter1), ptr(jitter2), ptr(sel1),
+                                         ptr(sel2), n_sel, ptr(out), ptr(out[3 * cap:]), ptr(out[6 * cap:]), cap,
+                                         ptr(self._counts), ptr(self._ws), wsb, s.cuda_stream), 'hpl_transform_pair')
+            self._counts_host.copy_(self._counts, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(s)
+        done.synchronize()                       # the one read-back: (valid, emitted)
+        V, k = self._counts_host.tolist()
+        self.last_counts = (V, k)
+        caller.wait_event(done)
+        out.record_stream(caller)
+        if k <= 0:
+            return None, None, None
+        return tuple(out[o * cap:o * cap + 3 * k].view(3, k) for o in (0, 3, 6))
+
+
 def round_up(x, m):
     return (x + m - 1) // m * m
 

@@ -397,6 +397,58 @@ typedef struct hpl_metrics_pair {
  * < 1, a null pointer or a negative stride. */
 int hpl_flow_metrics(const hpl_metrics_pair *pairs /* HOST */, int batch, hpl_metrics_pair *stage, double *out,
                      hplStream stream);
+/* The scalars of one hpl_transform_pair call, drawn on the host (transforms/transforms.py:565-606).  m: the together matrix
+ * scale . rot_y^T, row-major (a = p . m + bias); m2: cloud 2's rotation, row-major (b = b . m2^T + shift2).  Jitter k of
+ * component c is clip(jitter_sigmaK * N(0, 1), -jitter_clipK, jitter_clipK) as float32; a clip of 0 gives exactly ±0.  The
+ * depth cut keeps a point when a.z < depth_threshold and b.z < depth_threshold, or always when depth_threshold <= 0.  augment
+ * = 0: ProcessData (a = p1, b = p2, sf = p2 - p1: m, shift, m2, shift2 and the jitter are unused).  seed is the Philox key,
+ * counter the call number (two words of the Philox counter). */
+typedef struct hpl_transform_params {
+    float m[9];
+    float shift[3];
+    float m2[9];
+    float shift2[3];
+    double jitter_sigma1, jitter_clip1, jitter_sigma2, jitter_clip2;
+    float depth_threshold;
+    int32_t no_corr;
+    int32_t num_points;
+    int32_t allow_less_points;
+    int32_t augment;
+    int32_t pad_;
+    uint64_t seed;
+    uint64_t counter;
+} hpl_transform_params;
+/* Augmentation.__call__ / ProcessData.__call__ (transforms/transforms.py:494-640) of ONE pair, from the raw clouds to the
+ * sampled (pc1, pc2, sf), in one enqueue.  pc1, pc2: the clouds as loaded, (M, 3) float32 row-major, the same M (the
+ * reference pairs them point by point).  Per point the reference's operations in its order (bias = shift + jitter1,
+ * a = p1 . m + bias, b = p2 . m + bias, b = b . m2^T + shift2, sf = b - a, b += jitter2 unless no_corr), each product
+ * column as fmaf(z, m[2][c], fmaf(y, m[1][c], x * m[0][c])) -- numpy's float32 chain; then the depth cut (:509-512) and the
+ * sampling (:514-532).  Random draws come from Philox4x32-10 keyed by params->seed, counter (point, counter lo, counter hi,
+ * purpose): 0 jitter 1, 1 jitter 2 (Box-Muller in fp64), 2 / 3 the 63-bit selection keys of cloud 1 / cloud 2.  The emitted
+ * rows: the num_points valid points of smallest (key, index) in ascending key order when at least num_points are valid; every
+ * valid point in index order when num_points <= 0, or when fewer are valid and allow_less_points is set; none (a
+ * rejection) when fewer are valid without it, or when none is.  no_corr: cloud 2's rows are drawn independently from the
+ * same valid set (purpose 3), else they are cloud 1's; sf rows always follow cloud 1.
+ * Outputs: out_pc1 / out_pc2 / out_sf hold `capacity` x 3 floats each; k emitted rows are written as (3, k) row-major at
+ * their start.  counts (DEVICE, 2 int32) = (valid points, k), k = 0 for a rejection -- the one word pair the host reads back.
+ * Test hook (NULL otherwise): jitter1 / jitter2 (DEVICE, (M, 3) float32) replace the jitter draws; sel1 / sel2 (DEVICE,
+ * n_sel indices into the raw clouds, 0 <= index < M; sel2 needed with no_corr) replace the selection when any point is
+ * valid (k = n_sel).  `params` (HOST) is copied with hipMemcpyAsync on `stream` into the workspace: pass pinned memory and
+ * keep it unchanged until the copy has run.  workspace (DEVICE, 256-byte aligned): hpl_transform_workspace_bytes(M).
+ * HPL_EINVAL before any copy or launch for a null or misaligned pointer (arrays 4-byte aligned), M < 1 or M >= 2^31 - 1,
+ * a capacity below what num_points can emit (hpl_transform_capacity), a short workspace, a negative clip, or hook
+ * indices without their pair or outside 1 .. capacity. */
+int hpl_transform_pair(const float *pc1, const float *pc2, int64_t M, const hpl_transform_params *params /* HOST */,
+                       const float *jitter1, const float *jitter2, const int32_t *sel1, const int32_t *sel2, int64_t n_sel,
+                       float *out_pc1, float *out_pc2, float *out_sf, int64_t capacity, int32_t *counts, void *workspace,
+                       int64_t workspace_bytes, hplStream stream);
+/* bytes of hpl_transform_pair's workspace for M points (0 for M outside 1 .. 2^31 - 2) */
+int64_t hpl_transform_workspace_bytes(int64_t M);
+/* *capacity = the most rows hpl_transform_pair can emit for M points: min(num_points, M), or M when num_points <= 0.
+ * HPL_EINVAL for M outside 1 .. 2^31 - 2 or a null pointer. */
+int hpl_transform_capacity(int64_t M, int num_points, int64_t *capacity /* HOST */);
+/* the Philox4x32-10 block hpl_transform_pair draws from, on the host: out = philox(counter[4], key[2]) (HOST arrays) */
+int hpl_philox4x32_10(const uint32_t *counter, const uint32_t *key, uint32_t *out);
 /* optimizer.step() of main.py:216 for the Adam of main.py:138-140 (lr 1e-4, weight_decay 0, no amsgrad) over FLAT fp32 arrays,
  * step >= 1 counting this one: m = lerp(m, g, 1 - beta1); v = beta2 v + (1 - beta2) g^2;
  * p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps) -- torch's fused Adam operation by operation, the
