@@ -37,7 +37,7 @@ def _run_two_ranks(extra, timeout=420, world=2):
     s.close()
     env = dict(os.environ, MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), WORLD_SIZE=str(world), LOCAL_RANK='0',
                HPL_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--no-cpu-baseline'] + extra
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--full', '--no-cpu-baseline'] + extra
     procs = [subprocess.Popen(cmd, cwd=ROOT, env=dict(env, RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                               text=True) for r in reversed(range(world))]
     outs = []

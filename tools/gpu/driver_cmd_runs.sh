@@ -1,11 +1,11 @@
-# The driver's command five times on one box (boxes of the pool and runs on one box differ by a few per cent): every run's line is kept,
+# The driver's command with --full five times on one box (boxes of the pool and runs on one box differ by a few per cent): every run's line is kept,
 # the MEDIAN run by `value` becomes the round's r06_bench_driver_cmd*.json
 cd $GRAFT_REPO_ROOT
 python -c "from hplflownet_amd import build; build.build()" || exit 1      # (a library older than its sources is rebuilt here, not measured)
 O=gpurun_out; mkdir -p $O
 R=${1:-r06}
 for i in 1 2 3 4 5; do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --detail $O/${R}_drv${i}_detail.json > $O/${R}_drv${i}.json 2> /dev/null
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail $O/${R}_drv${i}_detail.json > $O/${R}_drv${i}.json 2> /dev/null
 done
 python - <<PY
 import json, shutil
@@ -13,7 +13,7 @@ runs = []
 for i in range(1, 6):
     d = json.load(open('$O/${R}_drv%d_detail.json' % i))
     runs.append((d['value'], i, d))
-out = ['# tools/gpu/driver_cmd_runs.sh: python bench.py --gpus 1 --steps 20 --warmup 5, five runs back to back on one box',
+out = ['# tools/gpu/driver_cmd_runs.sh: python bench.py --gpus 1 --steps 20 --warmup 5 --full, five runs back to back on one box',
        '# run  value (20 steps)  steady (>= 1 s)  forward-only  dominant launch us  roofline.frac  train ms  board W']
 for v, i, d in runs:
     out.append('%d  %.1f  %.1f  %.1f  %.1f  %.3f  %.2f  %s' % (i, v, d['steady']['value'], d['forward_only']['pairs_per_s'], d['roofline']['avg_launch_us'],

@@ -10,10 +10,10 @@ O=gpurun_out; mkdir -p $O
 R=r06
 export TMPDIR=/tmp
 db() { ls $O/$1/*/$2_results.db $O/$1/$2_results.db 2>/dev/null | head -1; }
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_mfma -o m -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-train-probe --detail '' --no-overlap > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE -d $O/pmc_mfma -o m -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-train-probe --detail '' --no-overlap > /dev/null 2>&1
 python tools/pmc_mfma.py $(db pmc_mfma m) $O/${R}_mfma_pmc > /dev/null
-rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o f -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-train-probe --detail '' --no-overlap > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o w -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-train-probe --detail '' --no-overlap > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/pmc_fetch -o f -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-train-probe --detail '' --no-overlap > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/pmc_write -o w -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-train-probe --detail '' --no-overlap > /dev/null 2>&1
 python tools/pmc_traffic.py $(db pmc_fetch f) $(db pmc_write w) $O/${R}_pmc_traffic.json > $O/${R}_pmc_traffic.txt
 rocprofv3 --kernel-trace -d $O/ft -o ft -- python tools/chain_run.py frustum 8192 > $O/${R}_chain_run.txt 2>&1
 python tools/forward_trace.py $(db ft ft) > $O/${R}_step_timeline.txt
@@ -24,10 +24,10 @@ head -6 $O/${R}_mfma_pmc.txt | cut -c1-200; head -3 $O/${R}_pmc_traffic.txt; tai
 
 python -m pytest tests -m gpu -q > $O/${R}_pytest_gpu.txt 2>&1; echo "pytest rc=$?"; grep -n "passed\|failed" $O/${R}_pytest_gpu.txt | tail -2
 
-python bench.py --detail $O/${R}_bench_plain_detail.json > $O/${R}_bench_plain.json 2> $O/${R}_bench_plain.err
-python bench.py --gpus 1 --steps 20 --warmup 5 --detail $O/${R}_bench_driver_cmd_detail.json > $O/${R}_bench_driver_cmd.json 2> /dev/null
-rocprofv3 --kernel-trace --stats -d $O/prof_k -o k -- python bench.py --detail $O/${R}_bench_detail.json > $O/${R}_bench.json 2> /dev/null
-python tools/prof_summary.py $(db prof_k k) "python bench.py" > $O/${R}_kernel_stats.txt; rm -rf $O/prof_k
+python bench.py --full --detail $O/${R}_bench_plain_detail.json > $O/${R}_bench_plain.json 2> $O/${R}_bench_plain.err
+python bench.py --gpus 1 --steps 20 --warmup 5 --full --detail $O/${R}_bench_driver_cmd_detail.json > $O/${R}_bench_driver_cmd.json 2> /dev/null
+rocprofv3 --kernel-trace --stats -d $O/prof_k -o k -- python bench.py --full --detail $O/${R}_bench_detail.json > $O/${R}_bench.json 2> /dev/null
+python tools/prof_summary.py $(db prof_k k) "python bench.py --full" > $O/${R}_kernel_stats.txt; rm -rf $O/prof_k
 head -12 $O/${R}_kernel_stats.txt | cut -c1-160
 HPL_FUSED_SPLIT=2 rocprofv3 --kernel-trace -d $O/lt -o lt -- python tools/lattice_trace.py run 8192 > $O/${R}_lattice_run.txt 2>&1
 python tools/lattice_trace.py show $(db lt lt) > $O/${R}_lattice_show.txt
@@ -41,9 +41,9 @@ for f in ('bench_plain', 'bench_driver_cmd'):
 PY
 
 python tools/point_sweep.py > $O/${R}_point_count_sweep.txt 2>&1; cat $O/${R}_point_count_sweep.txt
-python bench.py --train --steps 40 --warmup 5 --no-cpu-baseline --detail $O/${R}_train_bench_detail.json > $O/${R}_train_bench.json 2>/dev/null; tail -c 600 $O/${R}_train_bench.json; echo
-rocprofv3 --kernel-trace --stats -d $O/prof_t -o t -- python bench.py --train --steps 60 --no-cpu-baseline --detail '' > /dev/null 2>&1
-python tools/prof_summary.py $(db prof_t t) "python bench.py --train --steps 60 --no-cpu-baseline" > $O/${R}_train_kernel_stats.txt; rm -rf $O/prof_t
+python bench.py --train --steps 40 --warmup 5 --full --no-cpu-baseline --detail $O/${R}_train_bench_detail.json > $O/${R}_train_bench.json 2>/dev/null; tail -c 600 $O/${R}_train_bench.json; echo
+rocprofv3 --kernel-trace --stats -d $O/prof_t -o t -- python bench.py --train --steps 60 --full --no-cpu-baseline --detail '' > /dev/null 2>&1
+python tools/prof_summary.py $(db prof_t t) "python bench.py --train --steps 60 --full --no-cpu-baseline" > $O/${R}_train_kernel_stats.txt; rm -rf $O/prof_t
 PROBE_ONLY=native rocprofv3 --kernel-trace -d $O/prof_n -o n -- python tools/train_native_probe.py > $O/${R}_train_probe.txt 2>&1
 python tools/train_timeline.py $(db prof_n n) > $O/${R}_train_timeline.txt; rm -rf $O/prof_n
 head -1 $O/${R}_train_timeline.txt; tail -2 $O/${R}_train_timeline.txt

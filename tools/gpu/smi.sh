@@ -1,8 +1,9 @@
 cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
+O=${1:?usage: tools/gpu/smi.sh OUTDIR}
+mkdir -p $O
 which rocm-smi amd-smi 2>&1 | head -2
 rocm-smi --showclocks --showtemp --showpower --json 2>/dev/null | head -c 1500; echo
-python bench.py --steps 12000 --no-cpu-baseline > gpurun_out/soak2.json 2>/dev/null &
+python bench.py --steps 12000 --full --no-cpu-baseline > $O/soak2.json 2>/dev/null &
 BP=$!
 sleep 25
 for i in 1 2 3 4 5 6; do
@@ -16,4 +17,4 @@ done
 wait $BP
 python -c "
 import json
-d=json.load(open('gpurun_out/soak2.json')); print(round(d['value'],1), d['roofline']['avg_launch_us'], d['roofline'].get('shader_clock_ghz'))"
+d=json.load(open('$O/soak2.json')); print(round(d['value'],1), d['roofline']['avg_launch_us'], d['roofline'].get('shader_clock_ghz'))"

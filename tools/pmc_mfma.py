@@ -2,8 +2,8 @@
 """Executed MFMA work per kernel from a rocprofv3 --pmc run of bench.py (rocpd sqlite .db).
 
     rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
-        -d gpurun_out/pmc_mfma -o m -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-overlap
-    python tools/pmc_mfma.py gpurun_out/pmc_mfma/m_results.db profiles/r02_mfma_pmc
+        -d out/pmc_mfma -o m -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-overlap
+    python tools/pmc_mfma.py out/pmc_mfma/m_results.db profiles/r02_mfma_pmc
 
 writes <prefix>.txt (per-kernel table) and <prefix>.json (what bench.py reads: executed GFLOP per launch of the
 dominant gather-GEMM).  The unit of SQ_INSTS_VALU_MFMA_MOPS_F32 is calibrated inside the same run on

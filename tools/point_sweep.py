@@ -4,10 +4,10 @@
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run(extra):
-    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '60', '--warmup', '5', '--no-cpu-baseline', '--no-train-probe'] + extra,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '60', '--warmup', '5', '--full', '--no-cpu-baseline', '--no-train-probe'] + extra,
                          stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True).stdout
     return json.loads([l for l in out.splitlines() if l.startswith('{')][0])
-print('# python bench.py --points N --steps 60 --warmup 5 --no-cpu-baseline --no-train-probe   (one MI355X; pipelined output checked against the single-stream forward)')
+print('# python bench.py --points N --steps 60 --warmup 5 --full --no-cpu-baseline --no-train-probe   (one MI355X; pipelined output checked against the single-stream forward)')
 print('%-28s %9s %8s %14s %12s %12s %8s %6s' % ('workload', 'pairs/s', 'ms/step', 'fwd-only p/s', 'lattice ms', 'forward ms', 'board W', 'check'))
 for name, extra in [('HPLFlowNet N=%d' % n, ['--points', str(n)]) for n in (500, 1024, 2048, 4096, 8192, 16384, 32768)] + \
         [('HPLFlowNetShallow N=4096', ['--arch', 'HPLFlowNetShallow', '--points', '4096']), ('HPLFlowNet N=8192 surface', ['--data', 'surface'])]:
