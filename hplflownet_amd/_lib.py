@@ -48,6 +48,12 @@ class GConvDesc(ctypes.Structure):
                 ('a_guard', c_vp), ('y_guard', c_vp), ('guard_trips', c_vp)]
 
 
+class QueryInfo(ctypes.Structure):
+    """Mirror of `hpl_query_info`."""
+    _fields_ = [('slots', c_vp), ('keys', c_vp), ('ids', c_vp), ('mask', ctypes.c_uint64), ('mm', c_vp), ('pmm', c_vp),
+                ('batch', c_i32), ('pair_shift', c_i32), ('scale', c_f32), ('H0', c_i32)]
+
+
 class MetricsPair(ctypes.Structure):
     """Mirror of `hpl_metrics_pair`."""
     _fields_ = [('pred', c_vp), ('gt', c_vp), ('pc1', c_vp), ('n', c_i64), ('pred_sc', c_i64), ('pred_sp', c_i64),
@@ -184,6 +190,9 @@ _SIGNATURES = {
     'hpl_lattice_advance': (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_int)]),
     'hpl_lattice_tables': (ctypes.POINTER(LevelTables), [c_vp]),
     'hpl_lattice_extras': (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(c_i64)]),
+    'hpl_lattice_query_info': (ctypes.c_int, [c_vp, ctypes.POINTER(QueryInfo)]),
+    'hpl_lattice_query': (ctypes.c_int, [ctypes.POINTER(QueryInfo), c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.c_int, c_vp, c_vp, c_vp,
+                                         c_vp]),
     'hpl_plan_create': (c_vp, [ctypes.POINTER(Op), ctypes.c_int, ctypes.POINTER(Buf), ctypes.c_int,
                                ctypes.POINTER(Weight), ctypes.c_int, ctypes.POINTER(c_vp), ctypes.c_int]),
     'hpl_plan_destroy': (None, [c_vp]),

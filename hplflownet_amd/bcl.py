@@ -380,8 +380,10 @@ class BilateralConvFlex(nn.Module):
     def get_filter_size(self):
         return self.filter_size
 
-    def forward_cl(self, x, in_cloud, blur, out_cloud, out=None):
-        """Channel-last core.  x [N_in | H, C_in]; blur: NbrTable [15, H]; clouds: ops.CloudTables."""
+    def forward_cl(self, x, in_cloud, blur, out_cloud, out=None, keep=None):
+        """Channel-last core.  x [N_in | H, C_in]; blur: NbrTable [15, H]; clouds: ops.CloudTables.  keep (a list, slicing
+        layers): the vertex matrix the slice reads is appended to it -- in front of a trailing bias-only 1x1 when there is one
+        (flownet.DenseFlow); the same launches either way."""
         H = blur.t.shape[1]
         if self.do_splat:
             if in_cloud.H != H:
@@ -403,6 +405,8 @@ class BilateralConvFlex(nn.Module):
             # weight gradient all shrink).  sum_r(bary_r) = 1 up to fp32 rounding (transforms.py:340-345),
             # the difference (<= 1e-6 |b|) is inside the tolerance; gradients are those of the same function.
             y = _run_conv_stack(s, mods[:-1], blur, H, self.filter_size, self.use_leaky)
+            if keep is not None:
+                keep.append(y)
             conv = mods[-1]
             b = conv.bias if bias is None else (conv.bias + bias if conv.bias is not None else bias)
             if torch.is_grad_enabled() and y.requires_grad:
@@ -410,8 +414,16 @@ class BilateralConvFlex(nn.Module):
             else:
                 z = ops.slice_raw(y, out_cloud.bary, out_cloud.off, out_cloud.N)
             return ops.gconv(z, conv.weight, b, None, out_cloud.N, 1, act=ACT_NONE, bwd_mode='dense', out=out)
-        y = _run_conv_stack(s, self.blur_conv, blur, H, self.filter_size, self.use_leaky,
-                            out=None if self.do_slice else out)
+        if keep is not None and self.do_slice and len(mods) >= 2 and not isinstance(mods[-1], _ConvReLU):
+            z = _run_conv_stack(s, mods[:-1], blur, H, self.filter_size, self.use_leaky)
+            keep.append(z)
+            conv = _conv_of(mods[-1])
+            y = ops.gconv(z, conv.weight, conv.bias, None, H, 1, act=ACT_NONE, bwd_mode='dense', slope=_slope(self.use_leaky))
+        else:
+            y = _run_conv_stack(s, self.blur_conv, blur, H, self.filter_size, self.use_leaky,
+                                out=None if self.do_slice else out)
+            if keep is not None:
+                keep.append(y)
         if not self.do_slice:
             return y
         if torch.is_grad_enabled() and (y.requires_grad or (bias is not None and bias.requires_grad)):

@@ -361,6 +361,19 @@ extern "C" int hpl_lattice_keys_pair(const float *pc1, const float *pc2, const i
     return HPL_OK;
 }
 
+namespace hpl {
+namespace lat {
+void staged_table(const void *workspace, int64_t n1, int64_t n2, const int64_t **keys, const int32_t **ids, uint64_t *mask,
+                  const int32_t **mm) {
+    const WS w = carve(const_cast<void *>(workspace), n1, n2);
+    *keys = w.c[0].tkeys;
+    *ids = w.c[0].tid;
+    *mask = w.c[0].mask;
+    *mm = w.mm;
+}
+}  // namespace lat
+}  // namespace hpl
+
 extern "C" int64_t hpl_lattice_workspace_bytes(int64_t n1, int64_t n2) {
     if (n1 <= 0 || n2 <= 0) return 0;
     return carve(nullptr, n1, n2).bytes;

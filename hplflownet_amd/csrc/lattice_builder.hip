@@ -11,6 +11,7 @@
 //          levels), the counts stay on the device and come back once; hpl_lattice_advance only waits for that one
 //          read-back and fills in the tables.
 #include "common.h"
+#include "lattice_common.h"
 #include "lattice_fused.h"
 
 #include <new>
@@ -41,6 +42,7 @@ struct hpl_lattice {
     const float *pc[2] = {nullptr, nullptr};
     // per level scratch kept until its second half
     void *ws = nullptr;
+    void *ws0 = nullptr;           // level 0's hash workspace (its table of cloud 1 answers lattice queries)
     int32_t *vk[2] = {nullptr, nullptr}, *counts = nullptr, *off[2] = {nullptr, nullptr};
     float *bary[2] = {nullptr, nullptr};
     const int32_t *prev_vk[2] = {nullptr, nullptr};
@@ -84,6 +86,7 @@ int level_head(hpl_lattice *b) {
     b->bary[1] = b->take<float>(4 * n1);
     const int64_t wsb = hpl_lattice_workspace_bytes(n0, n1);
     b->ws = b->take<char>(wsb);
+    if (L == 0) b->ws0 = b->ws;
     b->off[0] = b->take<int32_t>(4 * n0);
     b->off[1] = b->take<int32_t>(4 * n1);
     b->vk[0] = b->take<int32_t>(16 * n0);
@@ -552,5 +555,29 @@ extern "C" int hpl_lattice_extras(const hpl_lattice *b, const void **out, int64_
     HPL_REQUIRE(b && b->done && out && arena_used, "hpl_lattice_extras: no finished build");
     for (int L = 0; L < b->spec.n_levels; ++L) { out[2 * L] = b->bary1[L]; out[2 * L + 1] = b->off1[L]; }
     *arena_used = b->cur - b->arena;
+    return HPL_OK;
+}
+
+extern "C" int hpl_lattice_query_info(const hpl_lattice *b, hpl_query_info *out) {
+    HPL_REQUIRE(b && b->done && out, "hpl_lattice_query_info: no finished build");
+    *out = hpl_query_info{};
+    out->scale = b->spec.scale[0];
+    out->H0 = (int32_t)b->tab[0].H0;
+    out->batch = 1;
+    if (b->last_fused) {        // the fused driver's level-0 table (a batch rebuilt under the default bounds: its last layout)
+        const fused::Level &V = b->plan.lv[0];
+        out->slots = V.tslot[0];
+        out->mask = (uint64_t)lat::pow2_at_least(8 * (int64_t)V.n_host[0]) - 1;
+        out->mm = V.dims + fused::D_MM;
+        out->batch = b->plan.batch;
+        if (b->plan.batch > 1) {
+            out->pmm = V.pmm;
+            out->pair_shift = V.pair_shift;
+        }
+        return HPL_OK;
+    }
+    // staged driver (spec.fused == 0, or a single pair that outgrew a bound): level 0's hash workspace, kept in the arena
+    HPL_REQUIRE(b->ws0 && b->batch == 1, "hpl_lattice_query_info: no level-0 table of the staged driver");
+    lat::staged_table(b->ws0, b->n_start[0], b->n_start[1], &out->keys, &out->ids, &out->mask, &out->mm);
     return HPL_OK;
 }

@@ -104,6 +104,11 @@ __device__ __forceinline__ void lattice_point(float q0, float q1, float q2, int6
     }
 }
 
+// cloud 1's table of the staged hpl_lattice_hash that ran in `workspace` over (n1, n2) points (lattice.hip; lattice queries):
+// packed keys, vertex ids, slots - 1 and the key range [8] the keys were packed over
+void staged_table(const void *workspace, int64_t n1, int64_t n2, const int64_t **keys, const int32_t **ids, uint64_t *mask,
+                  const int32_t **mm);
+
 inline int64_t pow2_at_least(int64_t x) { int64_t p = 64; while (p < x) p <<= 1; return p; }
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {

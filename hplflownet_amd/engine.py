@@ -27,7 +27,9 @@ visited in a fresh random order every epoch (DataLoader shuffle=True, main.py:67
 through `data.ProcessData` in order (main.py:76-90).  `--init xavier` gives the reference's start
 (xavier-normal weights, zero biases: main_utils.py:33-47, main.py:100-101).
 `--device-transforms` runs both transforms on the device instead (data.DeviceAugmentation / DeviceProcessData: the same
-protocol from a counter-based random stream).
+protocol from a counter-based random stream).  `--evaluate --dense` on real data also reports the metrics of
+the flow at every valid point of each frame, answered from the sampled forward (flownet.DenseFlow): an
+interpolation of the sampled forward, not the paper's protocol.
 
     python -m hplflownet_amd.engine --arch HPLFlowNet --points 8192 --pairs 8 --epochs 1 --ckpt-dir /tmp/ck
     python -m hplflownet_amd.engine --evaluate --resume /tmp/ck/model_best.pth.tar --pairs 4
@@ -286,7 +288,7 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data, batch_size=1, ragged=False):
+    def validate(self, data, batch_size=1, ragged=False, dense=False):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -296,33 +298,67 @@ class Trainer(object):
         The keys are EPE3D / Acc3DS / Acc3DR / Outliers, plus EPE2D / Acc2D when the reader has cameras (`has_cameras`): the
         reader decides, not the samples, so every rank issues the same collective.  Each forward is followed on its stream by
         one hpl_flow_metrics launch over its pairs, into a (len(data), 8) device array at the pairs' sample indices; that array
-        is read back once.  `val_pairs`: this rank's [(index into data, {metric: value})] in sample order."""
+        is read back once.  `val_pairs`: this rank's [(index into data, {metric: value})] in sample order.
+
+        dense=True (a DenseFrames reader): every forward also answers the flow at all valid points of its frames
+        (DenseFlow.query); those flows go through the same metrics into a second array, and the keys gain dense_<metric> plus
+        dense_coverage (the mean query coverage) and dense_full (the fraction of queries whose vertices were all found), all
+        means over pairs."""
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
+        dkeys = ['dense_' + k for k in keys] + ['dense_coverage', 'dense_full'] if dense else []
         self.val_batches = 0
         self.val_pairs = []
+        self._dense = None
         n = len(data)
         if n > 0:
             sums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
             stage = ops.MetricsStage(n, self.device)     # pinned descriptor rows, one per sample: no row is refilled in a call
+            if dense:
+                dsums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
+                dstage = ops.MetricsStage(n, self.device)
+                dcov = torch.zeros((n, 2), dtype=torch.float64, device=self.device)
+                from .flownet import DenseFlow
+                self._dense = DenseFlow(self.model)
             nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
 
-            def add(preds, samples):
+            def cameras_of(samples):
                 cameras = []
                 for s_ in samples:
                     cam = getattr(s_, 'camera', None) if cams else None
                     if cams and cam is None:
                         raise HplError('validate: the reader has cameras, but sample %d came without one' % (nxt[0] + len(cameras)))
                     cameras.append(cam)
-                ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras, sums, nxt[0], stage)
+                return cameras
+
+            def add(preds, samples):
+                ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras_of(samples), sums,
+                                       nxt[0], stage)
                 nxt[0] += len(samples)
+
+            def add_dense(qflows, covs, samples):
+                fulls = [s_.dense for s_ in samples]
+                ops.flow_metrics_pairs(qflows, [f[2] for f in fulls], [f[0] for f in fulls], cameras_of(samples), dsums, nxt[0],
+                                       dstage)
+                for b, c in enumerate(covs):
+                    dcov[nxt[0] + b, 0] = c.double().mean()
+                    dcov[nxt[0] + b, 1] = (c == 1).double().mean()
+            self._dense_add = add_dense if dense else None
             try:
                 self._validate_forwards(data, batch_size, ragged, add)
                 words = sums.cpu().numpy()               # the one read-back (it follows every launch on this stream)
+                if dense:
+                    dwords, dcv = dsums.cpu().numpy(), dcov.cpu().numpy()
             finally:
                 torch.cuda.current_stream(self.device).synchronize()     # the stage's copies have run before it is released
+                self._dense = self._dense_add = None
             self.val_pairs = [(i, ops.flow_metrics_fold(words[i], cams)) for i in range(n)]
+            if dense:
+                for i, v in self.val_pairs:
+                    v.update({'dense_' + k: x for k, x in ops.flow_metrics_fold(dwords[i], cams).items()})
+                    v['dense_coverage'], v['dense_full'] = float(dcv[i, 0]), float(dcv[i, 1])
+        keys = keys + dkeys
         agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
         # added over the ranks, so all ranks return the metrics of the WHOLE split (and agree on `best` in fit())
@@ -335,7 +371,7 @@ class Trainer(object):
         if batch_size > 1 and ragged:
             for group in self._ragged_batches(data, batch_size):
                 p1, p2 = [g[0] for g in group], [g[1] for g in group]
-                flows = self.model(p1, p2, self.gen.build_native_batch(p1, p2))      # (a list of one pair: build_native)
+                flows = self._forward(p1, p2, self.gen.build_native_batch(p1, p2), group)      # (a list of one pair: build_native)
                 self.val_batches += 1
                 add([f[0] for f in flows], group)
         elif batch_size > 1:
@@ -343,14 +379,27 @@ class Trainer(object):
                 p1 = torch.stack([g[0] for g in group])
                 p2 = torch.stack([g[1] for g in group])
                 lat = self.gen.build_native_batch(p1, p2) if len(group) > 1 else self.gen.build_native(p1[0], p2[0])
-                flow = self.model(p1, p2, lat)
+                flow = self._forward(p1, p2, lat, group)
                 self.val_batches += 1
                 add(list(flow), group)
         else:
             for s_, lat in self._lattices(data, list(range(len(data))), False):
-                flow = self.model(s_[0][None], s_[1][None], lat)
+                flow = self._forward(s_[0][None], s_[1][None], lat, [s_])
                 self.val_batches += 1
                 add([flow[0]], [s_])
+
+    def _forward(self, p1, p2, lat, samples):
+        """model(p1, p2, lat); under validate(dense=True) through DenseFlow, the frames' full clouds queried behind it (their
+        metrics are added before the sampled ones': both write the rows from the same sample index)."""
+        if self._dense is None:
+            return self.model(p1, p2, lat)
+        flow, state = self._dense.forward(p1, p2, lat)
+        qs = [s_.dense[0] for s_ in samples]
+        qf, cov = self._dense.query(state, qs if state.batch > 1 else qs[0])
+        if state.batch == 1:
+            qf, cov = [qf], [cov]
+        self._dense_add(qf, cov, samples)
+        return flow
 
     @staticmethod
     def _batches(data, batch_size):
@@ -522,6 +571,9 @@ def parse_args(argv=None):
                     help='--dataset FlyingThings3DSubset|KITTI: run the data transforms on the device (data.DeviceAugmentation for '
                          'training, data.DeviceProcessData for validation and --evaluate): the same protocol from a counter-based '
                          'random stream, so a different random sample than the host transforms (DESIGN.md §15)')
+    ap.add_argument('--dense', action='store_true',
+                    help='with --evaluate on FlyingThings3DSubset / KITTI: also the metrics of the flow at every valid point of each '
+                         'frame, answered from the sampled forward (DenseFlow, DESIGN.md §16; not the paper\'s protocol)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -534,6 +586,8 @@ def parse_args(argv=None):
         ap.error('--kitti-calib takes an existing directory and applies to --dataset KITTI')
     if a.device_transforms and a.dataset == 'synthetic':
         ap.error('--device-transforms applies to --dataset FlyingThings3DSubset|KITTI (synthetic pairs have no transform)')
+    if a.dense and (not a.evaluate or a.dataset == 'synthetic'):
+        ap.error('--dense applies to --evaluate with --dataset FlyingThings3DSubset|KITTI')
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -592,6 +646,51 @@ class _Shard(object):
         return point_counts(self.reader, self.ids[i])
 
 
+class _Both(object):
+    """A reader's transform that also runs `full` on the same loaded frame (DenseFrames)."""
+
+    def __init__(self, sampled, full, keep):
+        self.sampled, self.full, self.keep = sampled, full, keep
+        self.on_device = getattr(sampled, 'on_device', False)
+        self.sampler = getattr(sampled, 'sampler', sampled)      # (what _PairFolder.point_counts reads)
+
+    def __call__(self, data):
+        self.keep[0] = self.full(data)
+        return self.sampled(data)
+
+
+class DenseFrames(object):
+    """A reader whose samples also carry `.dense` = (pc1, pc2, sf) of every valid point of their frame, (3, M) float32 device
+    tensors in index order with sf = pc2 - pc1: `full` is a ProcessData / DeviceProcessData with num_points = 0 and
+    allow_less_points, applied to the same loaded frame as the reader's own transform (which gives the sampled pair)."""
+
+    def __init__(self, reader, full):
+        self.reader = reader
+        self._last = [None]
+        reader.transform = _Both(reader.transform, full, self._last)
+        self.has_cameras = bool(getattr(reader, 'has_cameras', False))
+        self.device = reader.device
+
+    def __len__(self):
+        return len(self.reader)
+
+    def check_counts(self):
+        return self.reader.check_counts()
+
+    def point_counts(self, i):
+        return point_counts(self.reader, i)
+
+    def __getitem__(self, i):
+        s_ = self.reader[i]
+        out = self._last[0]                   # the full transform of the frame the sample came from (the last one loaded)
+        if out is None or out[0] is None:
+            raise HplError('DenseFrames: the frame of sample %d has no valid point' % i)
+        if not all(torch.is_tensor(t) for t in out):
+            out = tuple(torch.from_numpy(np.ascontiguousarray(t[:, :3].T, dtype=np.float32)).to(self.device) for t in out)
+        s_.dense = tuple(out)
+        return s_
+
+
 def _real_data(a, tr, dev, rank, world):
     log = print if rank == 0 else (lambda *_: None)
     # the published evaluation protocol (configs/test_ours_KITTI.yaml:9,36-37, test_ours_FlyingThings3D.yaml:9,35-36):
@@ -622,9 +721,13 @@ def _real_data(a, tr, dev, rank, world):
         log('note: evaluating the first %d samples of each rank\'s shard only (--%s)' % (cap, 'val-pairs' if train is not None else 'pairs'))
     if train is not None and a.pairs > 0:
         log('note: training on the first %d samples of each rank\'s shard only (--pairs)' % a.pairs)
+    if a.dense:       # every valid point of each frame, in index order, beside the sampled pair (loaded once)
+        full = data_mod.DeviceProcessData(DATA_PROCESS, 0, True, seed=0, device=dev) if a.device_transforms else \
+            data_mod.ProcessData(DATA_PROCESS, 0, True, seed=0)
+        val = DenseFrames(val, full)
     val = _Shard(val, rank, world, cap)
     if train is None:
-        res = tr.validate(val, a.batch_size, a.ragged)
+        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -11,6 +11,7 @@ the reference forward by writes into column slices of one buffer per layer input
 Level L (0-based) hosts bcn{L+1} (Down, shared by both clouds), bcn{L+1}_ (Up) and, for
 L >= 2, corr{L-1}.
 """
+import ctypes
 import os
 import weakref
 
@@ -18,10 +19,10 @@ import torch
 import torch.nn as nn
 
 from . import _lib, ops
-from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, NbrTable, pointwise_conv,
+from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, NbrTable, _ConvReLU, _conv_of, pointwise_conv,
                   to_channel_first, to_channel_last)
 
-__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur']
+__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow']
 
 
 # ----------------------------------------------------------------------------- lattice container
@@ -226,6 +227,8 @@ class _FlowNetBase(nn.Module):
     #: inference on a device-built lattice runs as ONE native call (plan.ForwardPlan: the same launches issued by
     #: csrc/executor.hip instead of ~130 Python round trips); False forces the Python path below
     native_forward = not os.environ.get('HPL_NO_NATIVE')
+    #: DenseFlow.forward: a list the pair-batched inference path appends bcn1_'s vertex activation to (None: off)
+    _dense_keep = None
 
     def __init__(self, args):
         super(_FlowNetBase, self).__init__()
@@ -325,7 +328,7 @@ class _FlowNetBase(nn.Module):
             arena = getattr(generated_data, '_arena', None)
         if arena is not None:
             arena.record_stream(torch.cuda.current_stream(dev))
-        if self.native_forward and self.pair_batched and not torch.is_grad_enabled() and \
+        if self.native_forward and self.pair_batched and not torch.is_grad_enabled() and self._dense_keep is None and \
                 (native_lat is not None or isinstance(generated_data, DeviceLattice)):
             plan = self.forward_plan()
             if plan.accepts(generated_data):
@@ -430,8 +433,8 @@ class _FlowNetBase(nn.Module):
                 parts.append((down[0][L].shape[1], down[0][L]))
             x = _assemble(lv.H[0], parts, dev)
 
-            def produce(out, layer=layer, x=x, lv=lv):
-                return layer.forward_cl(x, None, lv.blur[0], lv.clouds[0], out=out)
+            def produce(out, layer=layer, x=x, lv=lv, keep=self._dense_keep if L == 0 else None):
+                return layer.forward_cl(x, None, lv.blur[0], lv.clouds[0], out=out, keep=keep)
             up, up_c = produce, layer.num_output[-1]
         y = up(None)                                           # [N, HEAD_IN]
         y = pointwise_conv(y, self.conv2.conv, True, self.use_leaky)
@@ -521,3 +524,150 @@ def load_reference_checkpoint(model, checkpoint, strict=True):
     sd = obj.get('state_dict', obj) if isinstance(obj, dict) else obj
     sd = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
     return model.load_state_dict(sd, strict=strict)
+
+
+# ----------------------------------------------------------------------------- dense flow
+class DenseState(object):
+    """What DenseFlow.forward keeps for later queries: the lattice (its arena holds the level-0 table of cloud 1), the vertex
+    activation Z the last Up layer slices ([H0, C] float32, all pairs) and the number of pairs.
+
+    Zw: HPLFlowNet only, made by the first query call with more rows than H0 and kept for later ones -- bcn1_'s trailing 1x1
+    applied to Z on the vertices ([H0, 1024] float32, a second ~106 MB per pair at N = 8 192).  Which side of the slice that
+    1x1 runs on is decided per query call from its total row count, so a point's flow can differ in its last bits with the
+    number of queries it is asked with (both orders are the same function, within the rounding of the GEMM)."""
+
+    def __init__(self, lat, Z, batch):
+        self.lat, self.Z, self.batch = lat, Z, batch
+        self.Zw = None
+
+
+class DenseFlow(object):
+    """Scene flow at any query points from one sampled forward.
+
+    The output at a pc1 point depends on that point only through its level-0 barycentric slice of bcn1_ (the last Up layer)
+    and the per-point head conv2 -> conv3 -> conv4.  `forward` runs the model's pair-batched inference path (the native
+    plan's launches) and also keeps bcn1_'s vertex activation Z (bcn1_'s stack minus its trailing bias-only 1x1 in
+    HPLFlowNet, C = 1024, ~106 MB per pair at N = 8 192; the whole stack in HPLFlowNetShallow, C = 128).  `query` locates points in pc1's level-0 lattice (hpl_lattice_query: no
+    insertion), slices Z there and runs the head:
+
+        df = DenseFlow(model)                       # eval-mode model, under torch.no_grad()
+        flow, state = df.forward(pc1, pc2, lat)     # flow == model(pc1, pc2, lat), bit for bit
+        qflow, cov = df.query(state, q)             # (3, Q) query flow, (Q,) coverage
+
+    A query whose simplex vertices are not all vertices of pc1's lattice gets the found ones only (renormalize: rescaled to sum
+    to 1); coverage 0 leaves the head's bias-only output, which the caller masks.  Batches (lattices of build_native_batch)
+    take lists of B query clouds and return lists.  Lattices without a native level-0 table (the reference wire format),
+    training lattices, autograd and mismatched shapes raise HplError before any launch."""
+
+    #: rows per pass of the query head: a 1024-wide fp32 matrix reaches the 2 GiB limit of the 32-bit offsets near 524 k rows
+    CHUNK = 65536
+    MAX_CHUNK = (1 << 31) // (4 * 1024) - 1
+
+    def __init__(self, model):
+        if not isinstance(model, _FlowNetBase):
+            raise _lib.HplError('DenseFlow wraps an HPLFlowNet or HPLFlowNetShallow')
+        self.model = model
+
+    def _refuse(self):
+        if torch.is_grad_enabled():
+            raise _lib.HplError('DenseFlow is inference only: run it under torch.no_grad()')
+        if self.model.training:
+            raise _lib.HplError('DenseFlow needs the model in eval mode')
+
+    def forward(self, pc1, pc2, lat):
+        """-> (flow as model(pc1, pc2, lat) returns it, DenseState).  lat: a NativeLattice of build_native /
+        build_native_batch."""
+        self._refuse()
+        info = getattr(lat, 'query_info', None)
+        if info is None or getattr(lat, 'tables', None) is None:
+            raise _lib.HplError('DenseFlow needs a natively built lattice (build_native / build_native_batch): this one has no '
+                                'level-0 table to query')
+        B = batch_of(pc1, pc2, lat, False, True)
+        dev = pc1[0].device if isinstance(pc1, (list, tuple)) else pc1.device
+        if not dev.type == 'cuda':
+            raise _lib.HplError('the HIP path needs device tensors (no CPU fallback)')
+        keep = []
+        self.model._dense_keep = keep            # the pair-batched Python path: the native plan's launches, bcn1_'s Z kept
+        try:
+            flow = self.model(pc1, pc2, lat)
+        finally:
+            self.model._dense_keep = None
+        if len(keep) != 1 or keep[0].shape[0] != int(lat.tables[0].H0):
+            raise _lib.HplError('DenseFlow: the forward did not run the pair-batched path')
+        return flow, DenseState(lat, keep[0], B)
+
+    def query(self, state, q, renormalize=True, chunk=None):
+        """q: (3, Q) float32 device tensor (single pair), or a list of B (3, Q_b) tensors (batch) -> (qflow (3, Q), coverage
+        (Q,)), or two lists."""
+        self._refuse()
+        if not isinstance(state, DenseState):
+            raise _lib.HplError('query takes the state DenseFlow.forward returned')
+        chunk = self.CHUNK if chunk is None else int(chunk)
+        if chunk < 1 or chunk > self.MAX_CHUNK:
+            raise _lib.HplError('chunk of %d rows (1 .. %d)' % (chunk, self.MAX_CHUNK))
+        listed = isinstance(q, (list, tuple))
+        qs = list(q) if listed else [q]
+        if state.batch > 1 and (not listed or len(qs) != state.batch):
+            raise _lib.HplError('a lattice of %d pairs takes a list of %d query clouds' % (state.batch, state.batch))
+        if state.batch == 1 and listed and len(qs) != 1:
+            raise _lib.HplError('a single-pair lattice takes one query cloud, got %d' % len(qs))
+        dev = state.Z.device
+        for t in qs:
+            if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != 3 or t.dtype != torch.float32 or t.device != dev:
+                raise _lib.HplError('every query cloud is a (3, Q) float32 tensor on %s' % dev)
+        counts = [int(t.shape[1]) for t in qs]
+        Q = sum(counts)
+        prefix = [0]
+        for c in counts:
+            prefix.append(prefix[-1] + c)
+        qcat = (qs[0] if len(qs) == 1 else torch.cat(qs, dim=1)).contiguous()
+        qflow = torch.empty((Q, 3), dtype=torch.float32, device=dev)
+        cov = torch.empty((Q,), dtype=torch.float32, device=dev)
+        if Q:
+            bary, off = self.locate(state, qcat, prefix, renormalize, cov)
+            for s in range(0, Q, chunk):
+                e = min(Q, s + chunk)
+                self.head(state, bary[:, s:e].contiguous(), off[:, s:e].contiguous(), qflow[s:e], Q)
+        if not listed:
+            return qflow.t(), cov
+        return [qflow[a:b].t() for a, b in zip(prefix[:-1], prefix[1:])], [cov[a:b] for a, b in zip(prefix[:-1], prefix[1:])]
+
+    def locate(self, state, q, prefix, renormalize, cov):
+        """hpl_lattice_query of (3, Q) queries -> bary (4, Q), off (4, Q); coverage into `cov`."""
+        L = _lib.load()
+        Q = q.shape[1]
+        bary = torch.empty((4, Q), dtype=torch.float32, device=q.device)
+        off = torch.empty((4, Q), dtype=torch.int32, device=q.device)
+        pre = (ctypes.c_int64 * len(prefix))(*prefix)
+        _lib.check(L.hpl_lattice_query(ctypes.byref(state.lat.query_info), q.data_ptr(), Q, pre if state.batch > 1 else None,
+                                       1 if renormalize else 0, bary.data_ptr(), off.data_ptr(), cov.data_ptr(), _lib.stream()),
+                   'hpl_lattice_query')
+        return bary, off
+
+    def head(self, state, bary, off, out, q_total):
+        """Slice Z at (bary, off) [n queries], bcn1_'s trailing 1x1 + bias (HPLFlowNet), conv2, conv3, conv4 -> out [n, 3]."""
+        m = self.model
+        layer = m.bcn1_
+        n = bary.shape[1]
+        bias = layer.bias if layer.use_bias else None
+        mods = list(layer.blur_conv)
+        reorder = len(mods) >= 2 and not isinstance(mods[-1], _ConvReLU)
+        if not reorder:
+            y = ops.slice_raw(state.Z, bary, off, n, bias=bias)
+        else:
+            conv = _conv_of(mods[-1])
+            H0 = state.Z.shape[0]
+            # both biases after the slice on either side, so that a query of partial or no coverage gets the same head input
+            b = conv.bias if bias is None else (bias if conv.bias is None else (conv.bias + bias))
+            if q_total > H0:          # more queries than vertices: the 1x1 on the vertices once (HPL_COND_SHRINK's other side)
+                W = state.Zw
+                if W is None:
+                    W = state.Zw = ops.gconv(state.Z, conv.weight, None, None, H0, 1, act=ops.ACT_NONE, bwd_mode='dense')
+                y = ops.slice_raw(W, bary, off, n, bias=b)
+            else:
+                z = ops.slice_raw(state.Z, bary, off, n)
+                y = ops.gconv(z, conv.weight, b, None, n, 1, act=ops.ACT_NONE, bwd_mode='dense')
+        y = pointwise_conv(y, m.conv2.conv, True, m.use_leaky)
+        y = pointwise_conv(y, m.conv3.conv, True, m.use_leaky)
+        pointwise_conv(y, m.conv4, False, m.use_leaky, out=out)
+        return out

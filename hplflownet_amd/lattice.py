@@ -490,6 +490,8 @@ class NativeLattice(object):
     #: a ragged batch (build_native_batch of lists): True, and the pairs' point counts [(N1_b, N2_b)]
     ragged = False
     point_counts = None
+    #: _lib.QueryInfo of the build's level-0 table of cloud 1 (hpl_lattice_query_info)
+    query_info = None
 
     def __init__(self, arena, tables, n_levels, extras, wide_up):
         self.arena, self.tables, self.n_levels, self.extras, self.wide_up = arena, tables, n_levels, extras, wide_up
@@ -788,9 +790,12 @@ class NativeLatticeBuild(object):
                         self.nb.observe([(int(arr[L].H0), int(arr[L].H1)) for L in range(n)])
                     if first:
                         torch.cuda.empty_cache()       # (the loose first arena's block would otherwise stay reserved beside the tight ones)
+                qinfo = _lib.QueryInfo()           # where the level-0 table of cloud 1 lives (DenseFlow's queries)
+                check(self.nb.lib.hpl_lattice_query_info(self.handle, ctypes.byref(qinfo)), 'hpl_lattice_query_info')
                 self.nb.release(self.handle)
                 self.handle = None
                 lat = NativeLattice(self.arena, arr, n, [int(e or 0) for e in extras], self.gen.wide_up)
+                lat.query_info = qinfo
                 lat.arena_used = used.value
                 if self.batch > 1:
                     lat.batch, lat.pair_counts = self.batch, pair_counts

@@ -848,6 +848,37 @@ const hpl_level_tables *hpl_lattice_tables(const hpl_lattice *b);
  * out[2*L+1] = off1; and the bytes of the arena in use */
 int hpl_lattice_extras(const hpl_lattice *b, const void **out /* HOST, 2 * n_levels */, int64_t *arena_used);
 
+/* ------------------------------------------------------------------------ *
+ * Lattice queries (csrc/lattice_query.hip): where arbitrary points fall in level 0 of cloud 1 of a finished build, without
+ * inserting.  The forward's level-0 slice of cloud 1 (bcn1_, models/HPLFlowNet.py:418-430) at the queries' own simplices.
+ * ------------------------------------------------------------------------ */
+typedef struct hpl_query_info {
+    const void *slots;        /* fused build: cloud 1's level-0 table, 16-byte slots {key lo, key hi, first entry, vertex id} */
+    const int64_t *keys;      /* staged build (a single pair that outgrew its bounds, or spec.fused == 0): packed keys ... */
+    const int32_t *ids;       /* ... and the vertex id of each slot of the same table */
+    uint64_t mask;            /* slots of the table - 1 */
+    const int32_t *mm;        /* DEVICE [8]: the level's per-coordinate key minima [4] and maxima [4] (single pair) */
+    const int32_t *pmm;       /* DEVICE [batch][8]: every pair's own range (batch > 1), else NULL */
+    int32_t batch, pair_shift; /* pairs of the build; a batch's packed key is pair << pair_shift | key within the pair's range */
+    float scale;              /* level-0 scale (scales_filter_map[0][0]) */
+    int32_t H0;               /* level-0 vertices of cloud 1, all pairs (the ids are global, pair-major) */
+} hpl_query_info;
+
+/* Call right after hpl_lattice_advance reported done (the pointers stay valid as long as the arena and until the next begin on
+ * `b` rewrites the arena; no launch, no copy).  HPL_EINVAL without a finished build. */
+int hpl_lattice_query_info(const hpl_lattice *b, hpl_query_info *out /* HOST */);
+/* Per query point q (3, Q) float32: its 4 level-0 simplex vertices and barycentric weights (the float statements of the
+ * builders' keys stage), each vertex looked up in cloud 1's table.  A vertex whose key lies outside the level's (a batch: its
+ * pair's) per-coordinate key range is missing without a probe (the packing is only injective inside it); so is one the table
+ * does not hold.  Outputs: off (4, Q) int32 vertex ids (a missing vertex: 0, weight 0), bary (4, Q) float32, coverage (Q)
+ * float32 = 1 when every vertex of nonzero weight was found, else the sum of the found weights.  renormalize != 0: the found
+ * weights of a query with 0 < coverage < 1 are divided by its coverage (a fully covered query keeps its weights' bits).
+ * pair_prefix (HOST, batch + 1 ints, NULL for batch 1): queries [pair_prefix[b], pair_prefix[b + 1]) belong to pair b.
+ * HPL_EINVAL before any launch for bad arguments (Q < 1 or >= 2^31, null or misaligned pointers, a prefix that does not
+ * start at 0, decreases or ends short of Q).  Stream-ordered, no host synchronisation. */
+int hpl_lattice_query(const hpl_query_info *info /* HOST */, const float *q, int64_t Q, const int64_t *pair_prefix /* HOST */,
+                      int renormalize, float *bary, int32_t *off, float *coverage, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
