@@ -193,6 +193,8 @@ _SIGNATURES = {
     'hpl_lattice_query_info': (ctypes.c_int, [c_vp, ctypes.POINTER(QueryInfo)]),
     'hpl_lattice_query': (ctypes.c_int, [ctypes.POINTER(QueryInfo), c_vp, c_i64, ctypes.POINTER(c_i64), ctypes.c_int, c_vp, c_vp, c_vp,
                                          c_vp]),
+    'hpl_knn_interp': (ctypes.c_int, [c_vp, c_i64, c_vp, ctypes.c_int, c_vp, c_i64, ctypes.c_int, c_f32, ctypes.c_int,
+                                      ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp, c_vp]),
     'hpl_plan_create': (c_vp, [ctypes.POINTER(Op), ctypes.c_int, ctypes.POINTER(Buf), ctypes.c_int,
                                ctypes.POINTER(Weight), ctypes.c_int, ctypes.POINTER(c_vp), ctypes.c_int]),
     'hpl_plan_destroy': (None, [c_vp]),

@@ -288,7 +288,7 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data, batch_size=1, ragged=False, dense=False):
+    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -303,7 +303,10 @@ class Trainer(object):
         dense=True (a DenseFrames reader): every forward also answers the flow at all valid points of its frames
         (DenseFlow.query); those flows go through the same metrics into a second array, and the keys gain dense_<metric> plus
         dense_coverage (the mean query coverage) and dense_full (the fraction of queries whose vertices were all found), all
-        means over pairs."""
+        means over pairs.  dense_fill='knn' (with dense_k neighbours): the part of a query the lattice does not
+        cover is filled from the sampled flow (DenseFlow.query(fill='knn')); the same keys, then of the filled flow."""
+        if dense_fill is not None and not dense:
+            raise HplError('validate: dense_fill applies to dense=True')
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
@@ -321,6 +324,7 @@ class Trainer(object):
                 dcov = torch.zeros((n, 2), dtype=torch.float64, device=self.device)
                 from .flownet import DenseFlow
                 self._dense = DenseFlow(self.model)
+                self._dense_fill = (dense_fill, dense_k)
             nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
 
             def cameras_of(samples):
@@ -395,7 +399,8 @@ class Trainer(object):
             return self.model(p1, p2, lat)
         flow, state = self._dense.forward(p1, p2, lat)
         qs = [s_.dense[0] for s_ in samples]
-        qf, cov = self._dense.query(state, qs if state.batch > 1 else qs[0])
+        fill, k = self._dense_fill
+        qf, cov = self._dense.query(state, qs if state.batch > 1 else qs[0], fill=fill, k=k)
         if state.batch == 1:
             qf, cov = [qf], [cov]
         self._dense_add(qf, cov, samples)
@@ -574,6 +579,10 @@ def parse_args(argv=None):
     ap.add_argument('--dense', action='store_true',
                     help='with --evaluate on FlyingThings3DSubset / KITTI: also the metrics of the flow at every valid point of each '
                          'frame, answered from the sampled forward (DenseFlow, DESIGN.md §16; not the paper\'s protocol)')
+    ap.add_argument('--dense-fill', default=None, choices=['knn'],
+                    help='with --dense: fill the part of each query that the sampled lattice does not cover by inverse-distance '
+                         'interpolation of the sampled flow from the --dense-k nearest sampled points (DESIGN.md §17)')
+    ap.add_argument('--dense-k', type=int, default=None, metavar='K', help='neighbours of --dense-fill knn (1 .. 8, default 3)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -588,6 +597,11 @@ def parse_args(argv=None):
         ap.error('--device-transforms applies to --dataset FlyingThings3DSubset|KITTI (synthetic pairs have no transform)')
     if a.dense and (not a.evaluate or a.dataset == 'synthetic'):
         ap.error('--dense applies to --evaluate with --dataset FlyingThings3DSubset|KITTI')
+    if a.dense_fill is not None and not a.dense:
+        ap.error('--dense-fill applies to --dense')
+    if a.dense_k is not None and (a.dense_fill is None or not 1 <= a.dense_k <= 8):
+        ap.error('--dense-k takes 1 .. 8 and applies to --dense-fill knn')
+    a.dense_k = a.dense_k or 3
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -727,7 +741,7 @@ def _real_data(a, tr, dev, rank, world):
         val = DenseFrames(val, full)
     val = _Shard(val, rank, world, cap)
     if train is None:
-        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense)
+        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -536,9 +536,35 @@ class DenseState(object):
     1x1 runs on is decided per query call from its total row count, so a point's flow can differ in its last bits with the
     number of queries it is asked with (both orders are the same function, within the rounding of the GEMM)."""
 
-    def __init__(self, lat, Z, batch):
+    def __init__(self, lat, Z, batch, pc1=None, flow=None):
         self.lat, self.Z, self.batch = lat, Z, batch
         self.Zw = None
+        self._pc1, self._flow = pc1, flow          # the forward's own pc1 argument and result, as given (no launch, no copy)
+        self._fill = None
+
+    def fill_inputs(self):
+        """What query(fill='knn') interpolates from, made by the first filled query and kept: the packed sampled pc1
+        (3, sum N_b), the forward's flow rows [sum N_b, 3] (both copies of the state's own: later edits of the tensors the
+        forward took and returned do not reach them) and the pairs' point prefix (B + 1 host ints)."""
+        if self._fill is None:
+            pc1, flow, B = self._pc1, self._flow, self.batch
+            if pc1 is None or flow is None:
+                raise _lib.HplError('fill=\'knn\' needs a state that kept the sampled cloud and its flow')
+            if isinstance(pc1, (list, tuple)):       # the forward's own row order: pair-major
+                counts = [int(p.shape[1]) for p in pc1]
+                packed = torch.cat(list(pc1), dim=1)
+                rows = torch.cat([f[0].t() for f in flow], dim=0)
+            else:
+                n = int(pc1.shape[-1])
+                counts = [n] * B
+                packed = (pc1.reshape(1, 3, n) if B == 1 else pc1).transpose(0, 1).reshape(3, B * n).clone()
+                rows = flow.transpose(1, 2).reshape(B * n, 3).clone()
+            prefix = [0]
+            for c in counts:
+                prefix.append(prefix[-1] + c)
+            self._fill = (packed.contiguous(), rows.contiguous(), prefix)
+            self._pc1 = self._flow = None
+        return self._fill
 
 
 class DenseFlow(object):
@@ -594,14 +620,23 @@ class DenseFlow(object):
             self.model._dense_keep = None
         if len(keep) != 1 or keep[0].shape[0] != int(lat.tables[0].H0):
             raise _lib.HplError('DenseFlow: the forward did not run the pair-batched path')
-        return flow, DenseState(lat, keep[0], B)
+        return flow, DenseState(lat, keep[0], B, pc1, flow)
 
-    def query(self, state, q, renormalize=True, chunk=None):
+    def query(self, state, q, renormalize=True, chunk=None, fill=None, k=3):
         """q: (3, Q) float32 device tensor (single pair), or a list of B (3, Q_b) tensors (batch) -> (qflow (3, Q), coverage
-        (Q,)), or two lists."""
+        (Q,)), or two lists.  fill='knn' (DESIGN.md §17): a query of coverage c < 1 gets c * (the lattice answer) + (1 - c) *
+        (the forward's flow interpolated from its pair's k nearest sampled points, ops.knn_interpolate); coverage is returned
+        as the lattice gave it."""
         self._refuse()
         if not isinstance(state, DenseState):
             raise _lib.HplError('query takes the state DenseFlow.forward returned')
+        if fill is not None:
+            if fill != 'knn':
+                raise _lib.HplError('fill = %r (None or \'knn\')' % (fill,))
+            if not renormalize:
+                raise _lib.HplError('fill=\'knn\' blends with the renormalised lattice answer: renormalize=False is refused')
+            if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
+                raise _lib.HplError('fill=\'knn\' takes k in 1 .. 8, got %r' % (k,))
         chunk = self.CHUNK if chunk is None else int(chunk)
         if chunk < 1 or chunk > self.MAX_CHUNK:
             raise _lib.HplError('chunk of %d rows (1 .. %d)' % (chunk, self.MAX_CHUNK))
@@ -628,6 +663,9 @@ class DenseFlow(object):
             for s in range(0, Q, chunk):
                 e = min(Q, s + chunk)
                 self.head(state, bary[:, s:e].contiguous(), off[:, s:e].contiguous(), qflow[s:e], Q)
+            if fill is not None:      # one launch over the whole batch: pair b's queries see pair b's sample only
+                packed, rows, rp = state.fill_inputs()
+                ops.knn_interpolate(packed, rows, qcat, k=k, ref_prefix=rp, q_prefix=prefix, out=qflow, coverage=cov)
         if not listed:
             return qflow.t(), cov
         return [qflow[a:b].t() for a, b in zip(prefix[:-1], prefix[1:])], [cov[a:b] for a, b in zip(prefix[:-1], prefix[1:])]

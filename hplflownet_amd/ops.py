@@ -365,6 +365,74 @@ def flow_metrics_fold(words, camera=True):
     return r
 
 
+# --------------------------------------------------------------------------- nearest neighbours
+def _soa3(x, what):
+    """A (3, n) float32 device cloud with unit stride along its points (rows may be views of a wider buffer)."""
+    if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] != 3 or x.dtype != torch.float32 or not x.is_cuda:
+        raise _lib.HplError('knn_interpolate: %s must be a (3, n) float32 device tensor, got %s' % (
+            what, (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x)))
+    if x.requires_grad:
+        raise _lib.HplError('knn_interpolate has no autograd: %s requires grad' % what)
+    n = x.shape[1]
+    if x.stride(0) < max(n, 1) or (n > 1 and x.stride(1) != 1):
+        x = x.contiguous()           # (after which a row starts max(n, 1) elements behind the previous one)
+    return x, max(n, 1) if x.is_contiguous() else x.stride(0)
+
+
+def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=None, return_neighbors=False, out=None,
+                    coverage=None):
+    """hpl_knn_interp on the current stream: for every query of q (3, Q) its k nearest points of ref (3, N),
+    exact, and the inverse-distance interpolation sum w_i v_i / sum w_i, w_i = 1 / (d2_i + eps), of values [N, C] (C <= 16)
+    -> [Q, C]; a query equal to a reference point gets that point's row bit for bit.  ref_prefix / q_prefix (host sequences of
+    B + 1 ints from 0 to N / Q): B pairs, every query searching its own pair's points.  return_neighbors: -> (out, idx (k, Q)
+    int32 into ref, dist2 (k, Q) float32), ascending; a pair of fewer than k points leaves idx = -1, dist2 = +inf.
+    out + coverage (Q,): the blend form -- `out` [Q, C] holds a base value per query and is updated in place to
+    coverage * base + (1 - coverage) * interpolation; rows of coverage 1 are neither searched nor written (their neighbour
+    columns keep idx = -1, dist2 = +inf).  No autograd: a tensor that requires grad raises HplError."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
+        raise _lib.HplError('knn_interpolate: k = %r (an int in 1 .. 8)' % (k,))
+    ref, ref_ld = _soa3(ref, 'ref')
+    q, q_ld = _soa3(q, 'q')
+    N, Q = ref.shape[1], q.shape[1]
+    dev = ref.device
+    if not torch.is_tensor(values) or values.dim() != 2 or values.shape[0] != N or values.dtype != torch.float32 or \
+            values.device != dev or q.device != dev:
+        raise _lib.HplError('knn_interpolate: values must be a (%d, C) float32 tensor on %s, and q on the same device' % (N, dev))
+    if values.requires_grad:
+        raise _lib.HplError('knn_interpolate has no autograd: values requires grad')
+    values = values.contiguous()
+    C = values.shape[1]
+    rp = [0, N] if ref_prefix is None else [int(x) for x in ref_prefix]
+    qp = [0, Q] if q_prefix is None else [int(x) for x in q_prefix]
+    if len(rp) != len(qp) or len(rp) < 2 or rp[-1] != N or qp[-1] != Q:
+        raise _lib.HplError('knn_interpolate: the prefixes hold B + 1 entries each and end at N = %d and Q = %d, got %s and %s'
+                            % (N, Q, rp, qp))
+    B = len(rp) - 1
+    if (out is None) != (coverage is None):
+        raise _lib.HplError('knn_interpolate: out (the base values) and coverage come together')
+    if out is not None:
+        for t, shape, what in ((out, (Q, C), 'out'), (coverage, (Q,), 'coverage')):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev or \
+                    not t.is_contiguous() or t.requires_grad:
+                raise _lib.HplError('knn_interpolate: %s must be a contiguous %s float32 tensor on %s' % (what, shape, dev))
+    else:
+        out = torch.empty((Q, C), dtype=torch.float32, device=dev)
+    idx = dist2 = None
+    if return_neighbors:
+        if coverage is None:
+            idx = torch.empty((k, Q), dtype=torch.int32, device=dev)
+            dist2 = torch.empty((k, Q), dtype=torch.float32, device=dev)
+        else:
+            idx = torch.full((k, Q), -1, dtype=torch.int32, device=dev)
+            dist2 = torch.full((k, Q), float('inf'), dtype=torch.float32, device=dev)
+    if Q == 0:
+        return (out, idx, dist2) if return_neighbors else out
+    check(_lib.load().hpl_knn_interp(ref.data_ptr(), ref_ld, values.data_ptr(), C, q.data_ptr(), q_ld, k, float(eps), B,
+                                     (ctypes.c_int64 * (B + 1))(*rp), (ctypes.c_int64 * (B + 1))(*qp), ptr(idx), ptr(dist2),
+                                     out.data_ptr(), ptr(coverage), stream()), 'hpl_knn_interp')
+    return (out, idx, dist2) if return_neighbors else out
+
+
 # --------------------------------------------------------------------------- data transforms
 def transform_capacity(M, num_points):
     """The most rows hpl_transform_pair emits for M points: min(num_points, M), or M when num_points <= 0."""

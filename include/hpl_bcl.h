@@ -879,6 +879,32 @@ int hpl_lattice_query_info(const hpl_lattice *b, hpl_query_info *out /* HOST */)
 int hpl_lattice_query(const hpl_query_info *info /* HOST */, const float *q, int64_t Q, const int64_t *pair_prefix /* HOST */,
                       int renormalize, float *bary, int32_t *off, float *coverage, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * k nearest neighbours and inverse-distance interpolation (csrc/knn_interp.hip): the feature propagation of point-based
+ * scene-flow networks, exact by brute force.  Fills the dense queries the level-0 lattice does not cover.
+ * ------------------------------------------------------------------------ */
+/* For every query q (3, Q) float32 SoA (row stride q_ld >= Q): its k (1 .. 8) nearest points of ref (3, N) float32 SoA (row
+ * stride ref_ld >= N) and the interpolation of val [N][C] float32 row-major (1 <= C <= 16) from them.  batch (1 .. 64) pairs:
+ * ref_prefix / q_prefix (HOST, batch + 1 ints each, from 0 to N / Q, non-decreasing) give every pair's points and queries; a
+ * query searches its own pair's points only (a pair with queries has >= 1 point).  The prefixes travel in the kernel arguments:
+ * stream-ordered, no copy, no host synchronisation.
+ * Arithmetic (float32, no contraction; tests/knn_oracle.py restates it in numpy): d2 = (dx * dx + dy * dy) + dz * dz with
+ * dx = q.x - p.x; candidates in index order, an entry replaced only by a strictly smaller d2 (ties: the smaller index; a d2
+ * that is not below +inf never enters); w_i = 1 / (d2_i + eps); interp = (sum_i w_i * v_i) / (sum_i w_i), i ascending; a
+ * nearest d2 of exactly 0 copies that point's row bit for bit.  A query with no neighbour at all (finite coordinates so far
+ * apart that every d2 overflows to +inf) gets idx = -1 throughout and a NaN interpolation (0 / 0), also through the blend.
+ * idx (k, Q) int32 / dist2 (k, Q) float32, both optional: the neighbours in ascending d2, indices into the packed ref; a pair
+ * of fewer than k points leaves idx = -1, dist2 = +inf, and such entries take no part in the interpolation.
+ * out [Q][C] float32.  coverage == NULL: out = interp.  coverage (Q) float32: out holds a base value per query and is updated in
+ * place: a query of coverage == 1 is neither searched nor written (out, idx, dist2 keep their bits), any other gets
+ * coverage * base + (1 - coverage) * interp.
+ * HPL_EINVAL before any launch (and without a device): k, C, batch out of range; eps < 0 or not finite; a prefix that does not
+ * start at 0 or decreases; a row stride below its count; null ref / val / q / out / prefixes; misaligned arrays; Q * C,
+ * N * C or k * Q >= 2^31.  Q == 0 is a no-op. */
+int hpl_knn_interp(const float *ref, int64_t ref_ld, const float *val, int C, const float *q, int64_t q_ld, int k, float eps,
+                   int batch, const int64_t *ref_prefix /* HOST */, const int64_t *q_prefix /* HOST */, int32_t *idx,
+                   float *dist2, float *out, const float *coverage, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif

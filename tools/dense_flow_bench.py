@@ -8,8 +8,13 @@ Per M in --sizes (HPLFlowNet, hash init, eval mode, no grad), all times from dev
   slice     hpl_slice of Z at those points (the head's first step, alone);
   query     DenseFlow.query of the M points (lookup + slice + trailing 1x1 + conv2 / conv3 / conv4), and head = query - lookup
             - slice;
-  coverage  mean coverage and the fraction of fully covered queries.
---lookup-only: only hpl_lattice_query, --reps times per size (what `rocprofv3 --kernel-trace --stats` is run on)."""
+  coverage  mean coverage and the fraction of fully covered queries;
+  fill      (profiles/dense_fill_bench.txt) hpl_knn_interp at k = --k over the M queries in the coverage form
+            query(fill='knn') uses (fully covered lanes idle), beside the plain form over all M queries (no lane idle) and
+            over the uncovered queries only, selected beforehand (what compacting them first could reach, its select and
+            scatter not counted); query_fill = DenseFlow.query(fill='knn') whole.
+--lookup-only / --fill-only: only hpl_lattice_query / only the coverage-form hpl_knn_interp, --reps times per size (what
+`rocprofv3 --kernel-trace --stats` is run on)."""
 import argparse
 import json
 import os
@@ -40,6 +45,8 @@ def main():
     ap.add_argument('--points', type=int, default=8192)
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--lookup-only', action='store_true')
+    ap.add_argument('--fill-only', action='store_true')
+    ap.add_argument('--k', type=int, default=3)
     a = ap.parse_args()
     import hplflownet_amd as H
     from hplflownet_amd import ops
@@ -68,6 +75,13 @@ def main():
             if a.lookup_only:
                 rows.append(dict(M=M, lookup_ms=lookup))
                 continue
+            if a.fill_only:
+                base, _ = df.query(state, q)
+                base = base.t().contiguous()
+                spc, sfl, _ = state.fill_inputs()
+                fill = timed(lambda: ops.knn_interpolate(spc, sfl, q, k=a.k, out=base, coverage=cov), a.reps)
+                rows.append(dict(M=M, k=a.k, fill_ms=fill))
+                continue
             fwd_model = timed(lambda: m(p1[None], p2[None], lat), a.reps)
             fwd_dense = timed(lambda: df.forward(p1[None], p2[None], lat), a.reps)
             bary, off = df.locate(state, q, [0, M], True, cov)
@@ -80,12 +94,21 @@ def main():
             df.query(state, q)
             sl = timed(slice_all, a.reps)
             qt = timed(lambda: df.query(state, q), a.reps)
-            _, c = df.query(state, q)
+            qb, c = df.query(state, q)
+            base = qb.t().contiguous()
+            spc, sfl, _ = state.fill_inputs()
+            fill = timed(lambda: ops.knn_interpolate(spc, sfl, q, k=a.k, out=base, coverage=c), a.reps)
+            fill_all = timed(lambda: ops.knn_interpolate(spc, sfl, q, k=a.k), a.reps)
+            qu = q[:, c != 1].contiguous()
+            fill_sel = timed(lambda: ops.knn_interpolate(spc, sfl, qu, k=a.k), a.reps)
+            df.query(state, q, fill='knn', k=a.k)
+            qft = timed(lambda: df.query(state, q, fill='knn', k=a.k), a.reps)
             rows.append(dict(M=M, sampled=a.points, H0=int(state.Z.shape[0]), Z_cols=C, forward_model_ms=fwd_model,
                              forward_dense_ms=fwd_dense, lookup_ms=lookup, slice_ms=sl, query_ms=qt,
-                             head_ms=qt - lookup - sl, coverage=float(c.double().mean()), full=float((c == 1).double().mean())))
+                             head_ms=qt - lookup - sl, k=a.k, fill_ms=fill, fill_all_queries_ms=fill_all,
+                             fill_uncovered_only_ms=fill_sel, query_fill_ms=qft, coverage=float(c.double().mean()), full=float((c == 1).double().mean())))
             print(json.dumps(rows[-1]), flush=True)
-    if a.lookup_only:
+    if a.lookup_only or a.fill_only:
         print(json.dumps(rows))
 
 
