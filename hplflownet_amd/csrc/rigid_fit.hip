@@ -1,0 +1,411 @@
+// rigid_fit.hip -- the rigid motion (R, t) that explains most of a pair's flow, robustly, and the flow refined by it
+// (hpl_rigid_fit): ego-motion from a scene-flow field without a host round trip.
+//
+// Per round two launches.  k_rigid_reduce: workgroups of 256 lanes, each inside ONE pair (the host gives the pairs' first
+// workgroups in the kernel arguments beside the point prefix) and over a span of 1024 consecutive points of it, lane l taking
+// points l, l + 256, l + 512, l + 768 of the span (coalesced dword loads: a pair may start at any index of any row stride, so
+// no wider load is aligned in general).  A point's weight of the round comes from the previous round's (R, t), read from the
+// workspace: reweight and reduce are one pass.  16 float64 sums per workgroup -- W, sum u dp, sum u dq, sum u dp dq^T about the
+// pair's first point -- go through a fixed LDS tree into the workspace.  k_rigid_solve: one workgroup per pair adds the
+// partials in a fixed order (16 strided runs in index order, then the runs in order) and lane 0 solves: Horn's unit quaternion,
+// the dominant eigenvector of the symmetric 4x4 matrix of H by cyclic Jacobi sweeps in float64.  A quaternion is a proper
+// rotation whatever the cloud: there is no determinant to fix.  k_rigid_apply writes residual, refined and the inlier share
+// (integer counts: their order does not matter).  2 (iters + 1) + 1 launches, no copy, no read-back, no floating-point atomic:
+// the bits depend on the pair alone, not on its place in a batch or on what else the device runs.
+//
+// The arithmetic is part of the interface (include/hpl_bcl.h; tests/rigid_oracle.py restates it in numpy with an SVD).
+#include "common.h"
+
+#include <math.h>
+
+using namespace hpl;
+
+namespace {
+
+constexpr int RF_MAX_BATCH = 64;
+constexpr int RF_MAX_ITERS = 16;
+constexpr int RF_BLOCK = 256;
+constexpr int RF_PER_LANE = 4;
+constexpr int RF_SPAN = RF_BLOCK * RF_PER_LANE;      // points per workgroup
+constexpr int RF_SUMS = 16;                          // W, Sp[3], Sq[3], Spq[9]
+constexpr int RF_STATE = 16;                         // doubles per pair: R[9], t[3], status, angle (deg), |t|, {inliers, done}
+constexpr int RF_RUNS = RF_BLOCK / RF_SUMS;          // strided runs of the solve kernel's sum
+constexpr int RF_SWEEPS = 12;
+
+struct RigidArgs {
+    const float *pc;
+    int64_t pc_ld;
+    const float *flow;
+    int64_t fsc, fsp;
+    const float *weight;
+    double *state;              // [batch][RF_STATE]
+    double *partials;           // [workgroups][RF_SUMS]
+    float *Rt, *stats, *residual, *refined;
+    double tau;
+    int32_t batch, round, last;
+    int32_t pprefix[RF_MAX_BATCH + 1];      // points of pairs 0 .. b-1 (N < 2^31 / 3)
+    int32_t bprefix[RF_MAX_BATCH + 1];      // workgroups of pairs 0 .. b-1
+};
+
+__device__ __forceinline__ int pair_of(const RigidArgs &a, int blk) {
+    int b = 0;                   // the last pair whose first workgroup is <= blk (empty pairs own no workgroup)
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) b = (b + s < a.batch && a.bprefix[b + s] <= blk) ? b + s : b;
+    return b;
+}
+
+struct Point {
+    double p[3], q[3];
+    float f[3];
+    float w;                     // the effective base weight: 0 for a weight that is not in (0, inf) and for a non-finite point
+};
+
+__device__ __forceinline__ Point load_point(const RigidArgs &a, int64_t i) {
+    Point pt;
+    const float x = a.pc[i], y = a.pc[a.pc_ld + i], z = a.pc[2 * a.pc_ld + i];
+    const float *f = a.flow + i * a.fsp;
+    pt.f[0] = f[0];
+    pt.f[1] = f[a.fsc];
+    pt.f[2] = f[2 * a.fsc];
+    const float w = a.weight ? a.weight[i] : 1.f;
+    const bool ok = isfinite(x) && isfinite(y) && isfinite(z) && isfinite(pt.f[0]) && isfinite(pt.f[1]) && isfinite(pt.f[2]);
+    pt.w = (ok && w > 0.f && w < INFINITY) ? w : 0.f;
+    pt.p[0] = (double)x; pt.p[1] = (double)y; pt.p[2] = (double)z;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) pt.q[k] = pt.p[k] + (double)pt.f[k];
+    return pt;
+}
+
+// |R p + t - q|^2 and, in m, R p + t - p
+__device__ __forceinline__ double residual2(const double *R, const Point &pt, double *m) {
+    double r2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double y = ((R[3 * k] * pt.p[0] + R[3 * k + 1] * pt.p[1]) + R[3 * k + 2] * pt.p[2]) + R[9 + k];
+        const double d = y - pt.q[k];
+        m[k] = y - pt.p[k];
+        r2 = r2 + d * d;
+    }
+    return r2;
+}
+
+__global__ void __launch_bounds__(RF_BLOCK) k_rigid_reduce(const RigidArgs a) {
+    __shared__ double red[RF_SUMS][RF_BLOCK];
+    const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int b = pair_of(a, blk);
+    const int p0 = a.pprefix[b], p1 = a.pprefix[b + 1];
+    const int64_t base = (int64_t)p0 + (int64_t)(blk - a.bprefix[b]) * RF_SPAN;
+    double piv[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float v = a.pc[k * a.pc_ld + p0];
+        piv[k] = isfinite(v) ? (double)v : 0.0;
+    }
+    double R[12];
+    if (a.round > 0) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) R[k] = a.state[(int64_t)b * RF_STATE + k];
+    }
+    const double itau2 = 1.0 / (a.tau * a.tau);
+    double acc[RF_SUMS];
+#pragma unroll
+    for (int k = 0; k < RF_SUMS; ++k) acc[k] = 0.0;
+#pragma unroll
+    for (int j = 0; j < RF_PER_LANE; ++j) {
+        const int64_t i = base + j * RF_BLOCK + t;
+        if (i >= p1) continue;
+        const Point pt = load_point(a, i);
+        if (!(pt.w > 0.f)) continue;
+        double u = (double)pt.w;
+        if (a.round > 0) {
+            double m[3];
+            const double s = 1.0 + residual2(R, pt, m) * itau2;
+            u = u / (s * s);                     // Geman-McClure
+        }
+        double dp[3], dq[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { dp[k] = pt.p[k] - piv[k]; dq[k] = pt.q[k] - piv[k]; }
+        acc[0] += u;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double up = u * dp[k];
+            acc[1 + k] += up;
+            acc[4 + k] += u * dq[k];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) acc[7 + 3 * k + c] += up * dq[c];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < RF_SUMS; ++k) red[k][t] = acc[k];
+    __syncthreads();
+    for (int w = RF_BLOCK / 2; w > 0; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int k = 0; k < RF_SUMS; ++k) red[k][t] += red[k][t + w];
+        }
+        __syncthreads();
+    }
+    if (t < RF_SUMS) a.partials[(int64_t)blk * RF_SUMS + t] = red[t][0];
+}
+
+// One rotation of the cyclic Jacobi sweep of the symmetric 4x4 A (eigenvectors accumulate in the columns of V).
+template <int P, int Q>
+__device__ __forceinline__ void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
+    const double apq = A[P][Q];
+    if (apq == 0.0) return;
+    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
+    const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));     // (theta = +-inf: 0)
+    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                // A <- A J
+        const double akp = A[k][P], akq = A[k][Q];
+        A[k][P] = c * akp - s * akq;
+        A[k][Q] = s * akp + c * akq;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {                // A <- J^T A
+        const double apk = A[P][k], aqk = A[Q][k];
+        A[P][k] = c * apk - s * aqk;
+        A[Q][k] = s * apk + c * aqk;
+    }
+    A[P][Q] = 0.0;
+    A[Q][P] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const double vkp = V[k][P], vkq = V[k][Q];
+        V[k][P] = c * vkp - s * vkq;
+        V[k][Q] = s * vkp + c * vkq;
+    }
+}
+
+// The unit quaternion (w, x, y, z) of the proper rotation that maximises tr(R H), H = sum u (p - mp)(q - mq)^T (Horn 1987).
+__device__ void horn_quaternion(const double *H, double *quat) {
+    const double Sxx = H[0], Sxy = H[1], Sxz = H[2], Syx = H[3], Syy = H[4], Syz = H[5], Szx = H[6], Szy = H[7], Szz = H[8];
+    double A[4][4] = {{(Sxx + Syy) + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
+                      {Syz - Szy, (Sxx - Syy) - Szz, Sxy + Syx, Szx + Sxz},
+                      {Szx - Sxz, Sxy + Syx, (Syy - Sxx) - Szz, Syz + Szy},
+                      {Sxy - Syx, Szx + Sxz, Syz + Szy, (Szz - Sxx) - Syy}};
+    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    for (int sweep = 0; sweep < RF_SWEEPS; ++sweep) {
+        double off = 0.0, all = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                all += A[i][j] * A[i][j];
+                if (i != j) off += A[i][j] * A[i][j];
+            }
+        if (!(off > 1e-32 * all)) break;         // (also a zero or non-finite matrix)
+        jacobi_rotate<0, 1>(A, V);
+        jacobi_rotate<0, 2>(A, V);
+        jacobi_rotate<0, 3>(A, V);
+        jacobi_rotate<1, 2>(A, V);
+        jacobi_rotate<1, 3>(A, V);
+        jacobi_rotate<2, 3>(A, V);
+    }
+    int best = 0;                                // the largest eigenvalue; ties go to the smaller index
+#pragma unroll
+    for (int i = 1; i < 4; ++i) best = A[i][i] > A[best][best] ? i : best;
+    double n2 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        quat[k] = best == 0 ? V[k][0] : best == 1 ? V[k][1] : best == 2 ? V[k][2] : V[k][3];
+        n2 += quat[k] * quat[k];
+    }
+    const double inv = (quat[0] < 0.0 ? -1.0 : 1.0) / sqrt(n2);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) quat[k] *= inv;
+}
+
+__global__ void __launch_bounds__(RF_BLOCK) k_rigid_solve(const RigidArgs a) {
+    __shared__ double run[RF_RUNS][RF_SUMS];
+    __shared__ double tot[RF_SUMS];
+    const int b = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int g = t / RF_SUMS, k = t % RF_SUMS;
+    const int b0 = a.bprefix[b], nb = a.bprefix[b + 1] - b0;
+    double s = 0.0;
+#pragma unroll 4
+    for (int j = g; j < nb; j += RF_RUNS) s += a.partials[(int64_t)(b0 + j) * RF_SUMS + k];
+    run[g][k] = s;
+    __syncthreads();
+    if (t < RF_SUMS) {
+        double v = 0.0;
+#pragma unroll
+        for (int r = 0; r < RF_RUNS; ++r) v += run[r][t];
+        tot[t] = v;
+    }
+    __syncthreads();
+    if (t != 0) return;
+
+    double *st = a.state + (int64_t)b * RF_STATE;
+    const int p0 = a.pprefix[b], n = a.pprefix[b + 1] - p0;
+    bool ok = n >= 3 && (a.round == 0 || st[12] != 0.0);     // a pair that failed at an earlier round stays failed
+    const double W = tot[0];
+#pragma unroll
+    for (int i = 0; i < RF_SUMS; ++i) ok = ok && isfinite(tot[i]);
+    ok = ok && W > 0.0;
+    double R[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+    double angle = 0.0, tn = 0.0;
+    if (ok) {
+        double mp[3], mq[3], H[9];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { mp[i] = tot[1 + i] / W; mq[i] = tot[4 + i] / W; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) H[3 * i + j] = tot[7 + 3 * i + j] - W * mp[i] * mq[j];
+        double q[4];
+        horn_quaternion(H, q);
+        const double w = q[0], x = q[1], y = q[2], z = q[3];
+        R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
+        R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+        R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+        double piv[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const float v = a.pc[i * a.pc_ld + p0];
+            piv[i] = isfinite(v) ? (double)v : 0.0;
+        }
+        // t = mq - R mp with mp = piv + mp', mq = piv + mq'
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const double rp = (R[3 * i] * (piv[0] + mp[0]) + R[3 * i + 1] * (piv[1] + mp[1])) + R[3 * i + 2] * (piv[2] + mp[2]);
+            R[9 + i] = (piv[i] + mq[i]) - rp;
+        }
+        angle = 2.0 * atan2(sqrt((x * x + y * y) + z * z), fabs(w)) * (180.0 / 3.14159265358979323846);
+        tn = sqrt((R[9] * R[9] + R[10] * R[10]) + R[11] * R[11]);
+#pragma unroll
+        for (int i = 0; i < 12; ++i) ok = ok && isfinite(R[i]);
+        if (!ok) {
+            const double I[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+#pragma unroll
+            for (int i = 0; i < 12; ++i) R[i] = I[i];
+            angle = tn = 0.0;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 12; ++i) st[i] = R[i];
+    st[12] = ok ? 1.0 : 0.0;
+    st[13] = angle;
+    st[14] = tn;
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(st + 15);       // the apply kernel's inlier count and finished workgroups
+    cnt[0] = 0u;
+    cnt[1] = 0u;
+    if (a.last) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) a.Rt[(int64_t)b * 12 + i] = (float)R[i];
+        float *o = a.stats + (int64_t)b * 4;
+        o[0] = ok ? 1.f : 0.f;
+        o[1] = 0.f;              // (k_rigid_apply's last workgroup of the pair writes the share of a fitted pair)
+        o[2] = (float)angle;
+        o[3] = (float)tn;
+    }
+}
+
+__global__ void __launch_bounds__(RF_BLOCK) k_rigid_apply(const RigidArgs a) {
+    const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
+    const int b = pair_of(a, blk);
+    const int p0 = a.pprefix[b], p1 = a.pprefix[b + 1];
+    const int64_t base = (int64_t)p0 + (int64_t)(blk - a.bprefix[b]) * RF_SPAN;
+    double *st = a.state + (int64_t)b * RF_STATE;
+    double R[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) R[k] = st[k];
+    const bool fitted = st[12] != 0.0;
+    int inl = 0;
+#pragma unroll
+    for (int j = 0; j < RF_PER_LANE; ++j) {
+        const int64_t i = base + j * RF_BLOCK + t;
+        bool inlier = false;
+        if (i < p1) {
+            const Point pt = load_point(a, i);
+            double m[3];
+            // (a pair without a fit has R = I, t = 0: its residual is |f|)
+            const double r = sqrt(residual2(R, pt, m));
+            inlier = fitted && pt.w > 0.f && r <= a.tau;
+            if (a.residual) a.residual[i] = (float)r;
+            if (a.refined) {
+                float *o = a.refined + i * 3;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) o[k] = inlier ? (float)m[k] : pt.f[k];
+            }
+        }
+        inl += __syncthreads_count(inlier ? 1 : 0);
+    }
+    if (t == 0 && fitted) {
+        uint32_t *cnt = reinterpret_cast<uint32_t *>(st + 15);
+        atomicAdd(&cnt[0], (uint32_t)inl);
+        __threadfence();
+        const uint32_t nb = (uint32_t)(a.bprefix[b + 1] - a.bprefix[b]);
+        if (atomicAdd(&cnt[1], 1u) == nb - 1u) {             // the pair's last workgroup: every count is in
+            __threadfence();
+            const uint32_t total = atomicAdd(&cnt[0], 0u);
+            a.stats[(int64_t)b * 4 + 1] = (float)((double)total / (double)(p1 - p0));
+        }
+    }
+}
+
+int64_t workspace_bytes(int batch, int64_t n_total) {
+    return (int64_t)sizeof(double) * ((int64_t)batch * RF_STATE + (cdiv(n_total, RF_SPAN) + batch) * RF_SUMS);
+}
+
+constexpr int64_t RF_MAX_POINTS = (((int64_t)1 << 31) + 2) / 3;     // N >= 2^31 / 3 is refused: 3 N elements pass 32 bits
+
+}  // namespace
+
+extern "C" int64_t hpl_rigid_fit_workspace_bytes(int batch, int64_t n_total) {
+    if (batch < 1 || batch > RF_MAX_BATCH || n_total < 0 || n_total >= RF_MAX_POINTS) return -1;
+    return workspace_bytes(batch, n_total);
+}
+
+extern "C" int hpl_rigid_fit(const float *pc, int64_t pc_ld, const float *flow, int64_t flow_sc, int64_t flow_sp,
+                             const float *weight, int batch, const int64_t *prefix, int iters, float tau, float *Rt, float *stats,
+                             float *residual, float *refined, void *workspace, int64_t workspace_bytes_, hplStream stream) {
+    HPL_REQUIRE(pc && flow && Rt && stats && prefix && workspace, "hpl_rigid_fit: null pointer");
+    HPL_REQUIRE(batch >= 1 && batch <= RF_MAX_BATCH, "hpl_rigid_fit: batch %d (1 .. %d)", batch, RF_MAX_BATCH);
+    HPL_REQUIRE(iters >= 0 && iters <= RF_MAX_ITERS, "hpl_rigid_fit: iters = %d (0 .. %d)", iters, RF_MAX_ITERS);
+    HPL_REQUIRE(tau > 0.f && isfinite(tau), "hpl_rigid_fit: tau must be finite and > 0");
+    HPL_REQUIRE(prefix[0] == 0, "hpl_rigid_fit: the prefix must start at 0");
+    for (int b = 0; b < batch; ++b)
+        HPL_REQUIRE(prefix[b + 1] >= prefix[b], "hpl_rigid_fit: the prefix decreases at pair %d", b);
+    const int64_t N = prefix[batch];
+    HPL_REQUIRE(N < RF_MAX_POINTS, "hpl_rigid_fit: %lld points pass the 32-bit element limit (N < 2^31 / 3)", (long long)N);
+    HPL_REQUIRE(pc_ld >= N, "hpl_rigid_fit: row stride %lld below %lld points", (long long)pc_ld, (long long)N);
+    HPL_REQUIRE(flow_sc >= 1 && flow_sp >= 1 && (flow_sp != 1 || flow_sc >= N) && (flow_sc != 1 || flow_sp >= 3 || N <= 1),
+                "hpl_rigid_fit: flow strides %lld (component) / %lld (point) overlap for %lld points", (long long)flow_sc,
+                (long long)flow_sp, (long long)N);
+    HPL_REQUIRE(workspace_bytes_ >= workspace_bytes(batch, N), "hpl_rigid_fit: workspace of %lld bytes, needs %lld",
+                (long long)workspace_bytes_, (long long)workspace_bytes(batch, N));
+    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(flow) | reinterpret_cast<uintptr_t>(weight) |
+                  reinterpret_cast<uintptr_t>(Rt) | reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(residual) |
+                  reinterpret_cast<uintptr_t>(refined)) & 3u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
+                "hpl_rigid_fit: arrays must be 4-byte aligned, the workspace 8-byte");
+    if (N == 0) return HPL_OK;
+    RigidArgs a{};
+    int64_t blocks = 0;
+    for (int b = 0; b < batch; ++b) {
+        a.pprefix[b] = (int32_t)prefix[b];
+        a.bprefix[b] = (int32_t)blocks;
+        blocks += cdiv(prefix[b + 1] - prefix[b], RF_SPAN);
+    }
+    a.pprefix[batch] = (int32_t)N;
+    a.bprefix[batch] = (int32_t)blocks;
+    a.pc = pc; a.pc_ld = pc_ld; a.flow = flow; a.fsc = flow_sc; a.fsp = flow_sp; a.weight = weight;
+    a.state = static_cast<double *>(workspace);
+    a.partials = a.state + (int64_t)batch * RF_STATE;
+    a.Rt = Rt; a.stats = stats; a.residual = residual; a.refined = refined;
+    a.tau = (double)tau;
+    a.batch = batch;
+    hipStream_t s = to_stream(stream);
+    for (int k = 0; k <= iters; ++k) {
+        a.round = k;
+        a.last = k == iters;
+        k_rigid_reduce<<<(unsigned)blocks, RF_BLOCK, 0, s>>>(a);
+        HPL_CHECK_LAUNCH("hpl_rigid_fit (reduce)");
+        k_rigid_solve<<<batch, RF_BLOCK, 0, s>>>(a);
+        HPL_CHECK_LAUNCH("hpl_rigid_fit (solve)");
+    }
+    k_rigid_apply<<<(unsigned)blocks, RF_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_rigid_fit (apply)");
+    return HPL_OK;
+}

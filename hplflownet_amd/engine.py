@@ -288,7 +288,7 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3):
+    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -304,13 +304,25 @@ class Trainer(object):
         (DenseFlow.query); those flows go through the same metrics into a second array, and the keys gain dense_<metric> plus
         dense_coverage (the mean query coverage) and dense_full (the fraction of queries whose vertices were all found), all
         means over pairs.  dense_fill='knn' (with dense_k neighbours): the part of a query the lattice does not
-        cover is filled from the sampled flow (DenseFlow.query(fill='knn')); the same keys, then of the filled flow."""
+        cover is filled from the sampled flow (DenseFlow.query(fill='knn')); the same keys, then of the filled flow.
+
+        rigid={'iters': T, 'tau': tau}: behind each forward's metrics launch one ops.rigid_fit over that forward's
+        pairs -- the robust rigid fit of (pc1, sampled flow) per pair; the flow is read in place, the clouds of a forward of
+        B > 1 pairs are packed with one copy first -- and one more metrics launch of the refined flow into a third array; the
+        forwards' fit statistics stay on the device and come back, joined by one concatenation, with the read-back.  The keys gain
+        rigid_<metric> plus rigid_inliers (the inlier share), rigid_angle_deg and rigid_trans (the fitted rotation angle and
+        |t|), means over pairs.  With dense=True the refinement is still of the sampled flow."""
         if dense_fill is not None and not dense:
             raise HplError('validate: dense_fill applies to dense=True')
+        if rigid is not None:
+            if not isinstance(rigid, dict) or set(rigid) - {'iters', 'tau'}:
+                raise HplError('validate: rigid takes {\'iters\': T, \'tau\': tau}, got %r' % (rigid,))
+            rigid = {'iters': int(rigid.get('iters', 4)), 'tau': float(rigid.get('tau', 0.1))}
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
         dkeys = ['dense_' + k for k in keys] + ['dense_coverage', 'dense_full'] if dense else []
+        rkeys = ['rigid_' + k for k in keys] + list(RIGID_STATS) if rigid is not None else []
         self.val_batches = 0
         self.val_pairs = []
         self._dense = None
@@ -325,6 +337,10 @@ class Trainer(object):
                 from .flownet import DenseFlow
                 self._dense = DenseFlow(self.model)
                 self._dense_fill = (dense_fill, dense_k)
+            if rigid is not None:
+                rsums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
+                rstage = ops.MetricsStage(n, self.device)
+                rstats = []                              # every forward's (B, 4) fit statistics, on the device
             nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
 
             def cameras_of(samples):
@@ -336,9 +352,17 @@ class Trainer(object):
                     cameras.append(cam)
                 return cameras
 
-            def add(preds, samples):
+            def add(preds, samples, batched=None):
                 ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras_of(samples), sums,
                                        nxt[0], stage)
+                if rigid is not None:
+                    from .flownet import rigid_refine
+                    # an equal batch goes as the forward's own (B, 3, N) tensors: its flow rows are read in place
+                    pc1, flow = batched if batched is not None else ([s_[0] for s_ in samples], list(preds))
+                    _, _, st, refined = rigid_refine(pc1, flow, **rigid)
+                    rstats.append(st)            # (sample order: the groups are runs of consecutive samples)
+                    ops.flow_metrics_pairs(list(refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
+                                           cameras_of(samples), rsums, nxt[0], rstage)
                 nxt[0] += len(samples)
 
             def add_dense(qflows, covs, samples):
@@ -354,6 +378,8 @@ class Trainer(object):
                 words = sums.cpu().numpy()               # the one read-back (it follows every launch on this stream)
                 if dense:
                     dwords, dcv = dsums.cpu().numpy(), dcov.cpu().numpy()
+                if rigid is not None:
+                    rwords, rst = rsums.cpu().numpy(), torch.cat(rstats).cpu().numpy()
             finally:
                 torch.cuda.current_stream(self.device).synchronize()     # the stage's copies have run before it is released
                 self._dense = self._dense_add = None
@@ -362,7 +388,11 @@ class Trainer(object):
                 for i, v in self.val_pairs:
                     v.update({'dense_' + k: x for k, x in ops.flow_metrics_fold(dwords[i], cams).items()})
                     v['dense_coverage'], v['dense_full'] = float(dcv[i, 0]), float(dcv[i, 1])
-        keys = keys + dkeys
+            if rigid is not None:
+                for i, v in self.val_pairs:
+                    v.update({'rigid_' + k: x for k, x in ops.flow_metrics_fold(rwords[i], cams).items()})
+                    v.update(zip(RIGID_STATS, (float(x) for x in rst[i, 1:])))
+        keys = keys + dkeys + rkeys
         agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
         # added over the ranks, so all ranks return the metrics of the WHOLE split (and agree on `best` in fit())
@@ -371,7 +401,8 @@ class Trainer(object):
         return {k: v / max(1.0, tot[-1]) for k, v in zip(keys, tot[:-1])}
 
     def _validate_forwards(self, data, batch_size, ragged, add):
-        """The forwards of validate(): add(preds, samples) after each, preds[b] the (3, N_b) flow view of samples[b]."""
+        """The forwards of validate(): add(preds, samples) after each, preds[b] the (3, N_b) flow view of samples[b]; an equal
+        batch adds its own (pc1, flow) tensors, both (B, 3, N), as a third argument."""
         if batch_size > 1 and ragged:
             for group in self._ragged_batches(data, batch_size):
                 p1, p2 = [g[0] for g in group], [g[1] for g in group]
@@ -385,7 +416,7 @@ class Trainer(object):
                 lat = self.gen.build_native_batch(p1, p2) if len(group) > 1 else self.gen.build_native(p1[0], p2[0])
                 flow = self._forward(p1, p2, lat, group)
                 self.val_batches += 1
-                add(list(flow), group)
+                add(list(flow), group, (p1, flow))
         else:
             for s_, lat in self._lattices(data, list(range(len(data))), False):
                 flow = self._forward(s_[0][None], s_[1][None], lat, [s_])
@@ -487,6 +518,10 @@ class Trainer(object):
         return self.min_loss
 
 
+#: validate(rigid=...): the per-pair fit statistics beside the rigid_<metric> keys (stats[1:] of ops.rigid_fit)
+RIGID_STATS = ('rigid_inliers', 'rigid_angle_deg', 'rigid_trans')
+
+
 def metric_keys(data):
     """The keys validate() reports for a reader: the four 3D metrics, and EPE2D / Acc2D when it has cameras (`has_cameras`).  Decided
     from the reader alone, never from its samples: a rank with an empty shard reports (and reduces) the same keys."""
@@ -583,6 +618,15 @@ def parse_args(argv=None):
                     help='with --dense: fill the part of each query that the sampled lattice does not cover by inverse-distance '
                          'interpolation of the sampled flow from the --dense-k nearest sampled points (DESIGN.md §17)')
     ap.add_argument('--dense-k', type=int, default=None, metavar='K', help='neighbours of --dense-fill knn (1 .. 8, default 3)')
+    ap.add_argument('--rigid-refine', action='store_true',
+                    help='with --evaluate: behind each forward fit the rigid motion that explains most of its sampled flow (per '
+                         'pair, on the device) and also report the metrics of the flow whose inliers are replaced by the rigid '
+                         'flow, as rigid_<metric>, with rigid_inliers / rigid_angle_deg / rigid_trans (DESIGN.md §18; with --dense '
+                         'the sampled flow only)')
+    ap.add_argument('--rigid-iters', type=int, default=None, metavar='T',
+                    help='reweighted solves of --rigid-refine after the least-squares one (0 .. 16, default 4)')
+    ap.add_argument('--rigid-tau', type=float, default=None, metavar='TAU',
+                    help='--rigid-refine: inlier threshold and scale of the Geman-McClure weights in metres (> 0, default 0.1)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -602,6 +646,14 @@ def parse_args(argv=None):
     if a.dense_k is not None and (a.dense_fill is None or not 1 <= a.dense_k <= 8):
         ap.error('--dense-k takes 1 .. 8 and applies to --dense-fill knn')
     a.dense_k = a.dense_k or 3
+    if a.rigid_refine and not a.evaluate:
+        ap.error('--rigid-refine applies to --evaluate')
+    if a.rigid_iters is not None and (not a.rigid_refine or not 0 <= a.rigid_iters <= 16):
+        ap.error('--rigid-iters takes 0 .. 16 and applies to --rigid-refine')
+    if a.rigid_tau is not None and (not a.rigid_refine or not 0 < a.rigid_tau < float('inf')):
+        ap.error('--rigid-tau takes a finite value > 0 and applies to --rigid-refine')
+    a.rigid = {'iters': 4 if a.rigid_iters is None else a.rigid_iters,
+               'tau': 0.1 if a.rigid_tau is None else a.rigid_tau} if a.rigid_refine else None
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -621,7 +673,8 @@ def main(argv=None):
     if a.dataset != 'synthetic':
         return _real_data(a, tr, dev, rank, world)
     if a.evaluate:
-        res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size, a.ragged)
+        res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size, a.ragged,
+                          rigid=a.rigid)
         if rank == 0:
             print(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
@@ -741,7 +794,7 @@ def _real_data(a, tr, dev, rank, world):
         val = DenseFrames(val, full)
     val = _Shard(val, rank, world, cap)
     if train is None:
-        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k)
+        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -22,7 +22,7 @@ from . import _lib, ops
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, NbrTable, _ConvReLU, _conv_of, pointwise_conv,
                   to_channel_first, to_channel_last)
 
-__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow']
+__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine']
 
 
 # ----------------------------------------------------------------------------- lattice container
@@ -524,6 +524,85 @@ def load_reference_checkpoint(model, checkpoint, strict=True):
     sd = obj.get('state_dict', obj) if isinstance(obj, dict) else obj
     sd = {(k[len('module.'):] if k.startswith('module.') else k): v for k, v in sd.items()}
     return model.load_state_dict(sd, strict=strict)
+
+
+# ----------------------------------------------------------------------------- rigid refinement
+def _pair_counts(lat_or_counts, total):
+    """Points per pair of a packed cloud of `total` points: from a lattice (a ragged one: its point_counts of cloud 1; an
+    equal batch: total / batch) or a sequence of counts."""
+    if lat_or_counts is None:
+        return [total]
+    if getattr(lat_or_counts, 'ragged', False):
+        counts = [int(c[0]) for c in lat_or_counts.point_counts]
+    elif hasattr(lat_or_counts, 'levels') or hasattr(lat_or_counts, 'batch'):
+        b = int(getattr(lat_or_counts, 'batch', 1) or 1)
+        counts = [total // b] * b
+    else:
+        counts = [int(c) for c in lat_or_counts]
+    if sum(counts) != total or any(c < 0 for c in counts):
+        raise _lib.HplError('rigid_refine: the point counts %s do not add up to %d points' % (counts, total))
+    return counts
+
+
+def _packed_rows(fls):
+    """The [sum N_b, 3] tensor whose consecutive row blocks the (3, N_b) views `fls` are -- the flows of a ragged forward
+    (ragged_flows) --, or None where they are anything else."""
+    f0, off = fls[0], fls[0].storage_offset()
+    for f in fls:
+        if f.dtype != f0.dtype or f.device != f0.device or tuple(f.stride()) != (1, 3) or f.storage_offset() != off or \
+                f.untyped_storage().data_ptr() != f0.untyped_storage().data_ptr():
+            return None
+        off += 3 * int(f.shape[1])
+    return f0.as_strided(((off - f0.storage_offset()) // 3, 3), (3, 1), f0.storage_offset())
+
+
+def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
+    """The rigid refinement of a forward's flow in ONE ops.rigid_fit call: per pair the robust rigid fit of
+    (pc1, flow) and the flow with its inliers replaced by the rigid flow.  pc1 / flow as the models take and return them: a
+    (B, 3, N) tensor pair (or (3, N): one pair), or two lists of B (3, N_b) / (1, 3, N_b) tensors (a ragged batch); a packed
+    (3, sum N_b) cloud with its flow takes the pairs' counts from lat_or_counts (the forward's lattice, or a sequence of
+    counts).  kw: iters, tau, weight (packed, pair-major), return_residual (packed) of ops.rigid_fit.
+    The flow a forward returned is read in place (a (B, 3, N) view of its [B N, 3] rows; the row-block views of a ragged
+    forward); B > 1 clouds are packed into one (3, sum N_b) tensor first (one copy), any other list of flows likewise.
+    -> (R (B, 3, 3), t (B, 3), stats (B, 4), refined[, residual]), refined in the form of `flow`: views of one [sum N_b, 3]
+    tensor."""
+    if isinstance(pc1, (list, tuple)) or isinstance(flow, (list, tuple)):
+        if not isinstance(pc1, (list, tuple)) or not isinstance(flow, (list, tuple)) or len(pc1) != len(flow) or not pc1:
+            raise _lib.HplError('rigid_refine: pc1 and flow are both lists of as many clouds, or both tensors')
+        lead = [f.dim() == 3 for f in flow]
+        pcs = [p[0] if p.dim() == 3 else p for p in pc1]
+        fls = [f[0] if f.dim() == 3 else f for f in flow]
+        counts = [int(p.shape[1]) for p in pcs]
+        if lat_or_counts is not None and _pair_counts(lat_or_counts, sum(counts)) != counts:
+            raise _lib.HplError('rigid_refine: the clouds hold %s points, the lattice or counts say otherwise' % (counts,))
+        pc = pcs[0] if len(pcs) == 1 else torch.cat(pcs, dim=1)
+        fl = fls[0] if len(fls) == 1 else _packed_rows(fls)
+        if fl is None:
+            fl = torch.cat([f.t() for f in fls], dim=0)
+        shape = lambda r, b: r.t().unsqueeze(0) if lead[b] else r.t()       # noqa: E731
+    elif pc1.dim() == 3:
+        B, _, n = pc1.shape
+        if flow.dim() != 3 or flow.shape[0] != B:
+            raise _lib.HplError('rigid_refine: a (B, 3, N) cloud takes a (B, 3, N) flow')
+        counts = [int(n)] * B
+        pc = pc1[0] if B == 1 else pc1.transpose(0, 1).reshape(3, B * n)
+        fl = flow[0] if B == 1 else flow.transpose(1, 2).reshape(B * n, 3)       # (the forward's rows: a view)
+        shape = None
+    else:
+        counts = _pair_counts(lat_or_counts, int(pc1.shape[1]))
+        pc, fl, shape = pc1, flow, False
+    prefix = [0]
+    for c in counts:
+        prefix.append(prefix[-1] + c)
+    res = ops.rigid_fit(pc, fl, prefix=prefix, **kw)
+    ref = res[3]
+    if shape is None:
+        ref = ref.view(len(counts), counts[0], 3).transpose(1, 2)
+    elif shape is False:
+        ref = ref.t() if tuple(flow.shape) == (3, ref.shape[0]) else ref
+    else:
+        ref = [shape(ref[prefix[b]:prefix[b + 1]], b) for b in range(len(counts))]
+    return res[:3] + (ref,) + res[4:]
 
 
 # ----------------------------------------------------------------------------- dense flow

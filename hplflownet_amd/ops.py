@@ -366,13 +366,13 @@ def flow_metrics_fold(words, camera=True):
 
 
 # --------------------------------------------------------------------------- nearest neighbours
-def _soa3(x, what):
+def _soa3(x, what, op='knn_interpolate'):
     """A (3, n) float32 device cloud with unit stride along its points (rows may be views of a wider buffer)."""
     if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] != 3 or x.dtype != torch.float32 or not x.is_cuda:
-        raise _lib.HplError('knn_interpolate: %s must be a (3, n) float32 device tensor, got %s' % (
-            what, (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x)))
+        raise _lib.HplError('%s: %s must be a (3, n) float32 device tensor, got %s' % (
+            op, what, (tuple(x.shape), x.dtype, x.device) if torch.is_tensor(x) else type(x)))
     if x.requires_grad:
-        raise _lib.HplError('knn_interpolate has no autograd: %s requires grad' % what)
+        raise _lib.HplError('%s has no autograd: %s requires grad' % (op, what))
     n = x.shape[1]
     if x.stride(0) < max(n, 1) or (n > 1 and x.stride(1) != 1):
         x = x.contiguous()           # (after which a row starts max(n, 1) elements behind the previous one)
@@ -431,6 +431,86 @@ def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=Non
                                      (ctypes.c_int64 * (B + 1))(*rp), (ctypes.c_int64 * (B + 1))(*qp), ptr(idx), ptr(dist2),
                                      out.data_ptr(), ptr(coverage), stream()), 'hpl_knn_interp')
     return (out, idx, dist2) if return_neighbors else out
+
+
+# --------------------------------------------------------------------------- rigid motion from flow
+_RIGID_WS = {}
+
+
+def _rigid_workspace(device, st, nbytes):
+    """Per-(device, stream) scratch of hpl_rigid_fit, one buffer per size class (the next power of two): a call on another
+    stream never shares the partial sums of one in flight."""
+    size = 1 << max(12, int(nbytes - 1).bit_length())
+    key = (device, st, size)
+    ws = _RIGID_WS.get(key)
+    if ws is None:
+        ws = _RIGID_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
+    return ws
+
+
+def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_residual=False, out=None):
+    """hpl_rigid_fit on the current stream: the rigid motion q = R p + t that explains most of the flow of
+    each pair, fitted by iteratively reweighted least squares (Geman-McClure weights of scale tau, iters reweighted solves
+    after the plain one; float64 sums in a fixed order), and the flow refined by it.  pc (3, N) float32; flow (3, N) or
+    [N, 3] float32 of any strides (the models' flow views and DenseFlow.query's answers are read in place; a (3, 3) tensor is
+    (3, N)); weight (N,) float32 or None -- for a dense flow, its coverage --: a weight that is not > 0 (NaN included) and a
+    non-finite point count as 0.  prefix (host sequence of B + 1 ints from 0 to N): B <= 64 pairs, each with its own fit.
+    -> (R (B, 3, 3), t (B, 3), stats (B, 4) = (status, inlier share, rotation angle in degrees, |t|), refined [N, 3]
+    [, residual (N,)]): an inlier (residual <= tau, weight > 0) gets the rigid flow R p + t - p, any other point its input
+    flow bit for bit.  status 0 (fewer than 3 points, or no weight): R = I, t = 0, refined = flow.  out: a contiguous [N, 3]
+    float32 tensor that takes the refined flow (it must not overlap flow).  No autograd, no host synchronisation."""
+    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= 16:
+        raise _lib.HplError('rigid_fit: iters = %r (an int in 0 .. 16)' % (iters,))
+    tau = float(tau)
+    if not (tau > 0 and tau < float('inf')):
+        raise _lib.HplError('rigid_fit: tau = %r (finite and > 0)' % (tau,))
+    pc, pc_ld = _soa3(pc, 'pc', 'rigid_fit')
+    N, dev = pc.shape[1], pc.device
+    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
+            (tuple(flow.shape) != (3, N) and tuple(flow.shape) != (N, 3)):
+        raise _lib.HplError('rigid_fit: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
+            N, N, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
+    if flow.requires_grad:
+        raise _lib.HplError('rigid_fit has no autograd: flow requires grad')
+    if tuple(flow.shape) != (3, N):
+        flow = flow.t()
+    if N > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N) or
+                  (flow.stride(0) == 1 and flow.stride(1) < 3 and N > 1)):
+        flow = flow.contiguous()
+    if weight is not None:
+        if not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32 or weight.device != dev \
+                or weight.requires_grad:
+            raise _lib.HplError('rigid_fit: weight must be a (%d,) float32 tensor on %s without grad' % (N, dev))
+        weight = weight.contiguous()
+    pp = [0, N] if prefix is None else [int(x) for x in prefix]
+    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != N or any(b < a for a, b in zip(pp, pp[1:])):
+        raise _lib.HplError('rigid_fit: the prefix holds B + 1 <= 65 non-decreasing entries from 0 to N = %d, got %s' % (N, pp))
+    B = len(pp) - 1
+    if out is not None:
+        if not torch.is_tensor(out) or tuple(out.shape) != (N, 3) or out.dtype != torch.float32 or out.device != dev or \
+                not out.is_contiguous() or out.requires_grad:
+            raise _lib.HplError('rigid_fit: out must be a contiguous (%d, 3) float32 tensor on %s' % (N, dev))
+    else:
+        out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    residual = torch.empty(N, dtype=torch.float32, device=dev) if return_residual else None
+    lib = _lib.load()
+    if N == 0:                                   # nothing to launch: every pair is empty
+        Rt = torch.zeros((B, 12), dtype=torch.float32, device=dev)
+        Rt[:, 0:9:4] = 1.0
+        stats = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+    else:
+        Rt = torch.empty((B, 12), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        nbytes = lib.hpl_rigid_fit_workspace_bytes(B, N)
+        if nbytes < 0:
+            raise _lib.HplError('rigid_fit: %d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)' % (B, N))
+        st = stream()
+        ws = _rigid_workspace(dev, st, nbytes)
+        check(lib.hpl_rigid_fit(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), ptr(weight), B,
+                                (ctypes.c_int64 * (B + 1))(*pp), iters, tau, Rt.data_ptr(), stats.data_ptr(), ptr(residual),
+                                out.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_rigid_fit')
+    res = (Rt[:, :9].view(B, 3, 3), Rt[:, 9:], stats, out)
+    return res + (residual,) if return_residual else res
 
 
 # --------------------------------------------------------------------------- data transforms

@@ -905,6 +905,39 @@ int hpl_knn_interp(const float *ref, int64_t ref_ld, const float *val, int C, co
                    int batch, const int64_t *ref_prefix /* HOST */, const int64_t *q_prefix /* HOST */, int32_t *idx,
                    float *dist2, float *out, const float *coverage, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Rigid motion from flow (csrc/rigid_fit.hip): the rotation R and translation t that explain most of a pair's scene flow --
+ * ego-motion on a mostly static scene --, fitted robustly on the device, and the flow refined by it.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_rigid_fit for `batch` pairs of n_total points together, in bytes (monotone in both); -1 for a batch
+ * outside 1 .. 64 or n_total outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_rigid_fit_workspace_bytes(int batch, int64_t n_total);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N); component k of the flow of point i at flow[k * flow_sc + i * flow_sp]
+ * (elements, both >= 1 and not overlapping: (3, N) rows and the forward's point-major [N][3] rows are read in place);
+ * weight (N) float32 or NULL (all 1).  batch (1 .. 64) pairs: prefix (HOST, batch + 1 ints from 0 to N, non-decreasing) gives
+ * every pair's points; it travels in the kernel arguments: stream-ordered, no copy, no host synchronisation,
+ * 2 (iters + 1) + 1 launches.
+ * Arithmetic per pair (float64 throughout, from the float32 inputs; tests/rigid_oracle.py restates it in numpy with an SVD
+ * in place of the quaternion), q_i = p_i + f_i: the effective base weight w_i is the given weight, 0 when that is not in
+ * (0, inf) (NaN included) or when a coordinate or a flow component of the point is not finite.  Round 0 uses u_i = w_i; for
+ * round k = 0 .. iters (0 .. 16): SOLVE W = sum u_i, the u-weighted centroids mp, mq, H = sum u_i (p_i - mp)(q_i - mq)^T
+ * (accumulated about the pair's first point), R = the proper rotation maximising tr(R H) (Horn's unit quaternion: the dominant
+ * eigenvector of the symmetric 4x4 matrix of H, cyclic Jacobi; never a reflection), t = mq - R mp; then, if k < iters, REWEIGHT
+ * (Geman-McClure) r_i = |R p_i + t - q_i|, u_i = w_i / (1 + (r_i / tau)^2)^2, tau > 0 finite.
+ * Rt [batch][12] float32: R row-major, then t, of the last solve.  residual (N) or NULL: r_i against that solve.  A point is
+ * an inlier when r_i <= tau and w_i > 0.  refined [N][3] point-major or NULL: R p_i + t - p_i for an inlier, the input flow
+ * bit for bit for any other point.  stats [batch][4] float32: status, the inlier share of the pair's points, the rotation
+ * angle in degrees, |t|.  status = 1 for a fit; 0 for a pair of fewer than 3 points or whose W is not > 0 (or not finite) at
+ * any round: then R = I, t = 0, share 0, residual = |f_i|, refined = the input flow.  All sums in a fixed order, no
+ * floating-point atomic: a pair's outputs are the same bits alone, anywhere in a batch and beside other work.
+ * workspace: DEVICE, 8-byte aligned, >= hpl_rigid_fit_workspace_bytes(batch, N); refined must not overlap the inputs.
+ * HPL_EINVAL before any launch (and without a device): batch, iters or tau out of range; a prefix that does not start at 0
+ * or decreases; pc_ld < N; flow strides < 1 or overlapping; null pc / flow / Rt / stats / prefix / workspace; a workspace that
+ * is too small; misaligned arrays; N >= 2^31 / 3.  N == 0 is a no-op. */
+int hpl_rigid_fit(const float *pc, int64_t pc_ld, const float *flow, int64_t flow_sc, int64_t flow_sp, const float *weight,
+                  int batch, const int64_t *prefix /* HOST */, int iters, float tau, float *Rt, float *stats, float *residual,
+                  float *refined, void *workspace, int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
