@@ -1,0 +1,424 @@
+// motion_segment.hip -- moving objects from a flow field (hpl_motion_segment): the points a rigid fit leaves
+// unexplained (residual > tau), grouped into the connected components of a fixed-radius graph over position and flow, numbered,
+// and each object's size, centroid and mean flow -- without a host round trip.
+//
+// The definition is the all-pairs predicate of include/hpl_bcl.h; a uniform grid only finds the candidates.  The cell edge is
+// 1.001 eps and a point's cell floor(x / (1.001 eps)) is taken in float64, so two points within eps of each other (even by the
+// rounded float32 predicate, which can exceed the real one by a few 2^-24) lie in the same or in adjacent cells: 27 cells hold
+// every partner.
+//
+//   k_seg_keys     a lane per point: mover or not, the 64-bit key (pair, cell x, y, z), parent[i] = i, labels -1 / -3
+//   rocPRIM        stable radix sort of ALL points by key (non-movers carry the largest key and end up behind the movers): the
+//                  size of every launch is a host number, nothing is read back
+//   k_seg_link     a lane per sorted mover: 9 binary searches for the runs of 3 z-adjacent cells, the predicate against every
+//                  earlier-indexed point of them, and for a linked pair the union of the two trees: the larger root is hooked
+//                  under the smaller one by a compare-and-swap that succeeds only on a root.  A parent word only ever
+//                  decreases, a failed swap hands back a smaller index to go on from: no lane waits for another, every loop
+//                  is bounded by the tree depth or the cell population
+//   k_seg_flatten  a lane per point: its root (the smallest index of its component), one integer atomic on the root's size
+//   k_seg_flag     roots of at least min_points movers
+//   rocPRIM        exclusive scan of the flags in index order: the objects' numbers (a pair's base is subtracted)
+//   k_seg_label    labels, the key (object number) of the second sort, points in objects
+//   rocPRIM        stable radix sort by object number: an object's points in index order
+//   k_seg_objects  a workgroup per (pair, table row): float64 sums in a fixed order (lane l takes the object's points l, l + 256,
+//                  ..., then an LDS tree), rounded once
+//
+// Integer counts do not depend on their order, the float sums have one order, the root is the smallest index: every output of
+// a pair is the same bits alone, anywhere in a batch and beside other work.
+#include "common.h"
+
+#include <math.h>
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_scan.hpp>
+
+using namespace hpl;
+
+namespace {
+
+constexpr int MS_MAX_BATCH = 64;
+constexpr int MS_MAX_OBJECTS = 4096;
+constexpr int MS_BLOCK = 256;
+constexpr int64_t MS_MAX_POINTS = (((int64_t)1 << 31) + 2) / 3;     // N >= 2^31 / 3 is refused, as hpl_rigid_fit does
+constexpr int MS_CELL_BITS = 19;
+constexpr int MS_CELL_BIAS = 1 << (MS_CELL_BITS - 1);
+constexpr double MS_CELL_MAX = (double)(MS_CELL_BIAS - 2);           // |cell| <= 2^18 - 2: the neighbours' fields stay in 19 bits
+constexpr double MS_CELL_MARGIN = 1.001;
+
+typedef unsigned long long u64;
+
+struct SegArgs {
+    const float *pc;
+    int64_t pc_ld;
+    const float *flow;
+    int64_t fsc, fsp;
+    const float *residual;
+    float tau, eps2, dv2;
+    double inv_cell;
+    int32_t n, batch, min_points, max_objects;
+    u64 *key, *skey;
+    int32_t *val, *sval;            // point indices: 0 .. n-1, and in key order
+    int32_t *parent, *size;         // per point: parent (-1: no mover), and on a root the size of its component
+    int32_t *flag, *excl;           // n + 1 each: object roots, and how many of them lie before an index
+    uint32_t *okey, *sokey;         // the second sort: object number (n: none)
+    int32_t *soval;
+    int32_t *labels, *obj_info, *stats;
+    float *obj_motion;
+    int32_t pprefix[MS_MAX_BATCH + 1];
+};
+
+__device__ __forceinline__ int pair_of(const SegArgs &a, int i) {
+    int b = 0;                   // the last pair that starts at or before i (empty pairs start where the next one does)
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) b = (b + s < a.batch && a.pprefix[b + s] <= i) ? b + s : b;
+    return b;
+}
+
+__device__ __forceinline__ u64 make_key(int b, int cx, int cy, int cz) {
+    return ((u64)b << (3 * MS_CELL_BITS)) | ((u64)cx << (2 * MS_CELL_BITS)) | ((u64)cy << MS_CELL_BITS) | (u64)cz;
+}
+
+// adds v to stats[pair][slot] for every lane with v != 0; a workgroup inside one pair sends one atomic
+__device__ __forceinline__ void count_into(const SegArgs &a, bool uniform, int b, int slot, int v) {
+    if (uniform) {
+        const int total = __syncthreads_count(v);
+        if (threadIdx.x == 0 && total) atomicAdd(&a.stats[b * 4 + slot], total);
+    } else if (v) {
+        atomicAdd(&a.stats[b * 4 + slot], 1);
+    }
+}
+
+__global__ void __launch_bounds__(MS_BLOCK) k_seg_keys(const SegArgs a) {
+    const int64_t i0 = (int64_t)blockIdx.x * MS_BLOCK;
+    const int64_t i64 = i0 + threadIdx.x;
+    const bool in = i64 < a.n;
+    const int i = in ? (int)i64 : a.n - 1;
+    const int b = pair_of(a, i);
+    const bool uniform = pair_of(a, (int)i0) == pair_of(a, (int)imin(i0 + MS_BLOCK - 1, a.n - 1));
+    bool mover = false, oob = false;
+    u64 key = ~0ull;
+    if (in) {
+        const float x = a.pc[i], y = a.pc[a.pc_ld + i], z = a.pc[2 * a.pc_ld + i];
+        const float *f = a.flow + (int64_t)i * a.fsp;
+        const float fx = f[0], fy = f[a.fsc], fz = f[2 * a.fsc];
+        const float r = a.residual[i];
+        const bool ok = isfinite(x) && isfinite(y) && isfinite(z) && isfinite(fx) && isfinite(fy) && isfinite(fz);
+        if (ok && r > a.tau) {                   // (a NaN residual fails the comparison)
+            const double cx = floor((double)x * a.inv_cell), cy = floor((double)y * a.inv_cell), cz = floor((double)z * a.inv_cell);
+            mover = fabs(cx) <= MS_CELL_MAX && fabs(cy) <= MS_CELL_MAX && fabs(cz) <= MS_CELL_MAX;
+            oob = !mover;
+            if (mover) key = make_key(b, (int)cx + MS_CELL_BIAS, (int)cy + MS_CELL_BIAS, (int)cz + MS_CELL_BIAS);
+        }
+        a.key[i] = key;
+        a.val[i] = i;
+        a.parent[i] = mover ? i : -1;
+        a.size[i] = 0;
+        a.labels[i] = oob ? -3 : -1;
+    }
+    count_into(a, uniform, b, 0, mover ? 1 : 0);
+    count_into(a, uniform, b, 3, oob ? 1 : 0);
+}
+
+__device__ __forceinline__ int load_parent(const int32_t *parent, int x) {
+    return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The root of x's tree as far as this lane can see it: a stale look only ends higher up the same tree.  parent[x] < x off a root.
+__device__ __forceinline__ int find_root(const int32_t *parent, int x) {
+    int p = load_parent(parent, x);
+    while (p != x) {
+        x = p;
+        p = load_parent(parent, x);
+    }
+    return x;
+}
+
+__device__ __forceinline__ void unite(int32_t *parent, int u, int v) {
+    int ru = find_root(parent, u), rv = find_root(parent, v);
+    while (ru != rv) {
+        const int hi = ru > rv ? ru : rv, lo = ru > rv ? rv : ru;
+        const int old = atomicCAS(parent + hi, hi, lo);
+        if (old == hi) return;                   // hi was a root and now hangs under lo
+        // hi has been hooked by another lane meanwhile: old < hi is its parent.  max(ru, rv) falls with every turn.
+        ru = find_root(parent, old);
+        rv = lo;
+    }
+}
+
+__device__ __forceinline__ int lower_bound(const u64 *keys, int n, u64 k) {
+    int lo = 0, len = n;
+    while (len > 0) {
+        const int half = len >> 1;
+        const bool right = keys[lo + half] < k;
+        lo = right ? lo + half + 1 : lo;
+        len = right ? len - half - 1 : half;
+    }
+    return lo;
+}
+
+__global__ void __launch_bounds__(MS_BLOCK) k_seg_link(const SegArgs a) {
+    const int64_t s64 = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    if (s64 >= a.n) return;
+    const int s = (int)s64;
+    const u64 key = a.skey[s];
+    if (key == ~0ull) return;
+    const int i = a.sval[s];
+    const float x = a.pc[i], y = a.pc[a.pc_ld + i], z = a.pc[2 * a.pc_ld + i];
+    const float *f = a.flow + (int64_t)i * a.fsp;
+    const float fx = f[0], fy = f[a.fsc], fz = f[2 * a.fsc];
+    const u64 cell_mask = ((u64)1 << MS_CELL_BITS) - 1;
+    const int cx = (int)((key >> (2 * MS_CELL_BITS)) & cell_mask), cy = (int)((key >> MS_CELL_BITS) & cell_mask);
+    const int cz = (int)(key & cell_mask), b = (int)(key >> (3 * MS_CELL_BITS));
+    for (int dx = -1; dx <= 1; ++dx) {
+        for (int dy = -1; dy <= 1; ++dy) {
+            const u64 klo = make_key(b, cx + dx, cy + dy, cz - 1), khi = make_key(b, cx + dx, cy + dy, cz + 1);
+            // every link is made once, by its later-indexed end
+            for (int t = lower_bound(a.skey, a.n, klo); t < a.n && a.skey[t] <= khi; ++t) {
+                const int j = a.sval[t];
+                if (j >= i) continue;
+                const float ex = x - a.pc[j], ey = y - a.pc[a.pc_ld + j], ez = z - a.pc[2 * a.pc_ld + j];
+                const float d2 = (ex * ex + ey * ey) + ez * ez;
+                if (!(d2 <= a.eps2)) continue;
+                const float *g = a.flow + (int64_t)j * a.fsp;
+                const float gx = fx - g[0], gy = fy - g[a.fsc], gz = fz - g[2 * a.fsc];
+                const float g2 = (gx * gx + gy * gy) + gz * gz;
+                if (!(g2 <= a.dv2)) continue;
+                unite(a.parent, i, j);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(MS_BLOCK) k_seg_flatten(const SegArgs a) {
+    const int64_t i64 = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    if (i64 >= a.n) return;
+    const int i = (int)i64;
+    int r = a.parent[i];                         // (the link kernel is over: plain loads see the final forest)
+    if (r < 0) return;
+    int p = r;
+    while ((p = a.parent[r]) != r) r = p;
+    a.okey[i] = (uint32_t)r;                     // the root, until k_seg_label turns it into the object number
+    // lanes of one component share a root: one atomic for those that agree with the wave's first active lane
+    const int r0 = __builtin_amdgcn_readfirstlane(r);
+    const bool same = r == r0;
+    const u64 m = __ballot(same);
+    if (same) {
+        if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x & 63)) == (int)(threadIdx.x & 63)) atomicAdd(&a.size[r0], __popcll(m));
+    } else {
+        atomicAdd(&a.size[r], 1);
+    }
+}
+
+__global__ void __launch_bounds__(MS_BLOCK) k_seg_flag(const SegArgs a) {
+    const int64_t i64 = (int64_t)blockIdx.x * MS_BLOCK + threadIdx.x;
+    if (i64 > a.n) return;
+    const int i = (int)i64;
+    a.flag[i] = (i < a.n && a.parent[i] == i && a.size[i] >= a.min_points) ? 1 : 0;
+}
+
+__global__ void __launch_bounds__(MS_BLOCK) k_seg_label(const SegArgs a) {
+    const int64_t i0 = (int64_t)blockIdx.x * MS_BLOCK;
+    const int64_t i64 = i0 + threadIdx.x;
+    const bool in = i64 < a.n;
+    const int i = in ? (int)i64 : a.n - 1;
+    const int b = pair_of(a, i);
+    const bool uniform = pair_of(a, (int)i0) == pair_of(a, (int)imin(i0 + MS_BLOCK - 1, a.n - 1));
+    bool member = false;
+    if (in) {
+        uint32_t k = (uint32_t)a.n;
+        if (a.parent[i] >= 0) {
+            const int r = (int)a.okey[i];
+            member = a.flag[r] != 0;
+            if (member) k = (uint32_t)a.excl[r];
+            a.labels[i] = member ? a.excl[r] - a.excl[a.pprefix[b]] : -2;
+        }
+        a.okey[i] = k;
+    }
+    count_into(a, uniform, b, 2, member ? 1 : 0);
+}
+
+__global__ void __launch_bounds__(MS_BLOCK) k_seg_objects(const SegArgs a) {
+    __shared__ double red[6][MS_BLOCK];
+    const int b = (int)blockIdx.x / a.max_objects, o = (int)blockIdx.x % a.max_objects, t = (int)threadIdx.x;
+    const int p0 = a.pprefix[b];
+    const int base = a.excl[p0], count = a.excl[a.pprefix[b + 1]] - base;
+    if (o == 0 && t == 0) a.stats[b * 4 + 1] = count;
+    int32_t *info = a.obj_info + ((int64_t)b * a.max_objects + o) * 2;
+    float *motion = a.obj_motion + ((int64_t)b * a.max_objects + o) * 6;
+    // the object's run in the second sort: its points in index order, the root first
+    const uint32_t k = (uint32_t)(base + o);
+    int lo = 0, len = o < count ? a.n : 0;
+    while (len > 0) {
+        const int half = len >> 1;
+        const bool right = a.sokey[lo + half] < k;
+        lo = right ? lo + half + 1 : lo;
+        len = right ? len - half - 1 : half;
+    }
+    if (o >= count || lo >= a.n) {               // an unused row (an object always has its run)
+        if (t == 0) { info[0] = -1; info[1] = 0; }
+        if (t < 6) motion[t] = 0.f;
+        return;
+    }
+    const int root = a.soval[lo], m = (int)imin(a.size[root], a.n - lo);
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int j = t; j < m; j += MS_BLOCK) {
+        const int i = a.soval[lo + j];
+        const float *f = a.flow + (int64_t)i * a.fsp;
+        acc[0] += (double)a.pc[i];
+        acc[1] += (double)a.pc[a.pc_ld + i];
+        acc[2] += (double)a.pc[2 * a.pc_ld + i];
+        acc[3] += (double)f[0];
+        acc[4] += (double)f[a.fsc];
+        acc[5] += (double)f[2 * a.fsc];
+    }
+#pragma unroll
+    for (int c = 0; c < 6; ++c) red[c][t] = acc[c];
+    __syncthreads();
+    for (int w = MS_BLOCK / 2; w > 0; w >>= 1) {
+        if (t < w) {
+#pragma unroll
+            for (int c = 0; c < 6; ++c) red[c][t] += red[c][t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) { info[0] = root - p0; info[1] = m; }
+    if (t < 6) motion[t] = (float)(red[t][0] / (double)m);
+}
+
+inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+
+inline int count_bits(int64_t n) {
+    int bits = 1;
+    while (((int64_t)1 << bits) <= n) ++bits;    // object numbers 0 .. n
+    return bits;
+}
+
+size_t temp_bytes(int64_t n) {
+    size_t s1 = 0, s2 = 0, sc = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, s1, (const u64 *)nullptr, (u64 *)nullptr, (const int32_t *)nullptr,
+                                    (int32_t *)nullptr, (size_t)n, 0u, 64u, (hipStream_t) nullptr);
+    (void)rocprim::radix_sort_pairs(nullptr, s2, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
+                                    (int32_t *)nullptr, (size_t)n, 0u, 32u, (hipStream_t) nullptr);
+    (void)rocprim::exclusive_scan(nullptr, sc, (const int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)(n + 1),
+                                  rocprim::plus<int32_t>(), (hipStream_t) nullptr);
+    const size_t m = s1 > s2 ? s1 : s2;
+    return m > sc ? m : sc;
+}
+
+// workspace: key | sorted key | val | sorted val | parent | size | flag | excl | object key | sorted object key | sorted object
+// val | rocPRIM temporaries
+struct Layout {
+    u64 *key, *skey;
+    int32_t *val, *sval, *parent, *size, *flag, *excl, *soval;
+    uint32_t *okey, *sokey;
+    void *temp;
+    int64_t bytes;
+    Layout(char *p, int64_t n) {
+        char *b = p;
+        auto take = [&p](int64_t nbytes) { char *q = p; p += align256(nbytes); return q; };
+        key = reinterpret_cast<u64 *>(take(n * 8));
+        skey = reinterpret_cast<u64 *>(take(n * 8));
+        val = reinterpret_cast<int32_t *>(take(n * 4));
+        sval = reinterpret_cast<int32_t *>(take(n * 4));
+        parent = reinterpret_cast<int32_t *>(take(n * 4));
+        size = reinterpret_cast<int32_t *>(take(n * 4));
+        flag = reinterpret_cast<int32_t *>(take((n + 1) * 4));
+        excl = reinterpret_cast<int32_t *>(take((n + 1) * 4));
+        okey = reinterpret_cast<uint32_t *>(take(n * 4));
+        sokey = reinterpret_cast<uint32_t *>(take(n * 4));
+        soval = reinterpret_cast<int32_t *>(take(n * 4));
+        temp = p;
+        bytes = p - b;
+    }
+};
+
+// rocPRIM does not promise that its temporary storage grows with n: the room kept for it covers n and the next power of two
+inline int64_t temp_room(int64_t n) {
+    int64_t cap = 1024;
+    while (cap < n) cap <<= 1;
+    return align256((int64_t)imax((int64_t)temp_bytes(n), (int64_t)temp_bytes(cap)));
+}
+
+int64_t workspace_bytes(int64_t n) { return Layout(nullptr, n).bytes + temp_room(n); }
+
+}  // namespace
+
+extern "C" int64_t hpl_motion_segment_workspace_bytes(int batch, int64_t n_total) {
+    if (batch < 1 || batch > MS_MAX_BATCH || n_total < 0 || n_total >= MS_MAX_POINTS) return -1;
+    return workspace_bytes(n_total);
+}
+
+extern "C" int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *flow, int64_t flow_sc, int64_t flow_sp,
+                                  const float *residual, int batch, const int64_t *prefix, float tau, float eps, float dv,
+                                  int min_points, int max_objects, int32_t *labels, int32_t *obj_info, float *obj_motion,
+                                  int32_t *stats, void *workspace, int64_t workspace_bytes_, hplStream stream) {
+    HPL_REQUIRE(pc && flow && residual && prefix && labels && obj_info && obj_motion && stats && workspace,
+                "hpl_motion_segment: null pointer");
+    HPL_REQUIRE(batch >= 1 && batch <= MS_MAX_BATCH, "hpl_motion_segment: batch %d (1 .. %d)", batch, MS_MAX_BATCH);
+    HPL_REQUIRE(tau > 0.f && isfinite(tau), "hpl_motion_segment: tau must be finite and > 0");
+    HPL_REQUIRE(eps > 0.f && isfinite(eps), "hpl_motion_segment: eps must be finite and > 0");
+    HPL_REQUIRE(dv > 0.f, "hpl_motion_segment: dv must be > 0 (+inf: no flow criterion)");
+    HPL_REQUIRE(min_points >= 1, "hpl_motion_segment: min_points = %d (>= 1)", min_points);
+    HPL_REQUIRE(max_objects >= 1 && max_objects <= MS_MAX_OBJECTS, "hpl_motion_segment: max_objects = %d (1 .. %d)", max_objects,
+                MS_MAX_OBJECTS);
+    HPL_REQUIRE(prefix[0] == 0, "hpl_motion_segment: the prefix must start at 0");
+    for (int b = 0; b < batch; ++b)
+        HPL_REQUIRE(prefix[b + 1] >= prefix[b], "hpl_motion_segment: the prefix decreases at pair %d", b);
+    const int64_t N = prefix[batch];
+    HPL_REQUIRE(N < MS_MAX_POINTS, "hpl_motion_segment: %lld points pass the 32-bit element limit (N < 2^31 / 3)", (long long)N);
+    HPL_REQUIRE(pc_ld >= N, "hpl_motion_segment: row stride %lld below %lld points", (long long)pc_ld, (long long)N);
+    HPL_REQUIRE(flow_sc >= 1 && flow_sp >= 1 && (flow_sp != 1 || flow_sc >= N) && (flow_sc != 1 || flow_sp >= 3 || N <= 1),
+                "hpl_motion_segment: flow strides %lld (component) / %lld (point) overlap for %lld points", (long long)flow_sc,
+                (long long)flow_sp, (long long)N);
+    HPL_REQUIRE(workspace_bytes_ >= workspace_bytes(N), "hpl_motion_segment: workspace of %lld bytes, needs %lld",
+                (long long)workspace_bytes_, (long long)workspace_bytes(N));
+    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(flow) | reinterpret_cast<uintptr_t>(residual) |
+                  reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(obj_info) |
+                  reinterpret_cast<uintptr_t>(obj_motion) | reinterpret_cast<uintptr_t>(stats)) & 3u) == 0 &&
+                    (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
+                "hpl_motion_segment: arrays must be 4-byte aligned, the workspace 256-byte");
+    if (N == 0) return HPL_OK;
+
+    const Layout L(static_cast<char *>(workspace), N);
+    SegArgs a{};
+    a.pc = pc; a.pc_ld = pc_ld; a.flow = flow; a.fsc = flow_sc; a.fsp = flow_sp; a.residual = residual;
+    a.tau = tau;
+    a.eps2 = eps * eps;                          // rounded once to float32, as the predicate states
+    a.dv2 = dv * dv;
+    a.inv_cell = 1.0 / (MS_CELL_MARGIN * (double)eps);
+    a.n = (int32_t)N; a.batch = batch; a.min_points = min_points; a.max_objects = max_objects;
+    a.key = L.key; a.skey = L.skey; a.val = L.val; a.sval = L.sval; a.parent = L.parent; a.size = L.size;
+    a.flag = L.flag; a.excl = L.excl; a.okey = L.okey; a.sokey = L.sokey; a.soval = L.soval;
+    a.labels = labels; a.obj_info = obj_info; a.obj_motion = obj_motion; a.stats = stats;
+    for (int b = 0; b <= batch; ++b) a.pprefix[b] = (int32_t)prefix[b];
+
+    hipStream_t s = to_stream(stream);
+    if (hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * (size_t)batch, s) != hipSuccess) {
+        set_error("hpl_motion_segment: clearing the counts failed: %s", hipGetErrorString(hipGetLastError()));
+        return HPL_EHIP;
+    }
+    const unsigned grid = (unsigned)cdiv(N, MS_BLOCK), grid1 = (unsigned)cdiv(N + 1, MS_BLOCK);
+    k_seg_keys<<<grid, MS_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_motion_segment (keys)");
+    size_t tb = (size_t)temp_room(N);
+    hipError_t e = rocprim::radix_sort_pairs(L.temp, tb, (const u64 *)L.key, L.skey, (const int32_t *)L.val, L.sval, (size_t)N, 0u,
+                                             64u, s);          // (the largest key, of the non-movers, has every bit set)
+    if (e != hipSuccess) { set_error("hpl_motion_segment: radix sort failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
+    k_seg_link<<<grid, MS_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_motion_segment (link)");
+    k_seg_flatten<<<grid, MS_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_motion_segment (flatten)");
+    k_seg_flag<<<grid1, MS_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_motion_segment (flag)");
+    tb = (size_t)temp_room(N);
+    e = rocprim::exclusive_scan(L.temp, tb, (const int32_t *)L.flag, L.excl, 0, (size_t)(N + 1), rocprim::plus<int32_t>(), s);
+    if (e != hipSuccess) { set_error("hpl_motion_segment: scan failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
+    k_seg_label<<<grid, MS_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_motion_segment (label)");
+    tb = (size_t)temp_room(N);
+    e = rocprim::radix_sort_pairs(L.temp, tb, (const uint32_t *)L.okey, L.sokey, (const int32_t *)L.val, L.soval, (size_t)N, 0u,
+                                  (unsigned)count_bits(N), s);
+    if (e != hipSuccess) { set_error("hpl_motion_segment: radix sort failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
+    k_seg_objects<<<(unsigned)(batch * max_objects), MS_BLOCK, 0, s>>>(a);
+    HPL_CHECK_LAUNCH("hpl_motion_segment (objects)");
+    return HPL_OK;
+}

@@ -288,7 +288,7 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None):
+    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None, segment=None):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -311,18 +311,28 @@ class Trainer(object):
         B > 1 pairs are packed with one copy first -- and one more metrics launch of the refined flow into a third array; the
         forwards' fit statistics stay on the device and come back, joined by one concatenation, with the read-back.  The keys gain
         rigid_<metric> plus rigid_inliers (the inlier share), rigid_angle_deg and rigid_trans (the fitted rotation angle and
-        |t|), means over pairs.  With dense=True the refinement is still of the sampled flow."""
+        |t|), means over pairs.  With dense=True the refinement is still of the sampled flow.
+
+        segment={'eps': e, 'dv': v, 'min_points': m} (with rigid): the fit also returns its residuals and one
+        ops.motion_segment call per forward groups the points above the fit's tau into moving objects.  Its integer counts stay
+        on the device and come back with the read-back.  The keys gain seg_objects (objects per pair), seg_moving (the share
+        of a pair's points in objects) and seg_noise (the share labelled -2: movers in no object), means over pairs."""
         if dense_fill is not None and not dense:
             raise HplError('validate: dense_fill applies to dense=True')
         if rigid is not None:
             if not isinstance(rigid, dict) or set(rigid) - {'iters', 'tau'}:
                 raise HplError('validate: rigid takes {\'iters\': T, \'tau\': tau}, got %r' % (rigid,))
             rigid = {'iters': int(rigid.get('iters', 4)), 'tau': float(rigid.get('tau', 0.1))}
+        if segment is not None:
+            if rigid is None:
+                raise HplError('validate: segment applies to rigid')
+            segment = segment_options(segment)
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
         dkeys = ['dense_' + k for k in keys] + ['dense_coverage', 'dense_full'] if dense else []
         rkeys = ['rigid_' + k for k in keys] + list(RIGID_STATS) if rigid is not None else []
+        rkeys = rkeys + list(SEGMENT_STATS) if segment is not None else rkeys
         self.val_batches = 0
         self.val_pairs = []
         self._dense = None
@@ -341,6 +351,7 @@ class Trainer(object):
                 rsums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
                 rstage = ops.MetricsStage(n, self.device)
                 rstats = []                              # every forward's (B, 4) fit statistics, on the device
+                sstats, scounts = [], []                 # segment: every forward's (B, 4) integer counts, on the device
             nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
 
             def cameras_of(samples):
@@ -359,7 +370,14 @@ class Trainer(object):
                     from .flownet import rigid_refine
                     # an equal batch goes as the forward's own (B, 3, N) tensors: its flow rows are read in place
                     pc1, flow = batched if batched is not None else ([s_[0] for s_ in samples], list(preds))
-                    _, _, st, refined = rigid_refine(pc1, flow, **rigid)
+                    if segment is None:
+                        _, _, st, refined = rigid_refine(pc1, flow, **rigid)
+                    else:
+                        from .flownet import segment_motion
+                        fit = rigid_refine(pc1, flow, return_residual=True, **rigid)
+                        st, refined = fit[2], fit[3]
+                        sstats.append(segment_motion(pc1, flow, rigid=fit, tau=rigid['tau'], **segment)[3])
+                        scounts.extend(int(s_[0].shape[1]) for s_ in samples)
                     rstats.append(st)            # (sample order: the groups are runs of consecutive samples)
                     ops.flow_metrics_pairs(list(refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
                                            cameras_of(samples), rsums, nxt[0], rstage)
@@ -380,6 +398,8 @@ class Trainer(object):
                     dwords, dcv = dsums.cpu().numpy(), dcov.cpu().numpy()
                 if rigid is not None:
                     rwords, rst = rsums.cpu().numpy(), torch.cat(rstats).cpu().numpy()
+                    if segment is not None:
+                        sst = torch.cat(sstats).cpu().numpy()
             finally:
                 torch.cuda.current_stream(self.device).synchronize()     # the stage's copies have run before it is released
                 self._dense = self._dense_add = None
@@ -392,6 +412,8 @@ class Trainer(object):
                 for i, v in self.val_pairs:
                     v.update({'rigid_' + k: x for k, x in ops.flow_metrics_fold(rwords[i], cams).items()})
                     v.update(zip(RIGID_STATS, (float(x) for x in rst[i, 1:])))
+                    if segment is not None:
+                        v.update(zip(SEGMENT_STATS, segment_fold(sst[i], scounts[i])))
         keys = keys + dkeys + rkeys
         agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
@@ -518,6 +540,28 @@ class Trainer(object):
         return self.min_loss
 
 
+#: validate(segment=...): the per-pair keys from hpl_motion_segment's integer counts
+SEGMENT_STATS = ('seg_objects', 'seg_moving', 'seg_noise')
+
+
+def segment_options(segment):
+    """validate's segment argument, checked and with its defaults: {'eps': 0.5, 'dv': inf, 'min_points': 5}."""
+    if not isinstance(segment, dict) or set(segment) - {'eps', 'dv', 'min_points'}:
+        raise HplError('validate: segment takes {\'eps\': e, \'dv\': v, \'min_points\': m}, got %r' % (segment,))
+    o = {'eps': float(segment.get('eps', 0.5)), 'dv': float(segment.get('dv', float('inf'))),
+         'min_points': int(segment.get('min_points', 5))}
+    if not (0 < o['eps'] < float('inf')) or not o['dv'] > 0 or o['min_points'] < 1:
+        raise HplError('validate: segment needs eps finite and > 0, dv > 0 and min_points >= 1, got %r' % (segment,))
+    return o
+
+
+def segment_fold(row, points):
+    """(seg_objects, seg_moving, seg_noise) of one pair of `points` points from its (movers, objects, points in objects, out of
+    range) counts."""
+    movers, objects, inside, _ = (int(x) for x in row)
+    return float(objects), inside / max(1, points), (movers - inside) / max(1, points)
+
+
 #: validate(rigid=...): the per-pair fit statistics beside the rigid_<metric> keys (stats[1:] of ops.rigid_fit)
 RIGID_STATS = ('rigid_inliers', 'rigid_angle_deg', 'rigid_trans')
 
@@ -627,6 +671,16 @@ def parse_args(argv=None):
                     help='reweighted solves of --rigid-refine after the least-squares one (0 .. 16, default 4)')
     ap.add_argument('--rigid-tau', type=float, default=None, metavar='TAU',
                     help='--rigid-refine: inlier threshold and scale of the Geman-McClure weights in metres (> 0, default 0.1)')
+    ap.add_argument('--segment', action='store_true',
+                    help='with --evaluate --rigid-refine: group the points the rigid fit leaves unexplained (residual above '
+                         '--rigid-tau) into moving objects on the device and report seg_objects / seg_moving / seg_noise '
+                         '(DESIGN.md §19)')
+    ap.add_argument('--segment-eps', type=float, default=None, metavar='E',
+                    help='--segment: link radius in metres (finite and > 0, default 0.5)')
+    ap.add_argument('--segment-dv', type=float, default=None, metavar='V',
+                    help='--segment: largest flow difference of two linked points in metres (> 0, default inf: positions alone)')
+    ap.add_argument('--segment-min-points', type=int, default=None, metavar='M',
+                    help='--segment: points of the smallest object (>= 1, default 5)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -654,6 +708,17 @@ def parse_args(argv=None):
         ap.error('--rigid-tau takes a finite value > 0 and applies to --rigid-refine')
     a.rigid = {'iters': 4 if a.rigid_iters is None else a.rigid_iters,
                'tau': 0.1 if a.rigid_tau is None else a.rigid_tau} if a.rigid_refine else None
+    if a.segment and not (a.evaluate and a.rigid_refine):
+        ap.error('--segment applies to --evaluate --rigid-refine')
+    if a.segment_eps is not None and (not a.segment or not 0 < a.segment_eps < float('inf')):
+        ap.error('--segment-eps takes a finite value > 0 and applies to --segment')
+    if a.segment_dv is not None and (not a.segment or not a.segment_dv > 0):
+        ap.error('--segment-dv takes a value > 0 and applies to --segment')
+    if a.segment_min_points is not None and (not a.segment or a.segment_min_points < 1):
+        ap.error('--segment-min-points takes a value >= 1 and applies to --segment')
+    a.segment = {'eps': 0.5 if a.segment_eps is None else a.segment_eps,
+                 'dv': float('inf') if a.segment_dv is None else a.segment_dv,
+                 'min_points': 5 if a.segment_min_points is None else a.segment_min_points} if a.segment else None
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -674,7 +739,7 @@ def main(argv=None):
         return _real_data(a, tr, dev, rank, world)
     if a.evaluate:
         res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size, a.ragged,
-                          rigid=a.rigid)
+                          rigid=a.rigid, segment=a.segment)
         if rank == 0:
             print(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
@@ -794,7 +859,8 @@ def _real_data(a, tr, dev, rank, world):
         val = DenseFrames(val, full)
     val = _Shard(val, rank, world, cap)
     if train is None:
-        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid)
+        res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid,
+                          segment=a.segment)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -22,7 +22,7 @@ from . import _lib, ops
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, NbrTable, _ConvReLU, _conv_of, pointwise_conv,
                   to_channel_first, to_channel_last)
 
-__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine']
+__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine', 'segment_motion']
 
 
 # ----------------------------------------------------------------------------- lattice container
@@ -556,25 +556,19 @@ def _packed_rows(fls):
     return f0.as_strided(((off - f0.storage_offset()) // 3, 3), (3, 1), f0.storage_offset())
 
 
-def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
-    """The rigid refinement of a forward's flow in ONE ops.rigid_fit call (DESIGN.md §18): per pair the robust rigid fit of
-    (pc1, flow) and the flow with its inliers replaced by the rigid flow.  pc1 / flow as the models take and return them: a
-    (B, 3, N) tensor pair (or (3, N): one pair), or two lists of B (3, N_b) / (1, 3, N_b) tensors (a ragged batch); a packed
-    (3, sum N_b) cloud with its flow takes the pairs' counts from lat_or_counts (the forward's lattice, or a sequence of
-    counts).  kw: iters, tau, weight (packed, pair-major), return_residual (packed) of ops.rigid_fit.
-    The flow a forward returned is read in place (a (B, 3, N) view of its [B N, 3] rows; the row-block views of a ragged
-    forward); B > 1 clouds are packed into one (3, sum N_b) tensor first (one copy), any other list of flows likewise.
-    -> (R (B, 3, 3), t (B, 3), stats (B, 4), refined[, residual]), refined in the form of `flow`: views of one [sum N_b, 3]
-    tensor."""
+def _packed_pairs(pc1, flow, lat_or_counts, who):
+    """The packed operands of ops.rigid_fit / ops.motion_segment for the forms the models take and return (rigid_refine's
+    docstring lists them).  -> (pc (3, sum N_b), flow, prefix, counts, shape): shape None for a (B, 3, N) pair of tensors,
+    False for a packed pair, else the function that gives pair b's rows the form of flow[b]."""
     if isinstance(pc1, (list, tuple)) or isinstance(flow, (list, tuple)):
         if not isinstance(pc1, (list, tuple)) or not isinstance(flow, (list, tuple)) or len(pc1) != len(flow) or not pc1:
-            raise _lib.HplError('rigid_refine: pc1 and flow are both lists of as many clouds, or both tensors')
+            raise _lib.HplError('%s: pc1 and flow are both lists of as many clouds, or both tensors' % who)
         lead = [f.dim() == 3 for f in flow]
         pcs = [p[0] if p.dim() == 3 else p for p in pc1]
         fls = [f[0] if f.dim() == 3 else f for f in flow]
         counts = [int(p.shape[1]) for p in pcs]
         if lat_or_counts is not None and _pair_counts(lat_or_counts, sum(counts)) != counts:
-            raise _lib.HplError('rigid_refine: the clouds hold %s points, the lattice or counts say otherwise' % (counts,))
+            raise _lib.HplError('%s: the clouds hold %s points, the lattice or counts say otherwise' % (who, counts))
         pc = pcs[0] if len(pcs) == 1 else torch.cat(pcs, dim=1)
         fl = fls[0] if len(fls) == 1 else _packed_rows(fls)
         if fl is None:
@@ -583,7 +577,7 @@ def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
     elif pc1.dim() == 3:
         B, _, n = pc1.shape
         if flow.dim() != 3 or flow.shape[0] != B:
-            raise _lib.HplError('rigid_refine: a (B, 3, N) cloud takes a (B, 3, N) flow')
+            raise _lib.HplError('%s: a (B, 3, N) cloud takes a (B, 3, N) flow' % who)
         counts = [int(n)] * B
         pc = pc1[0] if B == 1 else pc1.transpose(0, 1).reshape(3, B * n)
         fl = flow[0] if B == 1 else flow.transpose(1, 2).reshape(B * n, 3)       # (the forward's rows: a view)
@@ -594,6 +588,20 @@ def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
     prefix = [0]
     for c in counts:
         prefix.append(prefix[-1] + c)
+    return pc, fl, prefix, counts, shape
+
+
+def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
+    """The rigid refinement of a forward's flow in ONE ops.rigid_fit call (DESIGN.md §18): per pair the robust rigid fit of
+    (pc1, flow) and the flow with its inliers replaced by the rigid flow.  pc1 / flow as the models take and return them: a
+    (B, 3, N) tensor pair (or (3, N): one pair), or two lists of B (3, N_b) / (1, 3, N_b) tensors (a ragged batch); a packed
+    (3, sum N_b) cloud with its flow takes the pairs' counts from lat_or_counts (the forward's lattice, or a sequence of
+    counts).  kw: iters, tau, weight (packed, pair-major), return_residual (packed) of ops.rigid_fit.
+    The flow a forward returned is read in place (a (B, 3, N) view of its [B N, 3] rows; the row-block views of a ragged
+    forward); B > 1 clouds are packed into one (3, sum N_b) tensor first (one copy), any other list of flows likewise.
+    -> (R (B, 3, 3), t (B, 3), stats (B, 4), refined[, residual]), refined in the form of `flow`: views of one [sum N_b, 3]
+    tensor."""
+    pc, fl, prefix, counts, shape = _packed_pairs(pc1, flow, lat_or_counts, 'rigid_refine')
     res = ops.rigid_fit(pc, fl, prefix=prefix, **kw)
     ref = res[3]
     if shape is None:
@@ -603,6 +611,57 @@ def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
     else:
         ref = [shape(ref[prefix[b]:prefix[b + 1]], b) for b in range(len(counts))]
     return res[:3] + (ref,) + res[4:]
+
+
+# ----------------------------------------------------------------------------- moving objects
+def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False, iters=4, tau=0.1, weight=None, **kw):
+    """The moving objects of a forward's flow: ops.rigid_fit(return_residual=True) over the pairs -- unless
+    `rigid` hands in what an earlier rigid_refine(..., return_residual=True) or ops.rigid_fit(..., return_residual=True) of the
+    same operands returned --, then ONE ops.motion_segment call with that fit's residuals and tau.  pc1 / flow / lat_or_counts:
+    the forms rigid_refine takes, read in place the same way.  iters, tau, weight: of the fit; kw: eps, dv, min_points,
+    max_objects of ops.motion_segment.
+    -> (labels (sum N_b,) int32, packed pair-major; obj_info (B, max_objects, 2); obj_motion (B, max_objects, 6); stats (B, 4)):
+    no read-back, no host synchronisation.
+    object_fits=True, and only then, READS BACK stats and obj_info once (a host synchronisation: this is for interactive use,
+    not for an evaluation loop), gathers each listed object's points in object order and fits every object's own rigid
+    motion with ops.rigid_fit, the objects as its segments, 64 a call.  The result gains a fifth entry: per pair a tuple
+    (R (K_b, 3, 3), t (K_b, 3), stats (K_b, 4)) over the pair's first K_b = min(objects, max_objects) objects (an object of fewer
+    than 3 points has status 0, R = I, t = 0, as that op defines)."""
+    pc, fl, prefix, counts, _ = _packed_pairs(pc1, flow, lat_or_counts, 'segment_motion')
+    if rigid is None:
+        residual = ops.rigid_fit(pc, fl, weight=weight, iters=iters, tau=tau, prefix=prefix, return_residual=True)[4]
+    else:
+        residual = rigid[-1] if isinstance(rigid, (list, tuple)) and len(rigid) == 5 else None
+        if not torch.is_tensor(residual) or tuple(residual.shape) != (pc.shape[1],):
+            raise _lib.HplError('segment_motion: rigid is the result of a fit of the same operands with return_residual=True')
+    labels, info, motion, stats = ops.motion_segment(pc, fl, residual, tau=tau, prefix=prefix, **kw)
+    if not object_fits:
+        return labels, info, motion, stats
+    host = info.cpu().numpy()                                # the one read-back (it follows the launches on this stream)
+    dev = pc.device
+    fits = []
+    flt = fl if tuple(fl.shape) == (3, pc.shape[1]) else fl.t()          # (3, N) view, any strides
+    for b in range(len(counts)):
+        sizes = [int(c) for r, c in host[b] if r >= 0]
+        K = len(sizes)
+        if K == 0:
+            fits.append((torch.zeros((0, 3, 3), device=dev), torch.zeros((0, 3), device=dev), torch.zeros((0, 4), device=dev)))
+            continue
+        lab = labels[prefix[b]:prefix[b + 1]]
+        order = torch.argsort(torch.where((lab >= 0) & (lab < K), lab, K), stable=True)[:sum(sizes)] + prefix[b]
+        opc, ofl = pc[:, order].contiguous(), flt[:, order].contiguous()
+        Rs, ts, sts = [], [], []
+        for c in range(0, K, 64):
+            pre = [0]
+            for m in sizes[c:c + 64]:
+                pre.append(pre[-1] + m)
+            lo = sum(sizes[:c])
+            R, t, st, _ = ops.rigid_fit(opc[:, lo:lo + pre[-1]], ofl[:, lo:lo + pre[-1]], iters=iters, tau=tau, prefix=pre)
+            Rs.append(R)
+            ts.append(t)
+            sts.append(st)
+        fits.append((torch.cat(Rs), torch.cat(ts), torch.cat(sts)))
+    return labels, info, motion, stats, fits
 
 
 # ----------------------------------------------------------------------------- dense flow

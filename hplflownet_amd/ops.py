@@ -513,6 +513,93 @@ def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_resid
     return res + (residual,) if return_residual else res
 
 
+# --------------------------------------------------------------------------- moving objects from flow
+_SEGMENT_WS = {}
+
+
+def _segment_workspace(device, st, nbytes):
+    """Per-(device, stream) scratch of hpl_motion_segment, one buffer per size class (the next power of two), as
+    _rigid_workspace keeps them."""
+    size = 1 << max(12, int(nbytes - 1).bit_length())
+    key = (device, st, size)
+    ws = _SEGMENT_WS.get(key)
+    if ws is None:
+        ws = _SEGMENT_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
+    return ws
+
+
+def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_points=5, max_objects=256, prefix=None, out=None):
+    """hpl_motion_segment on the current stream: the points whose residual against a rigid fit exceeds tau
+    (the movers), grouped into the connected components of the graph that links two movers of a pair within eps metres of
+    each other whose flows differ by at most dv (+inf: positions alone); a component of at least min_points movers is an
+    object, numbered per pair in the order of its smallest point index.  pc (3, N) float32, flow (3, N) or [N, 3] float32 of
+    any strides, prefix: exactly as ops.rigid_fit takes them (read in place); residual (N,) float32 as rigid_fit returns it.
+    -> (labels (N,) int32: object number, -1 no mover, -2 noise, -3 out of the grid's range; obj_info (B, max_objects, 2) int32:
+    root index within the pair and point count, unused rows -1, 0; obj_motion (B, max_objects, 6) float32: centroid and mean
+    flow, unused rows 0; stats (B, 4) int32: movers, objects -- the true count, also past max_objects --, points in objects,
+    points out of range).  out: a contiguous (N,) int32 tensor that takes the labels.  The same bits for a pair alone and in
+    any batch.  No autograd, no host synchronisation, no read-back."""
+    def scalar(v, name, inf_ok=False):
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            v = float('nan')
+        if not (v > 0 and (inf_ok or v < float('inf'))):
+            raise _lib.HplError('motion_segment: %s = %r (%s > 0)' % (name, v, 'any value' if inf_ok else 'finite and'))
+        return v
+    tau, eps, dv = scalar(tau, 'tau'), scalar(eps, 'eps'), scalar(dv, 'dv', True)
+    for v, name, hi in ((min_points, 'min_points', 2 ** 31 - 1), (max_objects, 'max_objects', 4096)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise _lib.HplError('motion_segment: %s = %r (an int in 1 .. %d)' % (name, v, hi))
+    pc, pc_ld = _soa3(pc, 'pc', 'motion_segment')
+    N, dev = pc.shape[1], pc.device
+    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
+            (tuple(flow.shape) != (3, N) and tuple(flow.shape) != (N, 3)):
+        raise _lib.HplError('motion_segment: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
+            N, N, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
+    if flow.requires_grad:
+        raise _lib.HplError('motion_segment has no autograd: flow requires grad')
+    if tuple(flow.shape) != (3, N):
+        flow = flow.t()
+    if N > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N) or
+                  (flow.stride(0) == 1 and flow.stride(1) < 3 and N > 1)):
+        flow = flow.contiguous()
+    if not torch.is_tensor(residual) or tuple(residual.shape) != (N,) or residual.dtype != torch.float32 or \
+            residual.device != dev or residual.requires_grad:
+        raise _lib.HplError('motion_segment: residual must be a (%d,) float32 tensor on %s without grad' % (N, dev))
+    residual = residual.contiguous()
+    pp = [0, N] if prefix is None else [int(x) for x in prefix]
+    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != N or any(b < a for a, b in zip(pp, pp[1:])):
+        raise _lib.HplError('motion_segment: the prefix holds B + 1 <= 65 non-decreasing entries from 0 to N = %d, got %s' % (N, pp))
+    B = len(pp) - 1
+    if out is not None:
+        if not torch.is_tensor(out) or tuple(out.shape) != (N,) or out.dtype != torch.int32 or out.device != dev or \
+                not out.is_contiguous():
+            raise _lib.HplError('motion_segment: out must be a contiguous (%d,) int32 tensor on %s' % (N, dev))
+        labels = out
+    else:
+        labels = torch.empty(N, dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    if N == 0:                                   # nothing to launch: every pair is empty
+        info = torch.zeros((B, max_objects, 2), dtype=torch.int32, device=dev)
+        info[:, :, 0] = -1
+        return (labels, info, torch.zeros((B, max_objects, 6), dtype=torch.float32, device=dev),
+                torch.zeros((B, 4), dtype=torch.int32, device=dev))
+    info = torch.empty((B, max_objects, 2), dtype=torch.int32, device=dev)
+    motion = torch.empty((B, max_objects, 6), dtype=torch.float32, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    nbytes = lib.hpl_motion_segment_workspace_bytes(B, N)
+    if nbytes < 0:
+        raise _lib.HplError('motion_segment: %d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)' % (B, N))
+    st = stream()
+    ws = _segment_workspace(dev, st, nbytes)
+    check(lib.hpl_motion_segment(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), residual.data_ptr(), B,
+                                 (ctypes.c_int64 * (B + 1))(*pp), tau, eps, dv, min_points, max_objects, labels.data_ptr(),
+                                 info.data_ptr(), motion.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st),
+          'hpl_motion_segment')
+    return labels, info, motion, stats
+
+
 # --------------------------------------------------------------------------- data transforms
 def transform_capacity(M, num_points):
     """The most rows hpl_transform_pair emits for M points: min(num_points, M), or M when num_points <= 0."""

@@ -938,6 +938,43 @@ int hpl_rigid_fit(const float *pc, int64_t pc_ld, const float *flow, int64_t flo
                   int batch, const int64_t *prefix /* HOST */, int iters, float tau, float *Rt, float *stats, float *residual,
                   float *refined, void *workspace, int64_t workspace_bytes, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Moving objects from flow (csrc/motion_segment.hip): the points a rigid fit leaves unexplained, grouped into connected
+ * components over position and flow, numbered, with each object's size, centroid and mean flow.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_motion_segment for `batch` pairs of n_total points together, in bytes (monotone in both); -1 for a batch
+ * outside 1 .. 64 or n_total outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_motion_segment_workspace_bytes(int batch, int64_t n_total);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N), flow through flow_sc / flow_sp and prefix (HOST, batch + 1 ints, batch
+ * 1 .. 64) exactly as hpl_rigid_fit reads them; residual (N) float32 as hpl_rigid_fit writes it.  tau > 0 finite, eps > 0
+ * finite, dv > 0 (+inf: no flow criterion), min_points >= 1, 1 <= max_objects <= 4096.
+ * MOVER: point i is a mover when residual_i > tau (a NaN residual is not), its three coordinates and three flow components
+ * are finite, and its cell is representable: cell_k = floor(x_k * (1 / (1.001 * eps))) in float64 (the product 1.001 * eps,
+ * the quotient and the product with x_k each rounded once) with |cell_k| <= 2^18 - 2 for k = x, y, z.
+ * EDGE: movers i, j of the same pair are linked when d2 <= eps2 and g2 <= dv2, with d2 = (dx * dx + dy * dy) + dz * dz over
+ * the positions and g2 the same over the flows, in float32 with every operation rounded and no contraction (the arithmetic of
+ * hpl_knn_interp); eps2 = eps * eps and dv2 = dv * dv rounded once to float32.  Points of different pairs never link.
+ * COMPONENT: a connected component of that graph; its root is its smallest point index.  OBJECT: a component of at least
+ * min_points movers; a pair's objects are numbered 0, 1, ... in ascending root order.
+ * labels (N) int32: the object number of a mover in an object (numbers run past max_objects: nothing is dropped here); -1 no
+ * mover; -2 noise (a mover in a smaller component); -3 out of range (a mover but for its cell).
+ * obj_info [batch][max_objects][2] int32: root (index within the pair) and point count of the pair's first max_objects
+ * objects; unused rows -1, 0.  obj_motion [batch][max_objects][6] float32: centroid and mean flow of each: float64 sums of the
+ * float32 inputs in a fixed order (no floating-point atomic), divided by the count, rounded once; unused rows 0.
+ * stats [batch][4] int32: movers, objects (the true count, which may exceed max_objects), points in objects, points out of
+ * range.  Every output of a pair is the same bits alone, anywhere in a batch and beside other work.
+ * The grid is an accelerator only: the result is the all-pairs predicate's (tests/segment_oracle.py restates it in numpy).
+ * Stream-ordered, a fixed number of launches whose sizes depend on N, batch and max_objects alone, no copy back, no host
+ * synchronisation; no lane or workgroup waits for another.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_motion_segment_workspace_bytes(batch, N).
+ * HPL_EINVAL before any launch (and without a device): batch, tau, eps, dv, min_points or max_objects out of range or NaN; a
+ * prefix that does not start at 0 or decreases; pc_ld < N; flow strides < 1 or overlapping; a null array, prefix or
+ * workspace; misaligned arrays; a workspace that is too small; N >= 2^31 / 3.  N == 0 is a no-op. */
+int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *flow, int64_t flow_sc, int64_t flow_sp,
+                       const float *residual, int batch, const int64_t *prefix /* HOST */, float tau, float eps, float dv,
+                       int min_points, int max_objects, int32_t *labels, int32_t *obj_info, float *obj_motion, int32_t *stats,
+                       void *workspace, int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
