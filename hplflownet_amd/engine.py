@@ -46,7 +46,7 @@ import torch
 from . import data as data_mod
 from . import ops, parallel
 from ._lib import HplError
-from .flownet import HPLFlowNet, HPLFlowNetShallow, load_reference_checkpoint
+from .flownet import HPLFlowNet, HPLFlowNetShallow, load_reference_checkpoint, selfsup_loss
 from .lattice import GenerateDataUnsymmetric, LatticePipeline, NativeLatticeBuild
 from .synthetic import SCALES_FILTER_MAP, fill_module_, synthetic_pair
 
@@ -123,7 +123,8 @@ class SyntheticPairs(object):
 
 class Trainer(object):
     def __init__(self, arch='HPLFlowNet', device='cuda', lr=1e-4, seed=0, distributed=False, rank=0, init='hash',
-                 native_step=None):
+                 native_step=None, loss='epe3d', selfsup=None):
+        self.loss, self.selfsup = loss, selfsup_options(loss, selfsup)
         cls, nsc = ARCHS[arch]
         self.rank = rank
         self.arch, self.device = arch, torch.device(device)
@@ -153,9 +154,16 @@ class Trainer(object):
         # gradients in one flat arena the all-reduce runs on); HPL_NATIVE_TRAIN=0 / native_step=False keep the autograd path
         if native_step is None:
             native_step = os.environ.get('HPL_NATIVE_TRAIN', '1') != '0'
-        self.native_step = bool(native_step) and self.device.type == 'cuda'
+        # (the self-supervised loss runs on the autograd path: the native program's loss op takes a ground-truth flow)
+        self.native_step = bool(native_step) and self.device.type == 'cuda' and loss == 'epe3d'
         self.tplan = None
         self.native_steps = 0
+
+    def _pair_loss(self, flow, pc1, pc2, sf):
+        """The loss of one pair's forward: EPE3D against sf, or (loss='selfsup') the self-supervised loss, which never reads sf."""
+        if self.loss == 'selfsup':
+            return selfsup_loss(flow, pc1[None], pc2[None], **self.selfsup)[0]
+        return epe3d_loss(flow, sf[None])
 
     def train_step(self, pc1, pc2, sf, lat):
         """One optimiser step on one pair (main.py:203-217) -> the loss (device tensor, not synchronised)."""
@@ -176,7 +184,7 @@ class Trainer(object):
                 return r[1][0].clone()
             self.tplan.gflat.zero_()                 # a lattice the native backward refuses: autograd adds into the same arena
         flow = self.model(pc1[None], pc2[None], lat)
-        loss = epe3d_loss(flow, sf[None])
+        loss = self._pair_loss(flow, pc1, pc2, sf)
         if self.tplan is None:
             self.opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -218,7 +226,7 @@ class Trainer(object):
         for b in range(B):
             lb = self._single_lattice(pc1[b], pc2[b])
             flow = self.model(pc1[b][None], pc2[b][None], lb)
-            loss = epe3d_loss(flow, sf[b][None])
+            loss = self._pair_loss(flow, pc1[b], pc2[b], sf[b])
             (loss / B).backward()
             losses.append(loss.detach())
         if self.tplan is not None:
@@ -540,6 +548,25 @@ class Trainer(object):
         return self.min_loss
 
 
+def selfsup_options(loss, selfsup):
+    """Trainer's loss / selfsup arguments, checked: None for 'epe3d', else {'k': 8, 'w_chamfer': 1.0, 'w_smooth': 1.0} with the
+    given entries in place."""
+    if loss not in ('epe3d', 'selfsup'):
+        raise HplError('Trainer: loss is \'epe3d\' or \'selfsup\', got %r' % (loss,))
+    if loss == 'epe3d':
+        if selfsup is not None:
+            raise HplError('Trainer: selfsup options apply to loss=\'selfsup\'')
+        return None
+    selfsup = {} if selfsup is None else selfsup
+    if not isinstance(selfsup, dict) or set(selfsup) - {'k', 'w_chamfer', 'w_smooth'}:
+        raise HplError('Trainer: selfsup takes {\'k\': k, \'w_chamfer\': w, \'w_smooth\': w}, got %r' % (selfsup,))
+    o = {'k': selfsup.get('k', 8), 'w_chamfer': float(selfsup.get('w_chamfer', 1.0)), 'w_smooth': float(selfsup.get('w_smooth', 1.0))}
+    if isinstance(o['k'], bool) or not isinstance(o['k'], int) or not 0 <= o['k'] <= 8 or \
+            not 0 <= o['w_chamfer'] < float('inf') or not 0 <= o['w_smooth'] < float('inf') or (o['k'] == 0 and o['w_smooth'] != 0):
+        raise HplError('Trainer: selfsup needs k in 1 .. 8 (0 with w_smooth = 0) and finite weights >= 0, got %r' % (selfsup,))
+    return o
+
+
 #: validate(segment=...): the per-pair keys from hpl_motion_segment's integer counts
 SEGMENT_STATS = ('seg_objects', 'seg_moving', 'seg_noise')
 
@@ -681,6 +708,16 @@ def parse_args(argv=None):
                     help='--segment: largest flow difference of two linked points in metres (> 0, default inf: positions alone)')
     ap.add_argument('--segment-min-points', type=int, default=None, metavar='M',
                     help='--segment: points of the smallest object (>= 1, default 5)')
+    ap.add_argument('--loss', default='epe3d', choices=['epe3d', 'selfsup'],
+                    help='training loss: epe3d against the ground-truth flow (default), or selfsup: Chamfer distance between the '
+                         'warped cloud and pc2 plus the smoothness of the flow over the k nearest neighbours -- no flow label is '
+                         'read; it runs on the autograd path (DESIGN.md §20)')
+    ap.add_argument('--selfsup-k', type=int, default=None, metavar='K',
+                    help='--loss selfsup: neighbours of the smoothness graph (1 .. 8, default 8)')
+    ap.add_argument('--selfsup-chamfer-weight', type=float, default=None, metavar='W',
+                    help='--loss selfsup: weight of the Chamfer term (finite and >= 0, default 1)')
+    ap.add_argument('--selfsup-smooth-weight', type=float, default=None, metavar='W',
+                    help='--loss selfsup: weight of the smoothness term (finite and >= 0, default 1)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -719,6 +756,17 @@ def parse_args(argv=None):
     a.segment = {'eps': 0.5 if a.segment_eps is None else a.segment_eps,
                  'dv': float('inf') if a.segment_dv is None else a.segment_dv,
                  'min_points': 5 if a.segment_min_points is None else a.segment_min_points} if a.segment else None
+    on = a.loss == 'selfsup'
+    if on and a.evaluate:
+        ap.error('--loss applies to training (--evaluate reports the supervised metrics)')
+    if a.selfsup_k is not None and (not on or not 1 <= a.selfsup_k <= 8):
+        ap.error('--selfsup-k takes 1 .. 8 and applies to --loss selfsup')
+    for v, name in ((a.selfsup_chamfer_weight, '--selfsup-chamfer-weight'), (a.selfsup_smooth_weight, '--selfsup-smooth-weight')):
+        if v is not None and (not on or not 0 <= v < float('inf')):
+            ap.error('%s takes a finite value >= 0 and applies to --loss selfsup' % name)
+    a.selfsup = {'k': 8 if a.selfsup_k is None else a.selfsup_k,
+                 'w_chamfer': 1.0 if a.selfsup_chamfer_weight is None else a.selfsup_chamfer_weight,
+                 'w_smooth': 1.0 if a.selfsup_smooth_weight is None else a.selfsup_smooth_weight} if on else None
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -732,7 +780,7 @@ def main(argv=None):
     rank, world, local_rank = parallel.init_distributed()
     dev = torch.device('cuda', local_rank)
     torch.cuda.set_device(dev)
-    tr = Trainer(a.arch, dev, lr=a.lr, distributed=world > 1, rank=rank, init=a.init)
+    tr = Trainer(a.arch, dev, lr=a.lr, distributed=world > 1, rank=rank, init=a.init, loss=a.loss, selfsup=a.selfsup)
     if a.resume:
         tr.resume(a.resume, load_optimizer=not a.evaluate)
     if a.dataset != 'synthetic':

@@ -664,6 +664,37 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
     return labels, info, motion, stats, fits
 
 
+# ----------------------------------------------------------------------------- self-supervised loss
+def selfsup_loss(flow, pc1, pc2, k=8, w_chamfer=1.0, w_smooth=1.0):
+    """The self-supervised loss of a forward's flow in ONE ops.selfsup_loss call: Chamfer distance between
+    pc1 + flow and pc2 plus the smoothness of the flow over pc1's k-nearest-neighbour graph, per pair; no flow label.  flow /
+    pc1 / pc2 as the models return and take them, in the forms rigid_refine takes: (B, 3, N) tensors (or (3, N): one pair),
+    or lists of B (3, N_b) / (1, 3, N_b) tensors (a ragged batch).  The flow is read in place the same way.
+    -> (the mean of L over the pairs, a scalar that back-propagates into `flow` alone -- pc1 and pc2 get no gradient --,
+    components (B, 4) = (L, C12, C21, S) per pair, detached)."""
+    pc, fl, prefix1, counts, _ = _packed_pairs(pc1, flow, None, 'selfsup_loss')
+    B = len(counts)
+    if isinstance(pc2, (list, tuple)):
+        if len(pc2) != B:
+            raise _lib.HplError('selfsup_loss: pc1 lists %d clouds, pc2 %d' % (B, len(pc2)))
+        qs = [p[0] if p.dim() == 3 else p for p in pc2]
+        counts2 = [int(p.shape[1]) for p in qs]
+        q = qs[0] if B == 1 else torch.cat(qs, dim=1)
+    elif not torch.is_tensor(pc2) or pc2.dim() != (3 if torch.is_tensor(pc1) and pc1.dim() == 3 else 2) or \
+            (pc2.dim() == 3 and pc2.shape[0] != B):
+        raise _lib.HplError('selfsup_loss: pc2 comes in the form of pc1 (%d pairs)' % B)
+    elif pc2.dim() == 3:
+        counts2 = [int(pc2.shape[2])] * B
+        q = pc2[0] if B == 1 else pc2.transpose(0, 1).reshape(3, B * counts2[0])
+    else:
+        counts2, q = [int(pc2.shape[1])], pc2
+    prefix2 = [0]
+    for c in counts2:
+        prefix2.append(prefix2[-1] + c)
+    L, comps = ops.SelfSupLossFn.apply(fl, pc, q, k, w_chamfer, w_smooth, prefix1, prefix2)
+    return L.mean(), comps
+
+
 # ----------------------------------------------------------------------------- dense flow
 class DenseState(object):
     """What DenseFlow.forward keeps for later queries: the lattice (its arena holds the level-0 table of cloud 1), the vertex

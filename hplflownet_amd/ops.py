@@ -600,6 +600,132 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
     return labels, info, motion, stats
 
 
+# --------------------------------------------------------------------------- self-supervised loss
+_SELFSUP_WS = {}
+
+
+def _selfsup_workspace(device, st, nbytes):
+    """Per-(device, stream) scratch of hpl_selfsup_loss, one buffer per size class (the next power of two), as
+    _rigid_workspace keeps them."""
+    size = 1 << max(12, int(nbytes - 1).bit_length())
+    key = (device, st, size)
+    ws = _SELFSUP_WS.get(key)
+    if ws is None:
+        ws = _SELFSUP_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
+    return ws
+
+
+def _prefix(prefix, n, who, what):
+    pp = [0, n] if prefix is None else [int(x) for x in prefix]
+    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != n or any(b < a for a, b in zip(pp, pp[1:])):
+        raise _lib.HplError('%s: %s holds B + 1 <= 65 non-decreasing entries from 0 to %d, got %s' % (who, what, n, pp))
+    return pp
+
+
+def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None, prefix2=None, need_grad=True,
+                 return_neighbors=False, out=None):
+    """hpl_selfsup_loss on the current stream: per pair the Chamfer distance between the warped cloud
+    pc1 + flow and pc2 (both directions, squared distances to the nearest point, means over the points) plus the smoothness
+    of the flow over pc1's k-nearest-neighbour graph (mean over the points of the mean |f_i - f_n|^2 over a point's k nearest
+    other points), L = w_chamfer (C12 + C21) + w_smooth S, and dL/dflow with the neighbour assignments held constant.  pc1
+    (3, N1), pc2 (3, N2) float32; flow (3, N1) or [N1, 3] float32 of any strides (read in place, as ops.rigid_fit reads it).
+    k 1 .. 8, or 0 with w_smooth = 0 (no graph search); the weights finite and >= 0.  prefix1 / prefix2 (host sequences of B + 1
+    ints from 0 to N1 / N2): B <= 64 pairs, each with its own loss.
+    -> (loss (B, 4) = (L, C12, C21, S), dflow [N1, 3] or None with need_grad=False[, nn12 (N1,), nn21 (N2,), nbr (k, N1) int32
+    into the packed clouds, -1 where absent]).  out: a contiguous [N1, 3] float32 tensor that takes dflow (it must not overlap an
+    input).  Float64 sums in a fixed order: the same bits for a pair alone and in any batch.  This is the raw op (a tensor that
+    requires grad raises HplError; SelfSupLossFn is the autograd form); no host synchronisation, no read-back."""
+    who = 'selfsup_loss'
+    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 8:
+        raise _lib.HplError('%s: k = %r (an int in 0 .. 8)' % (who, k))
+    try:
+        w_chamfer, w_smooth = float(w_chamfer), float(w_smooth)
+    except (TypeError, ValueError):
+        w_chamfer = w_smooth = float('nan')
+    if not (0 <= w_chamfer < float('inf')) or not (0 <= w_smooth < float('inf')):
+        raise _lib.HplError('%s: the weights must be finite and >= 0, got %r / %r' % (who, w_chamfer, w_smooth))
+    if k == 0 and w_smooth != 0:
+        raise _lib.HplError('%s: k = 0 goes with w_smooth = 0' % who)
+    pc1, ld1 = _soa3(pc1, 'pc1', who)
+    pc2, ld2 = _soa3(pc2, 'pc2', who)
+    N1, N2, dev = pc1.shape[1], pc2.shape[1], pc1.device
+    if pc2.device != dev:
+        raise _lib.HplError('%s: pc1 on %s, pc2 on %s' % (who, dev, pc2.device))
+    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
+            (tuple(flow.shape) != (3, N1) and tuple(flow.shape) != (N1, 3)):
+        raise _lib.HplError('%s: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
+            who, N1, N1, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
+    if flow.requires_grad:
+        raise _lib.HplError('%s is the raw op: flow requires grad (SelfSupLossFn is the autograd form)' % who)
+    if tuple(flow.shape) != (3, N1):
+        flow = flow.t()
+    if N1 > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N1) or
+                   (flow.stride(0) == 1 and flow.stride(1) < 3 and N1 > 1)):
+        flow = flow.contiguous()
+    p1, p2 = _prefix(prefix1, N1, who, 'prefix1'), _prefix(prefix2, N2, who, 'prefix2')
+    if len(p1) != len(p2):
+        raise _lib.HplError('%s: prefix1 lists %d pairs, prefix2 %d' % (who, len(p1) - 1, len(p2) - 1))
+    B = len(p1) - 1
+    dflow = None
+    if out is not None:
+        if not need_grad or not torch.is_tensor(out) or tuple(out.shape) != (N1, 3) or out.dtype != torch.float32 or \
+                out.device != dev or not out.is_contiguous() or out.requires_grad:
+            raise _lib.HplError('%s: out (with need_grad) must be a contiguous (%d, 3) float32 tensor on %s' % (who, N1, dev))
+        dflow = out
+    elif need_grad:
+        dflow = torch.empty((N1, 3), dtype=torch.float32, device=dev)
+    nn12 = nn21 = nbr = None
+    if return_neighbors:
+        nn12 = torch.full((N1,), -1, dtype=torch.int32, device=dev)
+        nn21 = torch.full((N2,), -1, dtype=torch.int32, device=dev)
+        nbr = torch.full((k, N1), -1, dtype=torch.int32, device=dev)
+    if N1 == 0:                                  # nothing to launch: every component of every pair is 0
+        loss = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+    else:
+        lib = _lib.load()
+        loss = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        nbytes = lib.hpl_selfsup_loss_workspace_bytes(B, N1, N2, k)
+        if nbytes < 0:
+            raise _lib.HplError('%s: %d pairs of %d / %d points together, k = %d are outside the limits (64 pairs, counts < 2^31 / 3, '
+                                'k N1 < 2^31)' % (who, B, N1, N2, k))
+        st = stream()
+        ws = _selfsup_workspace(dev, st, nbytes)
+        check(lib.hpl_selfsup_loss(pc1.data_ptr(), ld1, flow.data_ptr(), flow.stride(0), flow.stride(1), pc2.data_ptr(), ld2, B,
+                                   (ctypes.c_int64 * (B + 1))(*p1), (ctypes.c_int64 * (B + 1))(*p2), k, w_chamfer, w_smooth,
+                                   loss.data_ptr(), ptr(dflow), ptr(nn12), ptr(nn21), ptr(nbr) if k > 0 else None, ws.data_ptr(),
+                                   ws.numel(), st), 'hpl_selfsup_loss')
+    return (loss, dflow, nn12, nn21, nbr) if return_neighbors else (loss, dflow)
+
+
+class SelfSupLossFn(torch.autograd.Function):
+    """ops.selfsup_loss with autograd: forward computes the loss and dL/dflow in ONE call; backward hands back that gradient
+    scaled by each pair's upstream gradient.  (flow (3, N1) or [N1, 3], pc1, pc2, k, w_chamfer, w_smooth, prefix1, prefix2) ->
+    (L (B,), components (B, 4), not differentiable).  pc1 and pc2 get no gradient: the neighbour assignments are constants."""
+
+    @staticmethod
+    def forward(ctx, flow, pc1, pc2, k, w_chamfer, w_smooth, prefix1, prefix2):
+        loss, dflow = selfsup_loss(pc1.detach(), flow.detach(), pc2.detach(), k, w_chamfer, w_smooth, prefix1, prefix2)
+        N1 = dflow.shape[0]
+        B = loss.shape[0]
+        pair = None
+        if B > 1:                                # the pair of every point (host numbers: no read-back)
+            counts = [b - a for a, b in zip(prefix1, prefix1[1:])]
+            pair = torch.repeat_interleave(torch.arange(B, device=dflow.device),
+                                           torch.tensor(counts, device=dflow.device), output_size=N1)
+        ctx.rows = tuple(flow.shape) != (3, N1)  # flow came point-major
+        ctx.pair = pair
+        ctx.save_for_backward(dflow)
+        comps = loss.clone()
+        ctx.mark_non_differentiable(comps)
+        return loss[:, 0].clone(), comps
+
+    @staticmethod
+    def backward(ctx, gL, _):
+        dflow, = ctx.saved_tensors
+        g = dflow * (gL[0] if ctx.pair is None else gL[ctx.pair][:, None])
+        return (g if ctx.rows else g.t()), None, None, None, None, None, None, None
+
+
 # --------------------------------------------------------------------------- data transforms
 def transform_capacity(M, num_points):
     """The most rows hpl_transform_pair emits for M points: min(num_points, M), or M when num_points <= 0."""

@@ -975,6 +975,49 @@ int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *flow, int64_
                        int min_points, int max_objects, int32_t *labels, int32_t *obj_info, float *obj_motion, int32_t *stats,
                        void *workspace, int64_t workspace_bytes, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Self-supervised loss (csrc/selfsup_loss.hip): Chamfer distance between the warped cloud pc1 + flow and pc2, plus the
+ * smoothness of the flow over pc1's k-nearest-neighbour graph, with the gradient by the flow.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_selfsup_loss for `batch` pairs of n1_total / n2_total points together and k neighbours, in bytes (monotone
+ * in all four); -1 for a batch outside 1 .. 64, k outside 0 .. 8, a count outside 0 .. 2^31 / 3 - 1 or k n1_total >= 2^31. */
+int64_t hpl_selfsup_loss_workspace_bytes(int batch, int64_t n1_total, int64_t n2_total, int k);
+/* pc1 (3, N1) and pc2 (3, N2) float32 SoA (row strides pc1_ld >= N1, pc2_ld >= N2); the flow of pc1's points through
+ * flow_sc / flow_sp exactly as hpl_rigid_fit reads it.  batch (1 .. 64) pairs: prefix1 / prefix2 (HOST, batch + 1 ints each
+ * from 0 to N1 / N2, non-decreasing, empty pairs allowed) travel in the kernel arguments.  k 1 .. 8, or 0 with w_smooth == 0
+ * (no graph search); w_chamfer, w_smooth finite and >= 0.
+ * Per pair, x_i point i of pc1, f_i its flow, p_i = x_i + f_i (per component, rounded once to float32), q_j point j of pc2.
+ * SEARCH: the arithmetic of hpl_knn_interp -- float32 d2 = (dx * dx + dy * dy) + dz * dz, no contraction, candidates in
+ * index order, an entry replaced only by a strictly smaller d2 (ties go to the smaller index), a d2 that is not below +inf
+ * (NaN included) never enters.  a(i): the nearest q to p_i.  b(j): the nearest p to q_j.  N(i): the k nearest x to x_i among
+ * the indices other than i (another index at the same position is a neighbour), nearest first; k_i = |N(i)| < k in a pair of
+ * fewer than k + 1 points.
+ * LOSS, float64 sums of the float32 inputs in a fixed order: C12 = (1 / N1) sum_i d2(p_i, q_a(i)) and C21 = (1 / N2) sum_j
+ * d2(q_j, p_b(j)) over the float32 d2 the search kept (a point without a neighbour adds 0); S = (1 / N1) sum_i (1 / k_i)
+ * sum_{n in N(i)} |f_i - f_n|^2, the differences in float64 (k_i = 0 adds 0; k = 0: S = 0).  A pair with N1 = 0 has all
+ * components 0, one with N2 = 0 has C12 = C21 = 0.  L = w_chamfer (C12 + C21) + w_smooth S (k = 0: the first product alone).
+ * loss [batch][4] float32: L, C12, C21, S, each rounded once.
+ * GRADIENT, the assignments a, b, N taken as constants, float64, rounded once: dflow [N1][3] point-major (or NULL: not
+ * computed), dL/df_i = w_chamfer [ (2 / N1)(p_i - q_a(i)) + (2 / N2) sum_{j: b(j) = i} (p_i - q_j) ]
+ *                   + w_smooth (2 / N1) [ (1 / k_i) sum_{n in N(i)} (f_i - f_n) + sum_{m: i in N(m)} (1 / k_m)(f_i - f_m) ]
+ * (k = 0: the first product alone); the sums over j and m run in ascending j / m order, each from 0, and join the point's own
+ * terms afterwards.  The graph is over positions alone: a non-finite flow spreads to the S of its pair and to the gradient of
+ * the points that list it, while a non-finite p_i or q_j is nobody's nearest point and adds 0 to C12 / C21.
+ * nn12 (N1), nn21 (N2), nbr (k, N1) int32 or NULL: a, b, N as indices into the packed arrays, -1 where absent.
+ * No floating-point atomic; a pair's outputs are the same bits alone, anywhere in a batch and beside other work.  Stream-
+ * ordered, a fixed number of launches whose sizes depend on N1, N2, batch and k alone (and on whether dflow is asked for), no
+ * copy back, no host synchronisation; no lane or workgroup waits for another.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_selfsup_loss_workspace_bytes(batch, N1, N2, k); dflow must not overlap pc1,
+ * flow or pc2.
+ * HPL_EINVAL before any launch (and without a device): batch or k out of range, k = 0 with w_smooth != 0; a weight that is
+ * negative, infinite or NaN; a prefix that does not start at 0 or decreases; a row stride below its count; flow strides < 1
+ * or overlapping; null pc1 / flow / prefixes / loss / workspace, null pc2 with N2 > 0; misaligned arrays; a workspace that is too small; a
+ * count >= 2^31 / 3 or k N1 >= 2^31; dflow overlapping an input.  N1 == 0 is a no-op. */
+int hpl_selfsup_loss(const float *pc1, int64_t pc1_ld, const float *flow, int64_t flow_sc, int64_t flow_sp, const float *pc2,
+                     int64_t pc2_ld, int batch, const int64_t *prefix1 /* HOST */, const int64_t *prefix2 /* HOST */, int k,
+                     float w_chamfer, float w_smooth, float *loss, float *dflow, int32_t *nn12, int32_t *nn21, int32_t *nbr,
+                     void *workspace, int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
