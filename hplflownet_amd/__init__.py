@@ -7,12 +7,13 @@ Public surface (mirrors the reference's operator interface for the path):
     rigid_refine                                                 (rigid motion from flow; flownet.py, ops.rigid_fit)
     segment_motion                                               (moving objects from flow; flownet.py, ops.motion_segment)
     selfsup_loss                                                 (Chamfer + smoothness loss; flownet.py, ops.selfsup_loss)
+    remove_ground                                                (fitted-plane ground removal; flownet.py, ops.ground_fit)
 The arithmetic lives in libhplbcl.so (csrc/*.hip, C ABI in include/hpl_bcl.h).
 """
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, Conv2dReLU, Conv3dReLU,  # noqa: F401
                   sparse_sum)
-from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, rigid_refine, segment_motion,  # noqa: F401
-                      selfsup_loss)
+from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, remove_ground, rigid_refine,  # noqa: F401
+                      segment_motion, selfsup_loss)
 from .lattice import GenerateDataUnsymmetric, to_reference_format  # noqa: F401
 
 __version__ = '0.1.0'

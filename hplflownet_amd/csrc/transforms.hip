@@ -18,6 +18,7 @@
 // The valid points in index order (allow_less_points, num_points <= 0) are a rocPRIM select of the flags.  Which of the two
 // is emitted, and how many, is decided on the device from the valid count: one enqueue, no host round trip.
 #include "common.h"
+#include "philox.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
@@ -30,27 +31,7 @@ namespace {
 constexpr int TT = 256;
 constexpr unsigned long long INVALID_KEY = ~0ull;        // above every 63-bit key
 
-struct u4 { uint32_t x, y, z, w; };
-
-__host__ __device__ inline uint32_t mulhilo(uint32_t a, uint32_t b, uint32_t *hi) {
-    const uint64_t p = (uint64_t)a * b;
-    *hi = (uint32_t)(p >> 32);
-    return (uint32_t)p;
-}
-
-// Philox4x32-10 (Salmon et al., SC'11): 10 rounds, key bumped between rounds.
-__host__ __device__ inline u4 philox4x32_10(u4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        uint32_t hi0, hi1;
-        const uint32_t lo0 = mulhilo(0xD2511F53u, c.x, &hi0);
-        const uint32_t lo1 = mulhilo(0xCD9E8D57u, c.z, &hi1);
-        c = u4{hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0};
-    }
-    return c;
-}
-
+// (Philox4x32-10 itself: philox.h)
 __device__ inline u4 draw(const hpl_transform_params &P, int64_t i, uint32_t purpose) {
     return philox4x32_10(u4{(uint32_t)i, (uint32_t)P.counter, (uint32_t)(P.counter >> 32), purpose},
                          (uint32_t)P.seed, (uint32_t)(P.seed >> 32));

@@ -334,9 +334,27 @@ class FlyingThings3DSubset(_PairFolder):
 class KITTI(_PairFolder):
     canonical = 200
 
-    def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None):
+    #: the keyword arguments of flownet.remove_ground that `ground` may hold
+    GROUND_KEYS = ('up', 'max_tilt_deg', 'hyps', 'tau', 'refine', 'cut')
+
+    def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None, ground=None):
+        """remove_ground: True -- the reference's rule, a correspondence is dropped when y < -1.4 in both clouds --, False, or
+        'plane': the same pair rule on a plane fitted to each cloud on the device (flownet.remove_ground(corr=True, seed=0,
+        call=<frame number>, **ground), DESIGN.md §21: a frame's result does not depend on the order of reading)."""
+        from . import _lib
         super(KITTI, self).__init__(transform, device)
         self.root = os.path.join(data_root, 'KITTI_processed_occ_final')
+        if remove_ground not in (True, False, 'plane'):
+            raise _lib.HplError('KITTI: remove_ground = %r (True, False or \'plane\')' % (remove_ground,))
+        self.ground = dict(ground or {})
+        if remove_ground == 'plane':
+            if torch.device(device).type != 'cuda':
+                raise _lib.HplError('KITTI: remove_ground=\'plane\' fits on the device, got device %s (there is no CPU fallback)' % (device,))
+            bad = sorted(set(self.ground) - set(self.GROUND_KEYS))
+            if bad:
+                raise _lib.HplError('KITTI: ground holds %s, got %s' % (', '.join(self.GROUND_KEYS), bad))
+        elif self.ground:
+            raise _lib.HplError('KITTI: ground applies to remove_ground=\'plane\'')
         self.remove_ground = remove_ground
         dirs = _leaf_dirs(self.root)
         self._found = len(dirs)
@@ -363,7 +381,14 @@ class KITTI(_PairFolder):
     def load(self, path):
         pc1 = np.load(os.path.join(path, 'pc1.npy'))
         pc2 = np.load(os.path.join(path, 'pc2.npy'))
-        if self.remove_ground:
+        if self.remove_ground == 'plane':
+            from .flownet import remove_ground
+            name = os.path.basename(path)
+            frame = int(name) if name.isdigit() else self.samples.index(path)
+            t1, t2 = (torch.from_numpy(np.ascontiguousarray(p[:, :3].T, dtype=np.float32)).to(self.device) for p in (pc1, pc2))
+            keep = remove_ground(t1, t2, corr=True, return_mask=True, seed=0, call=frame, **self.ground)[-1][0]
+            pc1, pc2 = pc1[keep], pc2[keep]
+        elif self.remove_ground:
             keep = ~((pc1[:, 1] < -1.4) & (pc2[:, 1] < -1.4))
             pc1, pc2 = pc1[keep], pc2[keep]
         return pc1, pc2

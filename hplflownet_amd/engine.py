@@ -718,6 +718,20 @@ def parse_args(argv=None):
                     help='--loss selfsup: weight of the Chamfer term (finite and >= 0, default 1)')
     ap.add_argument('--selfsup-smooth-weight', type=float, default=None, metavar='W',
                     help='--loss selfsup: weight of the smoothness term (finite and >= 0, default 1)')
+    ap.add_argument('--ground', default='threshold', choices=['threshold', 'plane'],
+                    help='--dataset KITTI: how the reader removes the ground: threshold -- the reference\'s rule, a correspondence '
+                         'with y < -1.4 in both clouds is dropped (default) --, or plane: the same pair rule on a plane fitted to '
+                         'each cloud on the device (DESIGN.md §21)')
+    ap.add_argument('--ground-tau', type=float, default=None, metavar='TAU',
+                    help='--ground plane: inlier distance of the fit in metres (finite and > 0, default 0.1)')
+    ap.add_argument('--ground-cut', type=float, default=None, metavar='C',
+                    help='--ground plane: a point at most C metres above the plane is ground (finite and >= 0, default 0.3)')
+    ap.add_argument('--ground-hyps', type=int, default=None, metavar='H',
+                    help='--ground plane: three-point hypotheses per cloud (1 .. 1024, default 256)')
+    ap.add_argument('--ground-tilt', type=float, default=None, metavar='DEG',
+                    help='--ground plane: largest tilt of the plane\'s normal from --ground-up in degrees (0 <= DEG < 90, default 20)')
+    ap.add_argument('--ground-up', type=float, nargs=3, default=None, metavar=('X', 'Y', 'Z'),
+                    help='--ground plane: the up direction (finite, not zero; default 0 1 0, KITTI\'s camera frame as the reader stores it)')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
@@ -767,6 +781,24 @@ def parse_args(argv=None):
     a.selfsup = {'k': 8 if a.selfsup_k is None else a.selfsup_k,
                  'w_chamfer': 1.0 if a.selfsup_chamfer_weight is None else a.selfsup_chamfer_weight,
                  'w_smooth': 1.0 if a.selfsup_smooth_weight is None else a.selfsup_smooth_weight} if on else None
+    on = a.ground == 'plane'
+    if on and a.dataset != 'KITTI':
+        ap.error('--ground applies to --dataset KITTI')
+    if a.ground_tau is not None and (not on or not 0 < a.ground_tau < float('inf')):
+        ap.error('--ground-tau takes a finite value > 0 and applies to --ground plane')
+    if a.ground_cut is not None and (not on or not 0 <= a.ground_cut < float('inf')):
+        ap.error('--ground-cut takes a finite value >= 0 and applies to --ground plane')
+    if a.ground_hyps is not None and (not on or not 1 <= a.ground_hyps <= 1024):
+        ap.error('--ground-hyps takes 1 .. 1024 and applies to --ground plane')
+    if a.ground_tilt is not None and (not on or not 0 <= a.ground_tilt < 90):
+        ap.error('--ground-tilt takes 0 <= DEG < 90 and applies to --ground plane')
+    if a.ground_up is not None and (not on or not all(abs(x) < float('inf') for x in a.ground_up) or not any(a.ground_up)):
+        ap.error('--ground-up takes three finite numbers, not all zero, and applies to --ground plane')
+    a.ground_fit = {'tau': 0.1 if a.ground_tau is None else a.ground_tau,
+                    'cut': 0.3 if a.ground_cut is None else a.ground_cut,
+                    'hyps': 256 if a.ground_hyps is None else a.ground_hyps,
+                    'max_tilt_deg': 20.0 if a.ground_tilt is None else a.ground_tilt,
+                    'up': (0.0, 1.0, 0.0) if a.ground_up is None else tuple(a.ground_up)} if on else None
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -885,7 +917,8 @@ def _real_data(a, tr, dev, rank, world):
         process = lambda less: data_mod.ProcessData(DATA_PROCESS, a.points, less, seed=0)                       # noqa: E731
         augment = lambda: data_mod.Augmentation(AUG_TOGETHER, AUG_PC2, DATA_PROCESS, a.points, False, seed=1 + rank)  # noqa: E731
     if a.dataset == 'KITTI':                        # evaluation only in the reference
-        val = data_mod.KITTI(process(True), a.data_root, device=dev, calib_dir=a.kitti_calib)
+        val = data_mod.KITTI(process(True), a.data_root, device=dev, calib_dir=a.kitti_calib,
+                             remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit)
         train = None
         if a.kitti_calib is None:
             log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')

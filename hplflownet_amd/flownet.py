@@ -664,6 +664,75 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
     return labels, info, motion, stats, fits
 
 
+# ----------------------------------------------------------------------------- ground removal
+def _clouds(x, who, what):
+    """The (3, N_b) clouds of a (3, N) tensor, a (B, 3, N) tensor or a list of (3, N_b) / (1, 3, N_b) tensors."""
+    if isinstance(x, (list, tuple)):
+        out = [c[0] if torch.is_tensor(c) and c.dim() == 3 else c for c in x]
+    elif torch.is_tensor(x) and x.dim() == 3:
+        out = [x[b] for b in range(x.shape[0])]
+    else:
+        out = [x]
+    if not out or any(not torch.is_tensor(c) or c.dim() != 2 or c.shape[0] != 3 for c in out):
+        raise _lib.HplError('%s: %s is a (3, N) or (B, 3, N) tensor or a list of (3, N_b) tensors' % (who, what))
+    return out
+
+
+def remove_ground(pc1, pc2, sf=None, corr=True, return_mask=False, **kw):
+    """The pair(s) without their ground, by ONE ops.ground_fit call over the 2 B clouds -- the pc1 clouds first, then the pc2
+    clouds -- (DESIGN.md §21): every cloud gets its own fitted plane.  pc1 / pc2 / sf in the forms rigid_refine takes: (3, N)
+    tensors (one pair), (B, 3, N) tensors, or lists of B (3, N_b) tensors.  kw: up, max_tilt_deg, hyps, tau, refine, cut, seed,
+    call of ops.ground_fit.
+    corr=True (the clouds of a pair correspond point to point, so they hold as many points): the reference's pair rule on the
+    fitted planes -- index i is dropped when it is ground in BOTH clouds; pc1, pc2 and sf are indexed together.
+    corr=False: each cloud is compacted on its own through keep_idx and the kept counts; sf follows pc1.
+    One read-back (corr=True: the pair masks; corr=False: the kept counts), as the device transforms make one.
+    -> (pc1 list of (3, K_b), pc2 list, sf list or None, planes (2, B, 4), stats (2, B, 4) int32[, masks]): return_mask (with
+    corr=True) appends the pairs' keep masks as host numpy bool arrays."""
+    who = 'remove_ground'
+    if 'return_votes' in kw or 'return_height' in kw:
+        raise _lib.HplError('%s takes the fitting arguments of ops.ground_fit, not its optional outputs' % who)
+    c1, c2 = _clouds(pc1, who, 'pc1'), _clouds(pc2, who, 'pc2')
+    fl = _clouds(sf, who, 'sf') if sf is not None else None
+    B = len(c1)
+    if len(c2) != B or (fl is not None and (len(fl) != B or any(f.shape[1] != c.shape[1] for f, c in zip(fl, c1)))):
+        raise _lib.HplError('%s: pc1, pc2 and sf hold as many clouds, and sf as many points as pc1' % who)
+    if corr and any(a.shape[1] != b.shape[1] for a, b in zip(c1, c2)):
+        raise _lib.HplError('%s: corr=True takes clouds that correspond point to point (as many points in pc1 and pc2)' % who)
+    if return_mask and not corr:
+        raise _lib.HplError('%s: return_mask comes with corr=True' % who)
+    if not 1 <= 2 * B <= 64:
+        raise _lib.HplError('%s: %d pairs (1 .. 32 a call)' % (who, B))
+    prefix = [0]
+    for c in c1 + c2:
+        prefix.append(prefix[-1] + int(c.shape[1]))
+    pc = torch.cat(c1 + c2, dim=1)
+    plane, stats, ground, keep = ops.ground_fit(pc, prefix=prefix, **kw)
+    n1 = prefix[B]
+    o1, o2, of, masks = [], [], ([] if fl is not None else None), []
+    if corr:
+        host = (~(ground[:n1].bool() & ground[n1:].bool())).cpu().numpy()       # the one read-back
+        for b in range(B):
+            m = host[prefix[b]:prefix[b + 1]]
+            masks.append(m)
+            idx = torch.from_numpy(m.nonzero()[0]).to(pc.device)
+            o1.append(c1[b].index_select(1, idx))
+            o2.append(c2[b].index_select(1, idx))
+            if fl is not None:
+                of.append(fl[b].index_select(1, idx))
+    else:
+        kept = stats[:, 3].cpu().tolist()                                       # the one read-back
+        for b in range(B):
+            i1 = keep[prefix[b]:prefix[b] + kept[b]].long() - prefix[b]
+            i2 = keep[prefix[B + b]:prefix[B + b] + kept[B + b]].long() - prefix[B + b]
+            o1.append(c1[b].index_select(1, i1))
+            o2.append(c2[b].index_select(1, i2))
+            if fl is not None:
+                of.append(fl[b].index_select(1, i1))
+    res = (o1, o2, of, plane.view(2, B, 4), stats.view(2, B, 4))
+    return res + (masks,) if return_mask else res
+
+
 # ----------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(flow, pc1, pc2, k=8, w_chamfer=1.0, w_smooth=1.0):
     """The self-supervised loss of a forward's flow in ONE ops.selfsup_loss call: Chamfer distance between

@@ -600,6 +600,104 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
     return labels, info, motion, stats
 
 
+# --------------------------------------------------------------------------- ground removal
+_GROUND_WS = {}
+
+
+def _ground_workspace(device, st, nbytes):
+    """Per-(device, stream) scratch of hpl_ground_fit, one buffer per size class (the next power of two), as
+    _rigid_workspace keeps them."""
+    size = 1 << max(12, int(nbytes - 1).bit_length())
+    key = (device, st, size)
+    ws = _GROUND_WS.get(key)
+    if ws is None:
+        ws = _GROUND_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
+    return ws
+
+
+def ground_min_cos(max_tilt_deg):
+    """The float32 cosine hpl_ground_fit takes for a largest tilt in degrees (0 <= tilt < 90)."""
+    import math
+    import struct
+    t = float(max_tilt_deg)
+    if not 0 <= t < 90:
+        raise _lib.HplError('ground_fit: max_tilt_deg = %r (0 <= tilt < 90 degrees)' % (max_tilt_deg,))
+    return struct.unpack('f', struct.pack('f', math.cos(math.radians(t))))[0]
+
+
+def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0.1, refine=2, cut=0.3, seed=0, call=0,
+               return_votes=False, return_height=False):
+    """hpl_ground_fit on the current stream: per cloud the ground plane n . x + d = 0 by RANSAC (hyps
+    three-point hypotheses from the counter-based stream (seed, call); a hypothesis whose normal tilts more than max_tilt_deg
+    from `up` is no candidate; a point votes within tau of the plane), refined by `refine` least-squares rounds on its inliers,
+    and every point classified by its signed height: ground when it is finite and at most `cut` above the plane.  pc (3, N)
+    float32 (rows may be views of a wider buffer); prefix (host sequence of B + 1 ints from 0 to N): B <= 64 clouds, each with
+    its own plane.
+    -> (plane (B, 4) float32 = (n, d), stats (B, 4) int32 = (status, winning hypothesis, its votes, kept count), ground (N,)
+    uint8, keep_idx (N,) int32: per cloud from prefix[b] on the packed indices of its kept points, ascending, then -1
+    [, votes (B, hyps) int32, -1 an invalid hypothesis][, height (N,) float32, NaN at a non-finite point]).  status 0 (no valid
+    hypothesis, fewer than 3 points): plane 0, nothing ground, every index kept.  No autograd, no host synchronisation."""
+    for name, v, lo, hi in (('hyps', hyps, 1, 1024), ('refine', refine, 0, 8)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise _lib.HplError('ground_fit: %s = %r (an int in %d .. %d)' % (name, v, lo, hi))
+    tau, cut = float(tau), float(cut)
+    if not (tau > 0 and tau < float('inf')):
+        raise _lib.HplError('ground_fit: tau = %r (finite and > 0)' % (tau,))
+    if not (cut >= 0 and cut < float('inf')):
+        raise _lib.HplError('ground_fit: cut = %r (finite and >= 0)' % (cut,))
+    min_cos = ground_min_cos(max_tilt_deg)
+    try:
+        upv = [float(x) for x in up]
+    except TypeError:
+        upv = []
+    if len(upv) != 3 or not all(abs(x) < float('inf') for x in upv) or not any(upv):
+        raise _lib.HplError('ground_fit: up = %r (three finite numbers, not all zero)' % (up,))
+    for name, v in (('seed', seed), ('call', call)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 64:
+            raise _lib.HplError('ground_fit: %s = %r (an int in 0 .. 2^64 - 1)' % (name, v))
+    pc, pc_ld = _soa3(pc, 'pc', 'ground_fit')
+    N, dev = pc.shape[1], pc.device
+    pp = [0, N] if prefix is None else [int(x) for x in prefix]
+    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != N or any(b < a for a, b in zip(pp, pp[1:])):
+        raise _lib.HplError('ground_fit: the prefix holds B + 1 <= 65 non-decreasing entries from 0 to N = %d, got %s' % (N, pp))
+    B = len(pp) - 1
+    lib = _lib.load()
+    votes = height = None
+    if N == 0:                                   # nothing to launch: every cloud is empty
+        plane = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+        stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+        stats[:, 1] = -1
+        ground = torch.zeros(0, dtype=torch.uint8, device=dev)
+        keep = torch.zeros(0, dtype=torch.int32, device=dev)
+        if return_votes:
+            votes = torch.full((B, hyps), -1, dtype=torch.int32, device=dev)
+        if return_height:
+            height = torch.zeros(0, dtype=torch.float32, device=dev)
+    else:
+        plane = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        ground = torch.empty(N, dtype=torch.uint8, device=dev)
+        keep = torch.empty(N, dtype=torch.int32, device=dev)
+        if return_votes:
+            votes = torch.empty((B, hyps), dtype=torch.int32, device=dev)
+        if return_height:
+            height = torch.empty(N, dtype=torch.float32, device=dev)
+        nbytes = lib.hpl_ground_fit_workspace_bytes(B, N, hyps)
+        if nbytes < 0:
+            raise _lib.HplError('ground_fit: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (B, N))
+        st = stream()
+        ws = _ground_workspace(dev, st, nbytes)
+        check(lib.hpl_ground_fit(pc.data_ptr(), pc_ld, B, (ctypes.c_int64 * (B + 1))(*pp), (ctypes.c_float * 3)(*upv), min_cos,
+                                 hyps, tau, refine, cut, seed, call, plane.data_ptr(), stats.data_ptr(), ptr(votes), ptr(height),
+                                 ground.data_ptr(), keep.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_ground_fit')
+    res = (plane, stats, ground, keep)
+    if return_votes:
+        res += (votes,)
+    if return_height:
+        res += (height,)
+    return res
+
+
 # --------------------------------------------------------------------------- self-supervised loss
 _SELFSUP_WS = {}
 

@@ -1018,6 +1018,58 @@ int hpl_selfsup_loss(const float *pc1, int64_t pc1_ld, const float *flow, int64_
                      float w_chamfer, float w_smooth, float *loss, float *dflow, int32_t *nn12, int32_t *nn21, int32_t *nbr,
                      void *workspace, int64_t workspace_bytes, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Ground removal (csrc/ground_fit.hip): per cloud the ground plane by RANSAC with a tilt gate against a given up vector,
+ * refined by least squares on its inliers; every point classified by its signed height over the plane, and the indices of
+ * the points that are not ground, stably compacted.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_ground_fit for `batch` clouds of n_total points together and `hyps` hypotheses, in bytes (monotone in all
+ * three); -1 for a batch outside 1 .. 64, hyps outside 1 .. 1024 or n_total outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_ground_fit_workspace_bytes(int batch, int64_t n_total, int hyps);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N).  batch (1 .. 64) clouds: prefix (HOST, batch + 1 ints from 0 to N,
+ * non-decreasing, empty clouds allowed) travels in the kernel arguments.  up (HOST, 3 floats, finite, not zero): the direction
+ * the ground's normal points to, of any length.  min_cos in (0, 1]: the cosine of the largest allowed tilt between normal and
+ * up.  hyps 1 .. 1024, refine 0 .. 8, tau > 0 finite (inlier distance), cut >= 0 finite.  seed / call: the random stream.
+ * Arithmetic per cloud of n points x_0 .. x_{n-1} (indices within the cloud): float64 throughout, computed from the float32
+ * inputs (up, min_cos, tau, cut promoted too), every operation rounded once, no contraction; parentheses give the order.
+ * VALID: a point whose three coordinates are finite.
+ * HYPOTHESIS h (0 .. hyps - 1): r = philox4x32_10(counter = (h, call lo, call hi, 16), key = (seed lo, seed hi));
+ * i_k = (uint64(r[k]) * n) >> 32 for k = 0, 1, 2 -- a function of h, n, seed and call alone.  a = x_{i_0}, u = x_{i_1} - a,
+ * v = x_{i_2} - a, m = u x v (m_x = u_y v_z - u_z v_y, m_y = u_z v_x - u_x v_z, m_z = u_x v_y - u_y v_x),
+ * q = (m_x m_x + m_y m_y) + m_z m_z, c = (m_x up_x + m_y up_y) + m_z up_z, uu the form of q over up; if c < 0, m and c are
+ * negated.  The hypothesis is valid when n >= 3, the three points are valid, q > 0 and finite, and
+ * c c >= ((min_cos min_cos) uu) q.
+ * VOTE: s_i = (m_x (x_i - a_x) + m_y (y_i - a_y)) + m_z (z_i - a_z); point i votes for h when it is valid and
+ * s_i s_i <= (tau tau) q.  votes [batch][hyps] int32 or NULL: the count, -1 for an invalid hypothesis.
+ * WINNER: the most votes, the smallest h among equals: n = m / sqrt(q) per component, d = -((n_x a_x + n_y a_y) + n_z a_z).
+ * A cloud without a valid hypothesis has status 0: plane all 0, nothing ground, height 0 at every point, keep_idx every index,
+ * stats (0, -1, 0, n).
+ * REFINE, `refine` rounds: the inliers of the current float64 plane are the valid points with |h_i| <= tau,
+ * h_i = ((n_x x_i + n_y y_i) + n_z z_i) + d.  With dp = x_i - a (the winner's a), W the inlier count, S1 = sum dp and
+ * S2 = sum dp dp^T (float64, a fixed order: per workgroup of 1024 consecutive points a tree, then the workgroups' partials in 16
+ * strided runs in index order, then the runs in order): mu = S1 / W, C_ij = S2_ij - (W mu_i) mu_j; the new normal is the unit
+ * eigenvector of C's smallest eigenvalue (cyclic Jacobi), negated if its c < 0; d = -((n_x (a_x + mu_x) + n_y (a_y + mu_y))
+ * + n_z (a_z + mu_z)).  A round with W < 3, a non-finite sum or result, or a normal with c c < ((min_cos min_cos) uu) (n . n)
+ * ends the refinement and keeps the plane it started from.
+ * CLASSIFY: plane [batch][4] float32 = (n, d), each rounded once; the classification reads those float32 values back, promoted
+ * to float64, so it is reproducible from `plane` alone.  height (N) float32 or NULL: h_i rounded once, NaN for an invalid
+ * point.  ground (N) uint8 or NULL: 1 when the point is valid and h_i <= cut (everything at or under the surface plus cut), else
+ * 0: invalid points are kept.  keep_idx (N) int32 or NULL: for each cloud from prefix[b] on, the indices into the packed
+ * arrays of its points that are not ground, ascending; the rest of the cloud's range -1.  stats [batch][4] int32: status (1 a
+ * fit, 0 none), the winning h, its votes, the kept count.
+ * Counts are integers (integer atomic adds commute); no floating-point atomic: a cloud's outputs are the same bits alone,
+ * anywhere in a batch and beside other work.  Stream-ordered, 6 + 2 refine launches (5 + 2 refine without keep_idx) whose sizes
+ * depend on N, batch, hyps and refine alone, no copy back, no host synchronisation; no lane or workgroup waits for another.
+ * workspace: DEVICE, 8-byte aligned, >= hpl_ground_fit_workspace_bytes(batch, N, hyps).
+ * HPL_EINVAL before any launch (and without a device): batch, hyps, refine, tau, cut or min_cos out of range or NaN; an up
+ * that is zero or not finite; a prefix that does not start at 0 or decreases; pc_ld < N; null pc / prefix / up / plane / stats
+ * / workspace; misaligned arrays; a workspace that is too small; N >= 2^31 / 3.  N == 0 is a no-op. */
+int hpl_ground_fit(const float *pc, int64_t pc_ld, int batch, const int64_t *prefix /* HOST */, const float *up /* HOST, 3 */,
+                   float min_cos, int hyps, float tau, int refine, float cut, uint64_t seed, uint64_t call,
+                   float *plane /* [batch][4] */, int32_t *stats /* [batch][4] */, int32_t *votes /* [batch][hyps] or NULL */,
+                   float *height /* (N) or NULL */, uint8_t *ground /* (N) or NULL */, int32_t *keep_idx /* (N) or NULL */,
+                   void *workspace, int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
