@@ -21,7 +21,7 @@
 // atomic: the bits depend on the cloud alone, not on its place in a batch or on what else the device runs.
 //
 // The arithmetic is part of the interface (include/hpl_bcl.h; tests/ground_oracle.py restates it in numpy).
-#include "common.h"
+#include "cloud_common.h"
 #include "philox.h"
 
 #include <math.h>
@@ -30,7 +30,6 @@ using namespace hpl;
 
 namespace {
 
-constexpr int GF_MAX_BATCH = 64;
 constexpr int GF_MAX_HYPS = 1024;
 constexpr int GF_MAX_REFINE = 8;
 constexpr int GF_BLOCK = 256;
@@ -59,15 +58,13 @@ struct GroundArgs {
     double tau, tau2, cut;
     uint32_t seed_lo, seed_hi, call_lo, call_hi;
     int32_t batch, hyps, last;
-    int32_t pprefix[GF_MAX_BATCH + 1];      // points of clouds 0 .. b-1 (N < 2^31 / 3)
-    int32_t bprefix[GF_MAX_BATCH + 1];      // workgroups of clouds 0 .. b-1
+    int32_t pprefix[CLOUD_MAX_BATCH + 1];      // points of clouds 0 .. b-1 (N < 2^31 / 3)
+    int32_t bprefix[CLOUD_MAX_BATCH + 1];      // workgroups of clouds 0 .. b-1
 };
 
+// the cloud of workgroup blk, in a scalar register
 __device__ __forceinline__ int cloud_of(const GroundArgs &a, int blk) {
-    int b = 0;                   // the last cloud whose first workgroup is <= blk (empty clouds own no workgroup)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) b = (b + s < a.batch && a.bprefix[b + s] <= blk) ? b + s : b;
-    return __builtin_amdgcn_readfirstlane(b);
+    return __builtin_amdgcn_readfirstlane(group_of(a.bprefix, a.batch, blk));
 }
 
 __device__ __forceinline__ bool load_point(const GroundArgs &a, int64_t i, double *p) {
@@ -220,69 +217,15 @@ __global__ void __launch_bounds__(GF_BLOCK) k_ground_reduce(const GroundArgs a) 
         acc[4] += dx * dx; acc[5] += dx * dy; acc[6] += dx * dz;
         acc[7] += dy * dy; acc[8] += dy * dz; acc[9] += dz * dz;
     }
-#pragma unroll
-    for (int k = 0; k < GF_SUMS; ++k) red[k][t] = acc[k];
-    __syncthreads();
-    for (int w = GF_BLOCK / 2; w > 0; w >>= 1) {
-        if (t < w) {
-#pragma unroll
-            for (int k = 0; k < GF_SUMS; ++k) red[k][t] += red[k][t + w];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(red, acc, t);
     if (t < GF_SUMS) a.partials[(int64_t)blk * GF_SUMS + t] = red[t][0];
-}
-
-// One rotation of the cyclic Jacobi sweep of the symmetric 3x3 A (eigenvectors accumulate in the columns of V).
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate3(double (&A)[3][3], double (&V)[3][3]) {
-    const double apq = A[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-    const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));     // (theta = +-inf: 0)
-    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {                // A <- A J
-        const double akp = A[k][P], akq = A[k][Q];
-        A[k][P] = c * akp - s * akq;
-        A[k][Q] = s * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {                // A <- J^T A
-        const double apk = A[P][k], aqk = A[Q][k];
-        A[P][k] = c * apk - s * aqk;
-        A[Q][k] = s * apk + c * aqk;
-    }
-    A[P][Q] = 0.0;
-    A[Q][P] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - s * vkq;
-        V[k][Q] = s * vkp + c * vkq;
-    }
 }
 
 __global__ void __launch_bounds__(GF_BLOCK) k_ground_solve(const GroundArgs a) {
     __shared__ double run[GF_RUNS][GF_SUMS];
     __shared__ double tot[GF_SUMS];
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int g = t >> 4, k = t & 15;
-    const int b0 = a.bprefix[b], nb = a.bprefix[b + 1] - b0;
-    if (k < GF_SUMS) {
-        double s = 0.0;
-#pragma unroll 4
-        for (int j = g; j < nb; j += GF_RUNS) s += a.partials[(int64_t)(b0 + j) * GF_SUMS + k];
-        run[g][k] = s;
-    }
-    __syncthreads();
-    if (t < GF_SUMS) {
-        double v = 0.0;
-#pragma unroll
-        for (int r = 0; r < GF_RUNS; ++r) v += run[r][t];
-        tot[t] = v;
-    }
-    __syncthreads();
+    fold_partials<GF_SUMS, GF_RUNS, GF_BLOCK>(a.partials, a.bprefix[b], a.bprefix[b + 1] - a.bprefix[b], run, tot, t);
     if (t != 0) return;
 
     double *st = a.state + (int64_t)b * GF_STATE;
@@ -294,30 +237,21 @@ __global__ void __launch_bounds__(GF_BLOCK) k_ground_solve(const GroundArgs a) {
         double nn[3] = {0, 0, 0}, d = 0.0;
         if (ok) {
             const double mu[3] = {tot[1] / W, tot[2] / W, tot[3] / W};
-            double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+            double A[3][3], V[3][3];
             A[0][0] = tot[4] - (W * mu[0]) * mu[0];
             A[0][1] = A[1][0] = tot[5] - (W * mu[0]) * mu[1];
             A[0][2] = A[2][0] = tot[6] - (W * mu[0]) * mu[2];
             A[1][1] = tot[7] - (W * mu[1]) * mu[1];
             A[1][2] = A[2][1] = tot[8] - (W * mu[1]) * mu[2];
             A[2][2] = tot[9] - (W * mu[2]) * mu[2];
-            for (int sweep = 0; sweep < GF_SWEEPS; ++sweep) {
-                double off = 0.0, all = 0.0;
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) {
-                        all += A[i][j] * A[i][j];
-                        if (i != j) off += A[i][j] * A[i][j];
-                    }
-                if (!(off > 1e-32 * all)) break;         // (also a zero or non-finite matrix)
-                jacobi_rotate3<0, 1>(A, V);
-                jacobi_rotate3<0, 2>(A, V);
-                jacobi_rotate3<1, 2>(A, V);
-            }
+            jacobi_eigen(A, V, GF_SWEEPS);
             int best = 0;                                // the smallest eigenvalue; ties go to the smaller index
+            double least = A[0][0];
 #pragma unroll
-            for (int i = 1; i < 3; ++i) best = A[i][i] < A[best][best] ? i : best;
+            for (int i = 1; i < 3; ++i) {
+                best = A[i][i] < least ? i : best;
+                least = A[i][i] < least ? A[i][i] : least;
+            }
 #pragma unroll
             for (int i = 0; i < 3; ++i) nn[i] = best == 0 ? V[i][0] : best == 1 ? V[i][1] : V[i][2];
             const double r = sqrt(dot3(nn, nn));
@@ -441,37 +375,35 @@ __global__ void __launch_bounds__(GF_BLOCK) k_ground_emit(const GroundArgs a) {
     }
 }
 
-constexpr int64_t GF_MAX_POINTS = (((int64_t)1 << 31) + 2) / 3;     // N >= 2^31 / 3 is refused: 3 N elements pass 32 bits
-
-int64_t align256(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
-struct Layout { int64_t hyp, state, partials, cnt, blockoff, total; };
-
-Layout layout(int batch, int64_t n_total, int hyps) {
-    const int64_t blocks = cdiv(n_total, GF_SPAN) + batch;
-    Layout l;
-    l.hyp = 0;
-    l.state = l.hyp + align256((int64_t)sizeof(double) * batch * hyps * GF_REC);
-    l.partials = l.state + align256((int64_t)sizeof(double) * batch * GF_STATE);
-    l.cnt = l.partials + align256((int64_t)sizeof(double) * blocks * GF_SUMS);
-    l.blockoff = l.cnt + align256((int64_t)sizeof(int32_t) * batch * hyps);
-    l.total = l.blockoff + align256((int64_t)sizeof(int32_t) * blocks);
-    return l;
-}
+// workspace: the hypotheses' records | the clouds' state | the reduce partials | the votes | the kept counts per workgroup
+struct Layout {                  // byte offsets
+    int64_t hyp, state, partials, cnt, blockoff, bytes;
+    Layout(int batch, int64_t n_total, int hyps) {
+        const int64_t blocks = cdiv(n_total, GF_SPAN) + batch;
+        Carver c;
+        hyp = c.take((int64_t)sizeof(double) * batch * hyps * GF_REC);
+        state = c.take((int64_t)sizeof(double) * batch * GF_STATE);
+        partials = c.take((int64_t)sizeof(double) * blocks * GF_SUMS);
+        cnt = c.take((int64_t)sizeof(int32_t) * batch * hyps);
+        blockoff = c.take((int64_t)sizeof(int32_t) * blocks);
+        bytes = c.bytes;
+    }
+};
 
 }  // namespace
 
 extern "C" int64_t hpl_ground_fit_workspace_bytes(int batch, int64_t n_total, int hyps) {
-    if (batch < 1 || batch > GF_MAX_BATCH || n_total < 0 || n_total >= GF_MAX_POINTS || hyps < 1 || hyps > GF_MAX_HYPS) return -1;
-    return layout(batch, n_total, hyps).total;
+    if (batch < 1 || batch > CLOUD_MAX_BATCH || n_total < 0 || n_total >= CLOUD_MAX_POINTS || hyps < 1 || hyps > GF_MAX_HYPS) return -1;
+    return Layout(batch, n_total, hyps).bytes;
 }
 
 extern "C" int hpl_ground_fit(const float *pc, int64_t pc_ld, int batch, const int64_t *prefix, const float *up, float min_cos,
                               int hyps, float tau, int refine, float cut, uint64_t seed, uint64_t call, float *plane,
                               int32_t *stats, int32_t *votes, float *height, uint8_t *ground, int32_t *keep_idx, void *workspace,
                               int64_t workspace_bytes_, hplStream stream) {
+    const char *const op = "hpl_ground_fit";
     HPL_REQUIRE(pc && prefix && up && plane && stats && workspace, "hpl_ground_fit: null pointer");
-    HPL_REQUIRE(batch >= 1 && batch <= GF_MAX_BATCH, "hpl_ground_fit: batch %d (1 .. %d)", batch, GF_MAX_BATCH);
+    HPL_CLOUD_CHECK(check_batch(op, batch));
     HPL_REQUIRE(hyps >= 1 && hyps <= GF_MAX_HYPS, "hpl_ground_fit: hyps = %d (1 .. %d)", hyps, GF_MAX_HYPS);
     HPL_REQUIRE(refine >= 0 && refine <= GF_MAX_REFINE, "hpl_ground_fit: refine = %d (0 .. %d)", refine, GF_MAX_REFINE);
     HPL_REQUIRE(tau > 0.f && isfinite(tau), "hpl_ground_fit: tau must be finite and > 0");
@@ -479,36 +411,22 @@ extern "C" int hpl_ground_fit(const float *pc, int64_t pc_ld, int batch, const i
     HPL_REQUIRE(min_cos > 0.f && min_cos <= 1.f, "hpl_ground_fit: min_cos must be in (0, 1]");
     const double uu = ((double)up[0] * (double)up[0] + (double)up[1] * (double)up[1]) + (double)up[2] * (double)up[2];
     HPL_REQUIRE(isfinite(up[0]) && isfinite(up[1]) && isfinite(up[2]) && uu > 0.0, "hpl_ground_fit: up must be finite and not zero");
-    HPL_REQUIRE(prefix[0] == 0, "hpl_ground_fit: the prefix must start at 0");
-    for (int b = 0; b < batch; ++b)
-        HPL_REQUIRE(prefix[b + 1] >= prefix[b], "hpl_ground_fit: the prefix decreases at cloud %d", b);
+    HPL_CLOUD_CHECK(check_prefix(op, "the prefix", "cloud", prefix, batch));
     const int64_t N = prefix[batch];
-    HPL_REQUIRE(N < GF_MAX_POINTS, "hpl_ground_fit: %lld points pass the 32-bit element limit (N < 2^31 / 3)", (long long)N);
-    HPL_REQUIRE(pc_ld >= N, "hpl_ground_fit: row stride %lld below %lld points", (long long)pc_ld, (long long)N);
-    const Layout l = layout(batch, N, hyps);
-    HPL_REQUIRE(workspace_bytes_ >= l.total, "hpl_ground_fit: workspace of %lld bytes, needs %lld", (long long)workspace_bytes_,
-                (long long)l.total);
-    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(plane) | reinterpret_cast<uintptr_t>(stats) |
-                  reinterpret_cast<uintptr_t>(votes) | reinterpret_cast<uintptr_t>(height) | reinterpret_cast<uintptr_t>(keep_idx)) &
-                 3u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
-                "hpl_ground_fit: arrays must be 4-byte aligned, the workspace 8-byte");
+    HPL_CLOUD_CHECK(check_points(op, N));
+    HPL_CLOUD_CHECK(check_row_stride(op, pc_ld, N));
+    const Layout l(batch, N, hyps);
+    HPL_CLOUD_CHECK(check_workspace(op, workspace, 8, workspace_bytes_, l.bytes));
+    HPL_CLOUD_CHECK(check_aligned4(op, {pc, plane, stats, votes, height, keep_idx}));
     if (N == 0) return HPL_OK;
     GroundArgs a{};
-    int64_t blocks = 0;
-    for (int b = 0; b < batch; ++b) {
-        a.pprefix[b] = (int32_t)prefix[b];
-        a.bprefix[b] = (int32_t)blocks;
-        blocks += cdiv(prefix[b + 1] - prefix[b], GF_SPAN);
-    }
-    a.pprefix[batch] = (int32_t)N;
-    a.bprefix[batch] = (int32_t)blocks;
-    char *ws = static_cast<char *>(workspace);
+    const int64_t blocks = narrow_prefix(prefix, batch, GF_SPAN, a.pprefix, a.bprefix);
     a.pc = pc; a.pc_ld = pc_ld;
-    a.hyp = reinterpret_cast<double *>(ws + l.hyp);
-    a.state = reinterpret_cast<double *>(ws + l.state);
-    a.partials = reinterpret_cast<double *>(ws + l.partials);
-    a.cnt = reinterpret_cast<int32_t *>(ws + l.cnt);
-    a.blockoff = reinterpret_cast<int32_t *>(ws + l.blockoff);
+    a.hyp = carved<double>(workspace, l.hyp);
+    a.state = carved<double>(workspace, l.state);
+    a.partials = carved<double>(workspace, l.partials);
+    a.cnt = carved<int32_t>(workspace, l.cnt);
+    a.blockoff = carved<int32_t>(workspace, l.blockoff);
     a.plane = plane; a.height = height; a.stats = stats; a.votes = votes; a.keep_idx = keep_idx; a.ground = ground;
     for (int k = 0; k < 3; ++k) a.up[k] = (double)up[k];
     a.gate = ((double)min_cos * (double)min_cos) * uu;

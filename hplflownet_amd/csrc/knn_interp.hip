@@ -10,7 +10,7 @@
 // The arithmetic is part of the interface (include/hpl_bcl.h, tests/knn_oracle.py restates it in numpy): float32
 // d2 = (dx * dx + dy * dy) + dz * dz with dx = q.x - p.x, no contraction (the library builds with -ffp-contract=off);
 // candidates in index order, an entry replaced only by a strictly smaller d2, so ties go to the smaller index.
-#include "common.h"
+#include "cloud_common.h"
 
 #include <limits.h>
 #include <math.h>
@@ -19,7 +19,6 @@ using namespace hpl;
 
 namespace {
 
-constexpr int KNN_MAX_BATCH = 64;
 constexpr int KNN_MAX_K = 8;
 constexpr int KNN_MAX_C = 16;
 constexpr int KNN_BLOCK = 256;
@@ -38,18 +37,16 @@ struct KnnArgs {
     int64_t Q;
     int32_t C, batch;
     float eps;
-    int32_t rprefix[KNN_MAX_BATCH + 1];     // points of pairs 0 .. b-1 (N < 2^31)
-    int32_t qprefix[KNN_MAX_BATCH + 1];     // queries of pairs 0 .. b-1 (Q < 2^31)
-    int32_t bprefix[KNN_MAX_BATCH + 1];     // workgroups of pairs 0 .. b-1
+    int32_t rprefix[CLOUD_MAX_BATCH + 1];   // points of pairs 0 .. b-1 (N < 2^31)
+    int32_t qprefix[CLOUD_MAX_BATCH + 1];   // queries of pairs 0 .. b-1 (Q < 2^31)
+    int32_t bprefix[CLOUD_MAX_BATCH + 1];   // workgroups of pairs 0 .. b-1
 };
 
 template <int K>
 __global__ void __launch_bounds__(KNN_BLOCK) k_knn_interp(const KnnArgs a) {
     __shared__ float4 tile[KNN_TILE];
     const int blk = (int)blockIdx.x;
-    int b = 0;                   // the last pair whose first workgroup is <= blk (empty pairs own no workgroup)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) b = (b + s < a.batch && a.bprefix[b + s] <= blk) ? b + s : b;
+    const int b = group_of(a.bprefix, a.batch, blk);
     const int p0 = a.rprefix[b], p1 = a.rprefix[b + 1];
     const int64_t qi = (int64_t)a.qprefix[b] + (int64_t)(blk - a.bprefix[b]) * KNN_BLOCK + threadIdx.x;
     bool active = qi < (int64_t)a.qprefix[b + 1];
@@ -145,18 +142,14 @@ void launch(const KnnArgs &a, unsigned blocks, hipStream_t s) {
 extern "C" int hpl_knn_interp(const float *ref, int64_t ref_ld, const float *val, int C, const float *q, int64_t q_ld, int k,
                               float eps, int batch, const int64_t *ref_prefix, const int64_t *q_prefix, int32_t *idx,
                               float *dist2, float *out, const float *coverage, hplStream stream) {
+    const char *const op = "hpl_knn_interp";
     HPL_REQUIRE(ref && val && q && out && ref_prefix && q_prefix, "hpl_knn_interp: null pointer");
     HPL_REQUIRE(k >= 1 && k <= KNN_MAX_K, "hpl_knn_interp: k = %d (1 .. %d)", k, KNN_MAX_K);
     HPL_REQUIRE(C >= 1 && C <= KNN_MAX_C, "hpl_knn_interp: %d value channels (1 .. %d)", C, KNN_MAX_C);
-    HPL_REQUIRE(batch >= 1 && batch <= KNN_MAX_BATCH, "hpl_knn_interp: batch %d (1 .. %d)", batch, KNN_MAX_BATCH);
+    HPL_CLOUD_CHECK(check_batch(op, batch));
     HPL_REQUIRE(eps >= 0.f && isfinite(eps), "hpl_knn_interp: eps must be finite and >= 0");
-    HPL_REQUIRE(ref_prefix[0] == 0 && q_prefix[0] == 0, "hpl_knn_interp: the prefixes must start at 0");
-    KnnArgs a{};
-    int64_t blocks = 0;
-    for (int b = 0; b < batch; ++b) {
-        HPL_REQUIRE(ref_prefix[b + 1] >= ref_prefix[b], "hpl_knn_interp: the point prefix decreases at pair %d", b);
-        HPL_REQUIRE(q_prefix[b + 1] >= q_prefix[b], "hpl_knn_interp: the query prefix decreases at pair %d", b);
-    }
+    HPL_CLOUD_CHECK(check_prefix(op, "the point prefix", "pair", ref_prefix, batch));
+    HPL_CLOUD_CHECK(check_prefix(op, "the query prefix", "pair", q_prefix, batch));
     const int64_t N = ref_prefix[batch], Q = q_prefix[batch];
     const int64_t lim = (int64_t)1 << 31;       // (N, Q below it first: the products cannot overflow)
     HPL_REQUIRE(N < lim && Q < lim && N * C < lim && Q * C < lim && (int64_t)k * Q < lim,
@@ -164,21 +157,14 @@ extern "C" int hpl_knn_interp(const float *ref, int64_t ref_ld, const float *val
                 (long long)Q, C, k);
     HPL_REQUIRE(ref_ld >= N && q_ld >= Q, "hpl_knn_interp: row strides %lld / %lld below %lld points / %lld queries",
                 (long long)ref_ld, (long long)q_ld, (long long)N, (long long)Q);
-    for (int b = 0; b < batch; ++b) {
+    for (int b = 0; b < batch; ++b)
         HPL_REQUIRE(ref_prefix[b + 1] > ref_prefix[b] || q_prefix[b + 1] == q_prefix[b],
                     "hpl_knn_interp: pair %d has queries and no points", b);
-        a.rprefix[b] = (int32_t)ref_prefix[b];
-        a.qprefix[b] = (int32_t)q_prefix[b];
-        a.bprefix[b] = (int32_t)blocks;
-        blocks += cdiv(q_prefix[b + 1] - q_prefix[b], KNN_BLOCK);
-    }
-    a.rprefix[batch] = (int32_t)N;
-    a.qprefix[batch] = (int32_t)Q;
-    a.bprefix[batch] = (int32_t)blocks;
-    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(ref) | reinterpret_cast<uintptr_t>(val) | reinterpret_cast<uintptr_t>(q) |
-                  reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(idx) | reinterpret_cast<uintptr_t>(dist2) |
-                  reinterpret_cast<uintptr_t>(coverage)) & 3u) == 0, "hpl_knn_interp: arrays must be 4-byte aligned");
+    HPL_CLOUD_CHECK(check_aligned4(op, {ref, val, q, out, idx, dist2, coverage}));
     if (Q == 0) return HPL_OK;
+    KnnArgs a{};
+    narrow_prefix(ref_prefix, batch, KNN_BLOCK, a.rprefix, nullptr);
+    const int64_t blocks = narrow_prefix(q_prefix, batch, KNN_BLOCK, a.qprefix, a.bprefix);
     a.ref = ref; a.ref_ld = ref_ld; a.val = val; a.q = q; a.q_ld = q_ld;
     a.idx = idx; a.dist2 = dist2; a.out = out; a.cov = coverage;
     a.Q = Q; a.C = C; a.batch = batch; a.eps = eps;

@@ -25,7 +25,7 @@
 //
 // Integer counts do not depend on their order, the float sums have one order, the root is the smallest index: every output of
 // a pair is the same bits alone, anywhere in a batch and beside other work.
-#include "common.h"
+#include "cloud_common.h"
 
 #include <math.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -35,10 +35,8 @@ using namespace hpl;
 
 namespace {
 
-constexpr int MS_MAX_BATCH = 64;
 constexpr int MS_MAX_OBJECTS = 4096;
 constexpr int MS_BLOCK = 256;
-constexpr int64_t MS_MAX_POINTS = (((int64_t)1 << 31) + 2) / 3;     // N >= 2^31 / 3 is refused, as hpl_rigid_fit does
 constexpr int MS_CELL_BITS = 19;
 constexpr int MS_CELL_BIAS = 1 << (MS_CELL_BITS - 1);
 constexpr double MS_CELL_MAX = (double)(MS_CELL_BIAS - 2);           // |cell| <= 2^18 - 2: the neighbours' fields stay in 19 bits
@@ -63,15 +61,11 @@ struct SegArgs {
     int32_t *soval;
     int32_t *labels, *obj_info, *stats;
     float *obj_motion;
-    int32_t pprefix[MS_MAX_BATCH + 1];
+    int32_t pprefix[CLOUD_MAX_BATCH + 1];
 };
 
-__device__ __forceinline__ int pair_of(const SegArgs &a, int i) {
-    int b = 0;                   // the last pair that starts at or before i (empty pairs start where the next one does)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) b = (b + s < a.batch && a.pprefix[b + s] <= i) ? b + s : b;
-    return b;
-}
+// the pair of point i: the last one that starts at or before i
+__device__ __forceinline__ int pair_of(const SegArgs &a, int i) { return group_of(a.pprefix, a.batch, i); }
 
 __device__ __forceinline__ u64 make_key(int b, int cx, int cy, int cz) {
     return ((u64)b << (3 * MS_CELL_BITS)) | ((u64)cx << (2 * MS_CELL_BITS)) | ((u64)cy << MS_CELL_BITS) | (u64)cz;
@@ -142,17 +136,6 @@ __device__ __forceinline__ void unite(int32_t *parent, int u, int v) {
         ru = find_root(parent, old);
         rv = lo;
     }
-}
-
-__device__ __forceinline__ int lower_bound(const u64 *keys, int n, u64 k) {
-    int lo = 0, len = n;
-    while (len > 0) {
-        const int half = len >> 1;
-        const bool right = keys[lo + half] < k;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
-    return lo;
 }
 
 __global__ void __launch_bounds__(MS_BLOCK) k_seg_link(const SegArgs a) {
@@ -245,14 +228,7 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_objects(const SegArgs a) {
     int32_t *info = a.obj_info + ((int64_t)b * a.max_objects + o) * 2;
     float *motion = a.obj_motion + ((int64_t)b * a.max_objects + o) * 6;
     // the object's run in the second sort: its points in index order, the root first
-    const uint32_t k = (uint32_t)(base + o);
-    int lo = 0, len = o < count ? a.n : 0;
-    while (len > 0) {
-        const int half = len >> 1;
-        const bool right = a.sokey[lo + half] < k;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
+    const int lo = lower_bound(a.sokey, o < count ? a.n : 0, (uint32_t)(base + o));
     if (o >= count || lo >= a.n) {               // an unused row (an object always has its run)
         if (t == 0) { info[0] = -1; info[1] = 0; }
         if (t < 6) motion[t] = 0.f;
@@ -270,26 +246,9 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_objects(const SegArgs a) {
         acc[4] += (double)f[a.fsc];
         acc[5] += (double)f[2 * a.fsc];
     }
-#pragma unroll
-    for (int c = 0; c < 6; ++c) red[c][t] = acc[c];
-    __syncthreads();
-    for (int w = MS_BLOCK / 2; w > 0; w >>= 1) {
-        if (t < w) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) red[c][t] += red[c][t + w];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(red, acc, t);
     if (t == 0) { info[0] = root - p0; info[1] = m; }
     if (t < 6) motion[t] = (float)(red[t][0] / (double)m);
-}
-
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
-inline int count_bits(int64_t n) {
-    int bits = 1;
-    while (((int64_t)1 << bits) <= n) ++bits;    // object numbers 0 .. n
-    return bits;
 }
 
 size_t temp_bytes(int64_t n) {
@@ -306,28 +265,22 @@ size_t temp_bytes(int64_t n) {
 
 // workspace: key | sorted key | val | sorted val | parent | size | flag | excl | object key | sorted object key | sorted object
 // val | rocPRIM temporaries
-struct Layout {
-    u64 *key, *skey;
-    int32_t *val, *sval, *parent, *size, *flag, *excl, *soval;
-    uint32_t *okey, *sokey;
-    void *temp;
-    int64_t bytes;
-    Layout(char *p, int64_t n) {
-        char *b = p;
-        auto take = [&p](int64_t nbytes) { char *q = p; p += align256(nbytes); return q; };
-        key = reinterpret_cast<u64 *>(take(n * 8));
-        skey = reinterpret_cast<u64 *>(take(n * 8));
-        val = reinterpret_cast<int32_t *>(take(n * 4));
-        sval = reinterpret_cast<int32_t *>(take(n * 4));
-        parent = reinterpret_cast<int32_t *>(take(n * 4));
-        size = reinterpret_cast<int32_t *>(take(n * 4));
-        flag = reinterpret_cast<int32_t *>(take((n + 1) * 4));
-        excl = reinterpret_cast<int32_t *>(take((n + 1) * 4));
-        okey = reinterpret_cast<uint32_t *>(take(n * 4));
-        sokey = reinterpret_cast<uint32_t *>(take(n * 4));
-        soval = reinterpret_cast<int32_t *>(take(n * 4));
-        temp = p;
-        bytes = p - b;
+struct Layout {                  // byte offsets
+    int64_t key, skey, val, sval, parent, size, flag, excl, okey, sokey, soval, bytes;
+    explicit Layout(int64_t n) {
+        Carver c;
+        key = c.take(n * 8);
+        skey = c.take(n * 8);
+        val = c.take(n * 4);
+        sval = c.take(n * 4);
+        parent = c.take(n * 4);
+        size = c.take(n * 4);
+        flag = c.take((n + 1) * 4);
+        excl = c.take((n + 1) * 4);
+        okey = c.take(n * 4);
+        sokey = c.take(n * 4);
+        soval = c.take(n * 4);
+        bytes = c.bytes;
     }
 };
 
@@ -338,12 +291,12 @@ inline int64_t temp_room(int64_t n) {
     return align256((int64_t)imax((int64_t)temp_bytes(n), (int64_t)temp_bytes(cap)));
 }
 
-int64_t workspace_bytes(int64_t n) { return Layout(nullptr, n).bytes + temp_room(n); }
+int64_t workspace_bytes(int64_t n) { return Layout(n).bytes + temp_room(n); }
 
 }  // namespace
 
 extern "C" int64_t hpl_motion_segment_workspace_bytes(int batch, int64_t n_total) {
-    if (batch < 1 || batch > MS_MAX_BATCH || n_total < 0 || n_total >= MS_MAX_POINTS) return -1;
+    if (batch < 1 || batch > CLOUD_MAX_BATCH || n_total < 0 || n_total >= CLOUD_MAX_POINTS) return -1;
     return workspace_bytes(n_total);
 }
 
@@ -351,34 +304,27 @@ extern "C" int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *f
                                   const float *residual, int batch, const int64_t *prefix, float tau, float eps, float dv,
                                   int min_points, int max_objects, int32_t *labels, int32_t *obj_info, float *obj_motion,
                                   int32_t *stats, void *workspace, int64_t workspace_bytes_, hplStream stream) {
+    const char *const op = "hpl_motion_segment";
     HPL_REQUIRE(pc && flow && residual && prefix && labels && obj_info && obj_motion && stats && workspace,
                 "hpl_motion_segment: null pointer");
-    HPL_REQUIRE(batch >= 1 && batch <= MS_MAX_BATCH, "hpl_motion_segment: batch %d (1 .. %d)", batch, MS_MAX_BATCH);
+    HPL_CLOUD_CHECK(check_batch(op, batch));
     HPL_REQUIRE(tau > 0.f && isfinite(tau), "hpl_motion_segment: tau must be finite and > 0");
     HPL_REQUIRE(eps > 0.f && isfinite(eps), "hpl_motion_segment: eps must be finite and > 0");
     HPL_REQUIRE(dv > 0.f, "hpl_motion_segment: dv must be > 0 (+inf: no flow criterion)");
     HPL_REQUIRE(min_points >= 1, "hpl_motion_segment: min_points = %d (>= 1)", min_points);
     HPL_REQUIRE(max_objects >= 1 && max_objects <= MS_MAX_OBJECTS, "hpl_motion_segment: max_objects = %d (1 .. %d)", max_objects,
                 MS_MAX_OBJECTS);
-    HPL_REQUIRE(prefix[0] == 0, "hpl_motion_segment: the prefix must start at 0");
-    for (int b = 0; b < batch; ++b)
-        HPL_REQUIRE(prefix[b + 1] >= prefix[b], "hpl_motion_segment: the prefix decreases at pair %d", b);
+    HPL_CLOUD_CHECK(check_prefix(op, "the prefix", "pair", prefix, batch));
     const int64_t N = prefix[batch];
-    HPL_REQUIRE(N < MS_MAX_POINTS, "hpl_motion_segment: %lld points pass the 32-bit element limit (N < 2^31 / 3)", (long long)N);
-    HPL_REQUIRE(pc_ld >= N, "hpl_motion_segment: row stride %lld below %lld points", (long long)pc_ld, (long long)N);
-    HPL_REQUIRE(flow_sc >= 1 && flow_sp >= 1 && (flow_sp != 1 || flow_sc >= N) && (flow_sc != 1 || flow_sp >= 3 || N <= 1),
-                "hpl_motion_segment: flow strides %lld (component) / %lld (point) overlap for %lld points", (long long)flow_sc,
-                (long long)flow_sp, (long long)N);
-    HPL_REQUIRE(workspace_bytes_ >= workspace_bytes(N), "hpl_motion_segment: workspace of %lld bytes, needs %lld",
-                (long long)workspace_bytes_, (long long)workspace_bytes(N));
-    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(flow) | reinterpret_cast<uintptr_t>(residual) |
-                  reinterpret_cast<uintptr_t>(labels) | reinterpret_cast<uintptr_t>(obj_info) |
-                  reinterpret_cast<uintptr_t>(obj_motion) | reinterpret_cast<uintptr_t>(stats)) & 3u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
-                "hpl_motion_segment: arrays must be 4-byte aligned, the workspace 256-byte");
+    HPL_CLOUD_CHECK(check_points(op, N));
+    HPL_CLOUD_CHECK(check_row_stride(op, pc_ld, N));
+    HPL_CLOUD_CHECK(check_flow_strides(op, flow_sc, flow_sp, N));
+    HPL_CLOUD_CHECK(check_workspace(op, workspace, 256, workspace_bytes_, workspace_bytes(N)));
+    HPL_CLOUD_CHECK(check_aligned4(op, {pc, flow, residual, labels, obj_info, obj_motion, stats}));
     if (N == 0) return HPL_OK;
 
-    const Layout L(static_cast<char *>(workspace), N);
+    const Layout L(N);
+    void *const temp = carved<char>(workspace, L.bytes);
     SegArgs a{};
     a.pc = pc; a.pc_ld = pc_ld; a.flow = flow; a.fsc = flow_sc; a.fsp = flow_sp; a.residual = residual;
     a.tau = tau;
@@ -386,10 +332,14 @@ extern "C" int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *f
     a.dv2 = dv * dv;
     a.inv_cell = 1.0 / (MS_CELL_MARGIN * (double)eps);
     a.n = (int32_t)N; a.batch = batch; a.min_points = min_points; a.max_objects = max_objects;
-    a.key = L.key; a.skey = L.skey; a.val = L.val; a.sval = L.sval; a.parent = L.parent; a.size = L.size;
-    a.flag = L.flag; a.excl = L.excl; a.okey = L.okey; a.sokey = L.sokey; a.soval = L.soval;
+    a.key = carved<u64>(workspace, L.key); a.skey = carved<u64>(workspace, L.skey);
+    a.val = carved<int32_t>(workspace, L.val); a.sval = carved<int32_t>(workspace, L.sval);
+    a.parent = carved<int32_t>(workspace, L.parent); a.size = carved<int32_t>(workspace, L.size);
+    a.flag = carved<int32_t>(workspace, L.flag); a.excl = carved<int32_t>(workspace, L.excl);
+    a.okey = carved<uint32_t>(workspace, L.okey); a.sokey = carved<uint32_t>(workspace, L.sokey);
+    a.soval = carved<int32_t>(workspace, L.soval);
     a.labels = labels; a.obj_info = obj_info; a.obj_motion = obj_motion; a.stats = stats;
-    for (int b = 0; b <= batch; ++b) a.pprefix[b] = (int32_t)prefix[b];
+    narrow_prefix(prefix, batch, MS_BLOCK, a.pprefix, nullptr);
 
     hipStream_t s = to_stream(stream);
     if (hipMemsetAsync(stats, 0, sizeof(int32_t) * 4 * (size_t)batch, s) != hipSuccess) {
@@ -400,7 +350,7 @@ extern "C" int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *f
     k_seg_keys<<<grid, MS_BLOCK, 0, s>>>(a);
     HPL_CHECK_LAUNCH("hpl_motion_segment (keys)");
     size_t tb = (size_t)temp_room(N);
-    hipError_t e = rocprim::radix_sort_pairs(L.temp, tb, (const u64 *)L.key, L.skey, (const int32_t *)L.val, L.sval, (size_t)N, 0u,
+    hipError_t e = rocprim::radix_sort_pairs(temp, tb, (const u64 *)a.key, a.skey, (const int32_t *)a.val, a.sval, (size_t)N, 0u,
                                              64u, s);          // (the largest key, of the non-movers, has every bit set)
     if (e != hipSuccess) { set_error("hpl_motion_segment: radix sort failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
     k_seg_link<<<grid, MS_BLOCK, 0, s>>>(a);
@@ -410,12 +360,12 @@ extern "C" int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *f
     k_seg_flag<<<grid1, MS_BLOCK, 0, s>>>(a);
     HPL_CHECK_LAUNCH("hpl_motion_segment (flag)");
     tb = (size_t)temp_room(N);
-    e = rocprim::exclusive_scan(L.temp, tb, (const int32_t *)L.flag, L.excl, 0, (size_t)(N + 1), rocprim::plus<int32_t>(), s);
+    e = rocprim::exclusive_scan(temp, tb, (const int32_t *)a.flag, a.excl, 0, (size_t)(N + 1), rocprim::plus<int32_t>(), s);
     if (e != hipSuccess) { set_error("hpl_motion_segment: scan failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
     k_seg_label<<<grid, MS_BLOCK, 0, s>>>(a);
     HPL_CHECK_LAUNCH("hpl_motion_segment (label)");
     tb = (size_t)temp_room(N);
-    e = rocprim::radix_sort_pairs(L.temp, tb, (const uint32_t *)L.okey, L.sokey, (const int32_t *)L.val, L.soval, (size_t)N, 0u,
+    e = rocprim::radix_sort_pairs(temp, tb, (const uint32_t *)a.okey, a.sokey, (const int32_t *)a.val, a.soval, (size_t)N, 0u,
                                   (unsigned)count_bits(N), s);
     if (e != hipSuccess) { set_error("hpl_motion_segment: radix sort failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
     k_seg_objects<<<(unsigned)(batch * max_objects), MS_BLOCK, 0, s>>>(a);

@@ -14,7 +14,7 @@
 // the bits depend on the pair alone, not on its place in a batch or on what else the device runs.
 //
 // The arithmetic is part of the interface (include/hpl_bcl.h; tests/rigid_oracle.py restates it in numpy with an SVD).
-#include "common.h"
+#include "cloud_common.h"
 
 #include <math.h>
 
@@ -22,7 +22,6 @@ using namespace hpl;
 
 namespace {
 
-constexpr int RF_MAX_BATCH = 64;
 constexpr int RF_MAX_ITERS = 16;
 constexpr int RF_BLOCK = 256;
 constexpr int RF_PER_LANE = 4;
@@ -43,16 +42,9 @@ struct RigidArgs {
     float *Rt, *stats, *residual, *refined;
     double tau;
     int32_t batch, round, last;
-    int32_t pprefix[RF_MAX_BATCH + 1];      // points of pairs 0 .. b-1 (N < 2^31 / 3)
-    int32_t bprefix[RF_MAX_BATCH + 1];      // workgroups of pairs 0 .. b-1
+    int32_t pprefix[CLOUD_MAX_BATCH + 1];      // points of pairs 0 .. b-1 (N < 2^31 / 3)
+    int32_t bprefix[CLOUD_MAX_BATCH + 1];      // workgroups of pairs 0 .. b-1
 };
-
-__device__ __forceinline__ int pair_of(const RigidArgs &a, int blk) {
-    int b = 0;                   // the last pair whose first workgroup is <= blk (empty pairs own no workgroup)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) b = (b + s < a.batch && a.bprefix[b + s] <= blk) ? b + s : b;
-    return b;
-}
 
 struct Point {
     double p[3], q[3];
@@ -92,7 +84,7 @@ __device__ __forceinline__ double residual2(const double *R, const Point &pt, do
 __global__ void __launch_bounds__(RF_BLOCK) k_rigid_reduce(const RigidArgs a) {
     __shared__ double red[RF_SUMS][RF_BLOCK];
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int b = pair_of(a, blk);
+    const int b = group_of(a.bprefix, a.batch, blk);
     const int p0 = a.pprefix[b], p1 = a.pprefix[b + 1];
     const int64_t base = (int64_t)p0 + (int64_t)(blk - a.bprefix[b]) * RF_SPAN;
     double piv[3];
@@ -135,47 +127,8 @@ __global__ void __launch_bounds__(RF_BLOCK) k_rigid_reduce(const RigidArgs a) {
             for (int c = 0; c < 3; ++c) acc[7 + 3 * k + c] += up * dq[c];
         }
     }
-#pragma unroll
-    for (int k = 0; k < RF_SUMS; ++k) red[k][t] = acc[k];
-    __syncthreads();
-    for (int w = RF_BLOCK / 2; w > 0; w >>= 1) {
-        if (t < w) {
-#pragma unroll
-            for (int k = 0; k < RF_SUMS; ++k) red[k][t] += red[k][t + w];
-        }
-        __syncthreads();
-    }
+    block_tree_sum(red, acc, t);
     if (t < RF_SUMS) a.partials[(int64_t)blk * RF_SUMS + t] = red[t][0];
-}
-
-// One rotation of the cyclic Jacobi sweep of the symmetric 4x4 A (eigenvectors accumulate in the columns of V).
-template <int P, int Q>
-__device__ __forceinline__ void jacobi_rotate(double (&A)[4][4], double (&V)[4][4]) {
-    const double apq = A[P][Q];
-    if (apq == 0.0) return;
-    const double theta = (A[Q][Q] - A[P][P]) / (2.0 * apq);
-    const double tt = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));     // (theta = +-inf: 0)
-    const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                // A <- A J
-        const double akp = A[k][P], akq = A[k][Q];
-        A[k][P] = c * akp - s * akq;
-        A[k][Q] = s * akp + c * akq;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                // A <- J^T A
-        const double apk = A[P][k], aqk = A[Q][k];
-        A[P][k] = c * apk - s * aqk;
-        A[Q][k] = s * apk + c * aqk;
-    }
-    A[P][Q] = 0.0;
-    A[Q][P] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double vkp = V[k][P], vkq = V[k][Q];
-        V[k][P] = c * vkp - s * vkq;
-        V[k][Q] = s * vkp + c * vkq;
-    }
 }
 
 // The unit quaternion (w, x, y, z) of the proper rotation that maximises tr(R H), H = sum u (p - mp)(q - mq)^T (Horn 1987).
@@ -185,27 +138,15 @@ __device__ void horn_quaternion(const double *H, double *quat) {
                       {Syz - Szy, (Sxx - Syy) - Szz, Sxy + Syx, Szx + Sxz},
                       {Szx - Sxz, Sxy + Syx, (Syy - Sxx) - Szz, Syz + Szy},
                       {Sxy - Syx, Szx + Sxz, Syz + Szy, (Szz - Sxx) - Syy}};
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < RF_SWEEPS; ++sweep) {
-        double off = 0.0, all = 0.0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                all += A[i][j] * A[i][j];
-                if (i != j) off += A[i][j] * A[i][j];
-            }
-        if (!(off > 1e-32 * all)) break;         // (also a zero or non-finite matrix)
-        jacobi_rotate<0, 1>(A, V);
-        jacobi_rotate<0, 2>(A, V);
-        jacobi_rotate<0, 3>(A, V);
-        jacobi_rotate<1, 2>(A, V);
-        jacobi_rotate<1, 3>(A, V);
-        jacobi_rotate<2, 3>(A, V);
-    }
+    double V[4][4];
+    jacobi_eigen(A, V, RF_SWEEPS);
     int best = 0;                                // the largest eigenvalue; ties go to the smaller index
+    double most = A[0][0];
 #pragma unroll
-    for (int i = 1; i < 4; ++i) best = A[i][i] > A[best][best] ? i : best;
+    for (int i = 1; i < 4; ++i) {
+        best = A[i][i] > most ? i : best;
+        most = A[i][i] > most ? A[i][i] : most;
+    }
     double n2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -221,20 +162,7 @@ __global__ void __launch_bounds__(RF_BLOCK) k_rigid_solve(const RigidArgs a) {
     __shared__ double run[RF_RUNS][RF_SUMS];
     __shared__ double tot[RF_SUMS];
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int g = t / RF_SUMS, k = t % RF_SUMS;
-    const int b0 = a.bprefix[b], nb = a.bprefix[b + 1] - b0;
-    double s = 0.0;
-#pragma unroll 4
-    for (int j = g; j < nb; j += RF_RUNS) s += a.partials[(int64_t)(b0 + j) * RF_SUMS + k];
-    run[g][k] = s;
-    __syncthreads();
-    if (t < RF_SUMS) {
-        double v = 0.0;
-#pragma unroll
-        for (int r = 0; r < RF_RUNS; ++r) v += run[r][t];
-        tot[t] = v;
-    }
-    __syncthreads();
+    fold_partials<RF_SUMS, RF_RUNS, RF_BLOCK>(a.partials, a.bprefix[b], a.bprefix[b + 1] - a.bprefix[b], run, tot, t);
     if (t != 0) return;
 
     double *st = a.state + (int64_t)b * RF_STATE;
@@ -304,7 +232,7 @@ __global__ void __launch_bounds__(RF_BLOCK) k_rigid_solve(const RigidArgs a) {
 
 __global__ void __launch_bounds__(RF_BLOCK) k_rigid_apply(const RigidArgs a) {
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int b = pair_of(a, blk);
+    const int b = group_of(a.bprefix, a.batch, blk);
     const int p0 = a.pprefix[b], p1 = a.pprefix[b + 1];
     const int64_t base = (int64_t)p0 + (int64_t)(blk - a.bprefix[b]) * RF_SPAN;
     double *st = a.state + (int64_t)b * RF_STATE;
@@ -349,47 +277,31 @@ int64_t workspace_bytes(int batch, int64_t n_total) {
     return (int64_t)sizeof(double) * ((int64_t)batch * RF_STATE + (cdiv(n_total, RF_SPAN) + batch) * RF_SUMS);
 }
 
-constexpr int64_t RF_MAX_POINTS = (((int64_t)1 << 31) + 2) / 3;     // N >= 2^31 / 3 is refused: 3 N elements pass 32 bits
-
 }  // namespace
 
 extern "C" int64_t hpl_rigid_fit_workspace_bytes(int batch, int64_t n_total) {
-    if (batch < 1 || batch > RF_MAX_BATCH || n_total < 0 || n_total >= RF_MAX_POINTS) return -1;
+    if (batch < 1 || batch > CLOUD_MAX_BATCH || n_total < 0 || n_total >= CLOUD_MAX_POINTS) return -1;
     return workspace_bytes(batch, n_total);
 }
 
 extern "C" int hpl_rigid_fit(const float *pc, int64_t pc_ld, const float *flow, int64_t flow_sc, int64_t flow_sp,
                              const float *weight, int batch, const int64_t *prefix, int iters, float tau, float *Rt, float *stats,
                              float *residual, float *refined, void *workspace, int64_t workspace_bytes_, hplStream stream) {
+    const char *const op = "hpl_rigid_fit";
     HPL_REQUIRE(pc && flow && Rt && stats && prefix && workspace, "hpl_rigid_fit: null pointer");
-    HPL_REQUIRE(batch >= 1 && batch <= RF_MAX_BATCH, "hpl_rigid_fit: batch %d (1 .. %d)", batch, RF_MAX_BATCH);
+    HPL_CLOUD_CHECK(check_batch(op, batch));
     HPL_REQUIRE(iters >= 0 && iters <= RF_MAX_ITERS, "hpl_rigid_fit: iters = %d (0 .. %d)", iters, RF_MAX_ITERS);
     HPL_REQUIRE(tau > 0.f && isfinite(tau), "hpl_rigid_fit: tau must be finite and > 0");
-    HPL_REQUIRE(prefix[0] == 0, "hpl_rigid_fit: the prefix must start at 0");
-    for (int b = 0; b < batch; ++b)
-        HPL_REQUIRE(prefix[b + 1] >= prefix[b], "hpl_rigid_fit: the prefix decreases at pair %d", b);
+    HPL_CLOUD_CHECK(check_prefix(op, "the prefix", "pair", prefix, batch));
     const int64_t N = prefix[batch];
-    HPL_REQUIRE(N < RF_MAX_POINTS, "hpl_rigid_fit: %lld points pass the 32-bit element limit (N < 2^31 / 3)", (long long)N);
-    HPL_REQUIRE(pc_ld >= N, "hpl_rigid_fit: row stride %lld below %lld points", (long long)pc_ld, (long long)N);
-    HPL_REQUIRE(flow_sc >= 1 && flow_sp >= 1 && (flow_sp != 1 || flow_sc >= N) && (flow_sc != 1 || flow_sp >= 3 || N <= 1),
-                "hpl_rigid_fit: flow strides %lld (component) / %lld (point) overlap for %lld points", (long long)flow_sc,
-                (long long)flow_sp, (long long)N);
-    HPL_REQUIRE(workspace_bytes_ >= workspace_bytes(batch, N), "hpl_rigid_fit: workspace of %lld bytes, needs %lld",
-                (long long)workspace_bytes_, (long long)workspace_bytes(batch, N));
-    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(pc) | reinterpret_cast<uintptr_t>(flow) | reinterpret_cast<uintptr_t>(weight) |
-                  reinterpret_cast<uintptr_t>(Rt) | reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(residual) |
-                  reinterpret_cast<uintptr_t>(refined)) & 3u) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7u) == 0,
-                "hpl_rigid_fit: arrays must be 4-byte aligned, the workspace 8-byte");
+    HPL_CLOUD_CHECK(check_points(op, N));
+    HPL_CLOUD_CHECK(check_row_stride(op, pc_ld, N));
+    HPL_CLOUD_CHECK(check_flow_strides(op, flow_sc, flow_sp, N));
+    HPL_CLOUD_CHECK(check_workspace(op, workspace, 8, workspace_bytes_, workspace_bytes(batch, N)));
+    HPL_CLOUD_CHECK(check_aligned4(op, {pc, flow, weight, Rt, stats, residual, refined}));
     if (N == 0) return HPL_OK;
     RigidArgs a{};
-    int64_t blocks = 0;
-    for (int b = 0; b < batch; ++b) {
-        a.pprefix[b] = (int32_t)prefix[b];
-        a.bprefix[b] = (int32_t)blocks;
-        blocks += cdiv(prefix[b + 1] - prefix[b], RF_SPAN);
-    }
-    a.pprefix[batch] = (int32_t)N;
-    a.bprefix[batch] = (int32_t)blocks;
+    const int64_t blocks = narrow_prefix(prefix, batch, RF_SPAN, a.pprefix, a.bprefix);
     a.pc = pc; a.pc_ld = pc_ld; a.flow = flow; a.fsc = flow_sc; a.fsp = flow_sp; a.weight = weight;
     a.state = static_cast<double *>(workspace);
     a.partials = a.state + (int64_t)batch * RF_STATE;

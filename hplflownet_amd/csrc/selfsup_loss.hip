@@ -20,7 +20,7 @@
 // and beside other work.
 //
 // The arithmetic is part of the interface (include/hpl_bcl.h; tests/selfsup_oracle.py restates it in numpy).
-#include "common.h"
+#include "cloud_common.h"
 
 #include <math.h>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -29,12 +29,10 @@ using namespace hpl;
 
 namespace {
 
-constexpr int SS_MAX_BATCH = 64;
 constexpr int SS_MAX_K = 8;
 constexpr int SS_BLOCK = 256;
 constexpr int SS_TILE = 1024;            // records per LDS tile: 16 KiB
 constexpr int SS_SHORT = 16;             // a longer incoming run is summed by its wave together
-constexpr int64_t SS_MAX_POINTS = (((int64_t)1 << 31) + 2) / 3;     // counts >= 2^31 / 3 are refused, as hpl_rigid_fit does
 
 typedef unsigned long long u64;
 
@@ -53,16 +51,9 @@ struct SsArgs {
     int32_t *nn12, *nn21, *nbr, *kcnt;   // (N1), (N2), (k, N1), (N1)
     uint32_t *key2, *skey2, *keyg, *skeyg;
     int32_t *val2, *sval2, *valg, *svalg;
-    int32_t p1[SS_MAX_BATCH + 1], p2[SS_MAX_BATCH + 1];     // points of pairs 0 .. b-1
-    int32_t b1[SS_MAX_BATCH + 1], b2[SS_MAX_BATCH + 1];     // workgroups of pairs 0 .. b-1 of a launch over N1 / N2
+    int32_t p1[CLOUD_MAX_BATCH + 1], p2[CLOUD_MAX_BATCH + 1];     // points of pairs 0 .. b-1
+    int32_t b1[CLOUD_MAX_BATCH + 1], b2[CLOUD_MAX_BATCH + 1];     // workgroups of pairs 0 .. b-1 of a launch over N1 / N2
 };
-
-__device__ __forceinline__ int pair_of(const int32_t *bprefix, int batch, int blk) {
-    int b = 0;                   // the last pair whose first workgroup is <= blk (empty pairs own no workgroup)
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) b = (b + s < batch && bprefix[b + s] <= blk) ? b + s : b;
-    return b;
-}
 
 __device__ __forceinline__ void load_flow(const SsArgs &a, int64_t i, float (&f)[3]) {
     const float *p = a.flow + i * a.fsp;
@@ -113,26 +104,21 @@ __device__ __forceinline__ void search(const SsArgs &a, float4 *tile, const floa
 }
 
 // the workgroup's sum of v in a fixed tree, on lane 0
-__device__ __forceinline__ double block_sum(double *red, double v) {
-    const int t = (int)threadIdx.x;
+__device__ __forceinline__ double block_sum(double (&red)[1][SS_BLOCK], double v) {
+    const double acc[1] = {v};
     __syncthreads();             // (red may still be read from an earlier sum)
-    red[t] = v;
-    __syncthreads();
-    for (int w = SS_BLOCK / 2; w > 0; w >>= 1) {
-        if (t < w) red[t] += red[t + w];
-        __syncthreads();
-    }
-    return red[0];
+    block_tree_sum(red, acc, (int)threadIdx.x);
+    return red[0][0];
 }
 
 // DIR 0: queries p_i among pc2.  DIR 1: queries q_j among the warped points.
 template <int DIR>
 __global__ void __launch_bounds__(SS_BLOCK) k_ss_nearest(const SsArgs a) {
     __shared__ float4 tile[SS_TILE];
-    __shared__ double red[SS_BLOCK];
+    __shared__ double red[1][SS_BLOCK];
     const int blk = (int)blockIdx.x;
     const int32_t *qp = DIR == 0 ? a.p1 : a.p2, *rp = DIR == 0 ? a.p2 : a.p1, *bp = DIR == 0 ? a.b1 : a.b2;
-    const int b = pair_of(bp, a.batch, blk);
+    const int b = group_of(bp, a.batch, blk);
     const int64_t qi = (int64_t)qp[b] + (int64_t)(blk - bp[b]) * SS_BLOCK + threadIdx.x;
     const bool active = qi < (int64_t)qp[b + 1];
     float qx = nanf(""), qy = 0.f, qz = 0.f;
@@ -174,9 +160,9 @@ __global__ void __launch_bounds__(SS_BLOCK) k_ss_nearest(const SsArgs a) {
 template <int K>
 __global__ void __launch_bounds__(SS_BLOCK) k_ss_graph(const SsArgs a) {
     __shared__ float4 tile[SS_TILE];
-    __shared__ double red[SS_BLOCK];
+    __shared__ double red[1][SS_BLOCK];
     const int blk = (int)blockIdx.x;
-    const int b = pair_of(a.b1, a.batch, blk);
+    const int b = group_of(a.b1, a.batch, blk);
     const int64_t qi = (int64_t)a.p1[b] + (int64_t)(blk - a.b1[b]) * SS_BLOCK + threadIdx.x;
     const bool active = qi < (int64_t)a.p1[b + 1];
     float qx = nanf(""), qy = 0.f, qz = 0.f;
@@ -216,17 +202,6 @@ __global__ void __launch_bounds__(SS_BLOCK) k_ss_graph(const SsArgs a) {
     }
     const double s = block_sum(red, term);
     if (threadIdx.x == 0) a.partS[blk] = s;
-}
-
-__device__ __forceinline__ int lower_bound(const uint32_t *keys, int n, uint32_t k) {
-    int lo = 0, len = n;
-    while (len > 0) {
-        const int half = len >> 1;
-        const bool right = keys[lo + half] < k;
-        lo = right ? lo + half + 1 : lo;
-        len = right ? len - half - 1 : half;
-    }
-    return lo;
 }
 
 // One entry of an incoming run.  KIND 0: q_j picked p_i: p_i - q_j.  KIND 1: x_m lists x_i: (f_i - f_m) / k_m.
@@ -287,7 +262,7 @@ __device__ __forceinline__ void incoming_sum(const SsArgs &a, int lo, int len, c
 
 __global__ void __launch_bounds__(SS_BLOCK) k_ss_grad(const SsArgs a) {
     const int blk = (int)blockIdx.x;
-    const int b = pair_of(a.b1, a.batch, blk);
+    const int b = group_of(a.b1, a.batch, blk);
     const int64_t i64 = (int64_t)a.p1[b] + (int64_t)(blk - a.b1[b]) * SS_BLOCK + threadIdx.x;
     const bool active = i64 < (int64_t)a.p1[b + 1];
     const int i = (int)i64;
@@ -341,7 +316,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_ss_grad(const SsArgs a) {
 }
 
 __global__ void __launch_bounds__(SS_BLOCK) k_ss_fold(const SsArgs a) {
-    __shared__ double red[SS_BLOCK];
+    __shared__ double red[1][SS_BLOCK];
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
     const int n1p = a.p1[b + 1] - a.p1[b], n2p = a.p2[b + 1] - a.p2[b];
     const int nb1 = a.b1[b + 1] - a.b1[b], nb2 = a.b2[b + 1] - a.b2[b];
@@ -366,14 +341,6 @@ __global__ void __launch_bounds__(SS_BLOCK) k_ss_fold(const SsArgs a) {
     o[3] = (float)S;
 }
 
-inline int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-
-inline int count_bits(int64_t n) {
-    int bits = 1;
-    while (((int64_t)1 << bits) <= n) ++bits;    // keys 0 .. n
-    return bits;
-}
-
 size_t temp_bytes(int64_t n) {
     size_t s = 0;
     (void)rocprim::radix_sort_pairs(nullptr, s, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
@@ -390,34 +357,33 @@ inline int64_t temp_room(int64_t n) {
 }
 
 // workspace: the three partial arrays | nn12 | nn21 | nbr | k_i | the two sorts' keys and values, unsorted and sorted | rocPRIM
-struct Layout {                  // byte offsets (a size query has no base address to offset)
+struct Layout {                  // byte offsets
     int64_t part12, part21, partS, nn12, nn21, nbr, kcnt, key2, skey2, val2, sval2, keyg, skeyg, valg, svalg, bytes;
     Layout(int batch, int64_t n1, int64_t n2, int k) {
-        int64_t p = 0;
-        auto take = [&p](int64_t nbytes) { const int64_t q = p; p += align256(nbytes); return q; };
+        Carver c;
         const int64_t w1 = cdiv(n1, SS_BLOCK) + batch, w2 = cdiv(n2, SS_BLOCK) + batch, e = n1 * k;
-        part12 = take(w1 * 8);
-        part21 = take(w2 * 8);
-        partS = take(w1 * 8);
-        nn12 = take(n1 * 4);
-        nn21 = take(n2 * 4);
-        nbr = take(e * 4);
-        kcnt = take(n1 * 4);
-        key2 = take(n2 * 4);
-        skey2 = take(n2 * 4);
-        val2 = take(n2 * 4);
-        sval2 = take(n2 * 4);
-        keyg = take(e * 4);
-        skeyg = take(e * 4);
-        valg = take(e * 4);
-        svalg = take(e * 4);
-        bytes = p;
+        part12 = c.take(w1 * 8);
+        part21 = c.take(w2 * 8);
+        partS = c.take(w1 * 8);
+        nn12 = c.take(n1 * 4);
+        nn21 = c.take(n2 * 4);
+        nbr = c.take(e * 4);
+        kcnt = c.take(n1 * 4);
+        key2 = c.take(n2 * 4);
+        skey2 = c.take(n2 * 4);
+        val2 = c.take(n2 * 4);
+        sval2 = c.take(n2 * 4);
+        keyg = c.take(e * 4);
+        skeyg = c.take(e * 4);
+        valg = c.take(e * 4);
+        svalg = c.take(e * 4);
+        bytes = c.bytes;
     }
 };
 
 bool in_range(int batch, int64_t n1, int64_t n2, int k) {
-    return batch >= 1 && batch <= SS_MAX_BATCH && k >= 0 && k <= SS_MAX_K && n1 >= 0 && n1 < SS_MAX_POINTS && n2 >= 0 &&
-           n2 < SS_MAX_POINTS && n1 * k < ((int64_t)1 << 31);
+    return batch >= 1 && batch <= CLOUD_MAX_BATCH && k >= 0 && k <= SS_MAX_K && n1 >= 0 && n1 < CLOUD_MAX_POINTS && n2 >= 0 &&
+           n2 < CLOUD_MAX_POINTS && n1 * k < ((int64_t)1 << 31);
 }
 
 // the two sorts share the room: enough for either
@@ -448,35 +414,25 @@ extern "C" int hpl_selfsup_loss(const float *pc1, int64_t pc1_ld, const float *f
                                 const float *pc2, int64_t pc2_ld, int batch, const int64_t *prefix1, const int64_t *prefix2, int k,
                                 float w_chamfer, float w_smooth, float *loss, float *dflow, int32_t *nn12, int32_t *nn21,
                                 int32_t *nbr, void *workspace, int64_t workspace_bytes_, hplStream stream) {
+    const char *const op = "hpl_selfsup_loss";
     HPL_REQUIRE(pc1 && flow && prefix1 && prefix2 && loss && workspace, "hpl_selfsup_loss: null pointer");
-    HPL_REQUIRE(batch >= 1 && batch <= SS_MAX_BATCH, "hpl_selfsup_loss: batch %d (1 .. %d)", batch, SS_MAX_BATCH);
+    HPL_CLOUD_CHECK(check_batch(op, batch));
     HPL_REQUIRE(k >= 0 && k <= SS_MAX_K, "hpl_selfsup_loss: k = %d (0 .. %d)", k, SS_MAX_K);
     HPL_REQUIRE(w_chamfer >= 0.f && isfinite(w_chamfer) && w_smooth >= 0.f && isfinite(w_smooth),
                 "hpl_selfsup_loss: the weights must be finite and >= 0");
     HPL_REQUIRE(k >= 1 || w_smooth == 0.f, "hpl_selfsup_loss: k = 0 goes with w_smooth = 0");
-    HPL_REQUIRE(prefix1[0] == 0 && prefix2[0] == 0, "hpl_selfsup_loss: the prefixes must start at 0");
-    for (int b = 0; b < batch; ++b) {
-        HPL_REQUIRE(prefix1[b + 1] >= prefix1[b], "hpl_selfsup_loss: the prefix of pc1 decreases at pair %d", b);
-        HPL_REQUIRE(prefix2[b + 1] >= prefix2[b], "hpl_selfsup_loss: the prefix of pc2 decreases at pair %d", b);
-    }
+    HPL_CLOUD_CHECK(check_prefix(op, "the prefix of pc1", "pair", prefix1, batch));
+    HPL_CLOUD_CHECK(check_prefix(op, "the prefix of pc2", "pair", prefix2, batch));
     const int64_t N1 = prefix1[batch], N2 = prefix2[batch];
     HPL_REQUIRE(pc2 || N2 == 0, "hpl_selfsup_loss: null pointer (pc2 of %lld points)", (long long)N2);
     HPL_REQUIRE(in_range(batch, N1, N2, k),
                 "hpl_selfsup_loss: %lld / %lld points, k = %d pass the 32-bit element limit (counts < 2^31 / 3, k N1 < 2^31)",
                 (long long)N1, (long long)N2, k);
-    HPL_REQUIRE(pc1_ld >= N1 && pc2_ld >= N2, "hpl_selfsup_loss: row strides %lld / %lld below %lld / %lld points",
-                (long long)pc1_ld, (long long)pc2_ld, (long long)N1, (long long)N2);
-    HPL_REQUIRE(flow_sc >= 1 && flow_sp >= 1 && (flow_sp != 1 || flow_sc >= N1) && (flow_sc != 1 || flow_sp >= 3 || N1 <= 1),
-                "hpl_selfsup_loss: flow strides %lld (component) / %lld (point) overlap for %lld points", (long long)flow_sc,
-                (long long)flow_sp, (long long)N1);
-    const int64_t need = workspace_bytes(batch, N1, N2, k);
-    HPL_REQUIRE(workspace_bytes_ >= need, "hpl_selfsup_loss: workspace of %lld bytes, needs %lld", (long long)workspace_bytes_,
-                (long long)need);
-    HPL_REQUIRE(((reinterpret_cast<uintptr_t>(pc1) | reinterpret_cast<uintptr_t>(flow) | reinterpret_cast<uintptr_t>(pc2) |
-                  reinterpret_cast<uintptr_t>(loss) | reinterpret_cast<uintptr_t>(dflow) | reinterpret_cast<uintptr_t>(nn12) |
-                  reinterpret_cast<uintptr_t>(nn21) | reinterpret_cast<uintptr_t>(nbr)) & 3u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(workspace) & 255u) == 0,
-                "hpl_selfsup_loss: arrays must be 4-byte aligned, the workspace 256-byte");
+    HPL_CLOUD_CHECK(check_row_stride(op, pc1_ld, N1));
+    HPL_CLOUD_CHECK(check_row_stride(op, pc2_ld, N2));
+    HPL_CLOUD_CHECK(check_flow_strides(op, flow_sc, flow_sp, N1));
+    HPL_CLOUD_CHECK(check_workspace(op, workspace, 256, workspace_bytes_, workspace_bytes(batch, N1, N2, k)));
+    HPL_CLOUD_CHECK(check_aligned4(op, {pc1, flow, pc2, loss, dflow, nn12, nn21, nbr}));
     if (dflow && N1 > 0) {
         const int64_t fext = (N1 - 1) * flow_sp + 2 * flow_sc + 1;
         HPL_REQUIRE(!overlaps(dflow, 3 * N1, pc1, 2 * pc1_ld + N1) && !overlaps(dflow, 3 * N1, flow, fext) &&
@@ -486,39 +442,29 @@ extern "C" int hpl_selfsup_loss(const float *pc1, int64_t pc1_ld, const float *f
     if (N1 == 0) return HPL_OK;
 
     const Layout L(batch, N1, N2, k);
-    char *const w = static_cast<char *>(workspace);
-    void *const temp = w + L.bytes;
+    void *const temp = carved<char>(workspace, L.bytes);
     SsArgs a{};
-    int64_t blocks1 = 0, blocks2 = 0;
-    for (int b = 0; b < batch; ++b) {
-        a.p1[b] = (int32_t)prefix1[b];
-        a.p2[b] = (int32_t)prefix2[b];
-        a.b1[b] = (int32_t)blocks1;
-        a.b2[b] = (int32_t)blocks2;
-        blocks1 += cdiv(prefix1[b + 1] - prefix1[b], SS_BLOCK);
-        blocks2 += cdiv(prefix2[b + 1] - prefix2[b], SS_BLOCK);
-    }
-    a.p1[batch] = (int32_t)N1; a.p2[batch] = (int32_t)N2;
-    a.b1[batch] = (int32_t)blocks1; a.b2[batch] = (int32_t)blocks2;
+    const int64_t blocks1 = narrow_prefix(prefix1, batch, SS_BLOCK, a.p1, a.b1);
+    const int64_t blocks2 = narrow_prefix(prefix2, batch, SS_BLOCK, a.p2, a.b2);
     a.pc1 = pc1; a.ld1 = pc1_ld; a.flow = flow; a.fsc = flow_sc; a.fsp = flow_sp; a.pc2 = pc2; a.ld2 = pc2_ld;
     a.wc = w_chamfer; a.ws = w_smooth;
     a.batch = batch; a.k = k; a.n1 = (int32_t)N1; a.n2 = (int32_t)N2; a.grad = dflow ? 1 : 0;
     a.loss = loss; a.dflow = dflow; a.nn12_out = nn12; a.nn21_out = nn21; a.nbr_out = nbr;
-    a.part12 = reinterpret_cast<double *>(w + L.part12);
-    a.part21 = reinterpret_cast<double *>(w + L.part21);
-    a.partS = reinterpret_cast<double *>(w + L.partS);
-    a.nn12 = reinterpret_cast<int32_t *>(w + L.nn12);
-    a.nn21 = reinterpret_cast<int32_t *>(w + L.nn21);
-    a.nbr = reinterpret_cast<int32_t *>(w + L.nbr);
-    a.kcnt = reinterpret_cast<int32_t *>(w + L.kcnt);
-    a.key2 = reinterpret_cast<uint32_t *>(w + L.key2);
-    a.skey2 = reinterpret_cast<uint32_t *>(w + L.skey2);
-    a.val2 = reinterpret_cast<int32_t *>(w + L.val2);
-    a.sval2 = reinterpret_cast<int32_t *>(w + L.sval2);
-    a.keyg = reinterpret_cast<uint32_t *>(w + L.keyg);
-    a.skeyg = reinterpret_cast<uint32_t *>(w + L.skeyg);
-    a.valg = reinterpret_cast<int32_t *>(w + L.valg);
-    a.svalg = reinterpret_cast<int32_t *>(w + L.svalg);
+    a.part12 = carved<double>(workspace, L.part12);
+    a.part21 = carved<double>(workspace, L.part21);
+    a.partS = carved<double>(workspace, L.partS);
+    a.nn12 = carved<int32_t>(workspace, L.nn12);
+    a.nn21 = carved<int32_t>(workspace, L.nn21);
+    a.nbr = carved<int32_t>(workspace, L.nbr);
+    a.kcnt = carved<int32_t>(workspace, L.kcnt);
+    a.key2 = carved<uint32_t>(workspace, L.key2);
+    a.skey2 = carved<uint32_t>(workspace, L.skey2);
+    a.val2 = carved<int32_t>(workspace, L.val2);
+    a.sval2 = carved<int32_t>(workspace, L.sval2);
+    a.keyg = carved<uint32_t>(workspace, L.keyg);
+    a.skeyg = carved<uint32_t>(workspace, L.skeyg);
+    a.valg = carved<int32_t>(workspace, L.valg);
+    a.svalg = carved<int32_t>(workspace, L.svalg);
 
     hipStream_t s = to_stream(stream);
     k_ss_nearest<0><<<(unsigned)blocks1, SS_BLOCK, 0, s>>>(a);

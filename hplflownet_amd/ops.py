@@ -379,6 +379,53 @@ def _soa3(x, what, op='knn_interpolate'):
     return x, max(n, 1) if x.is_contiguous() else x.stride(0)
 
 
+def _int_in(who, name, v, lo, hi):
+    """v when it is an int (no bool) in lo .. hi."""
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise _lib.HplError('%s: %s = %r (an int in %d .. %d)' % (who, name, v, lo, hi))
+    return v
+
+
+def _prefix(prefix, n, who, what='the prefix'):
+    """The host list of B + 1 <= 65 non-decreasing ints from 0 to n (None: one pair)."""
+    pp = [0, n] if prefix is None else [int(x) for x in prefix]
+    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != n or any(b < a for a, b in zip(pp, pp[1:])):
+        raise _lib.HplError('%s: %s holds B + 1 <= 65 non-decreasing entries from 0 to %d, got %s' % (who, what, n, pp))
+    return pp
+
+
+def _flow_view(flow, N, dev, who, raw_op_hint=None):
+    """A (3, N) or [N, 3] float32 flow on dev as a (3, N) view of any strides that keep its elements apart (the models' flow
+    views and DenseFlow.query's answers are read in place; anything else is copied).  raw_op_hint: what to tell a caller
+    whose flow requires grad."""
+    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
+            (tuple(flow.shape) != (3, N) and tuple(flow.shape) != (N, 3)):
+        raise _lib.HplError('%s: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
+            who, N, N, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
+    if flow.requires_grad:
+        raise _lib.HplError(raw_op_hint or '%s has no autograd: flow requires grad' % who)
+    if tuple(flow.shape) != (3, N):
+        flow = flow.t()
+    if N > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N) or
+                  (flow.stride(0) == 1 and flow.stride(1) < 3 and N > 1)):
+        flow = flow.contiguous()
+    return flow
+
+
+_WORKSPACES = {}
+
+
+def _workspace(op, device, st, nbytes):
+    """Per-(op, device, stream) scratch, one buffer per size class (the next power of two): a call on another stream never
+    shares the partial sums of one in flight."""
+    size = 1 << max(12, int(nbytes - 1).bit_length())
+    key = (op, device, st, size)
+    ws = _WORKSPACES.get(key)
+    if ws is None:
+        ws = _WORKSPACES[key] = torch.empty(size, dtype=torch.uint8, device=device)
+    return ws
+
+
 def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=None, return_neighbors=False, out=None,
                     coverage=None):
     """hpl_knn_interp on the current stream: for every query of q (3, Q) its k nearest points of ref (3, N),
@@ -389,8 +436,7 @@ def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=Non
     out + coverage (Q,): the blend form -- `out` [Q, C] holds a base value per query and is updated in place to
     coverage * base + (1 - coverage) * interpolation; rows of coverage 1 are neither searched nor written (their neighbour
     columns keep idx = -1, dist2 = +inf).  No autograd: a tensor that requires grad raises HplError."""
-    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
-        raise _lib.HplError('knn_interpolate: k = %r (an int in 1 .. 8)' % (k,))
+    _int_in('knn_interpolate', 'k', k, 1, 8)
     ref, ref_ld = _soa3(ref, 'ref')
     q, q_ld = _soa3(q, 'q')
     N, Q = ref.shape[1], q.shape[1]
@@ -434,20 +480,6 @@ def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=Non
 
 
 # --------------------------------------------------------------------------- rigid motion from flow
-_RIGID_WS = {}
-
-
-def _rigid_workspace(device, st, nbytes):
-    """Per-(device, stream) scratch of hpl_rigid_fit, one buffer per size class (the next power of two): a call on another
-    stream never shares the partial sums of one in flight."""
-    size = 1 << max(12, int(nbytes - 1).bit_length())
-    key = (device, st, size)
-    ws = _RIGID_WS.get(key)
-    if ws is None:
-        ws = _RIGID_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
-    return ws
-
-
 def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_residual=False, out=None):
     """hpl_rigid_fit on the current stream: the rigid motion q = R p + t that explains most of the flow of
     each pair, fitted by iteratively reweighted least squares (Geman-McClure weights of scale tau, iters reweighted solves
@@ -459,32 +491,19 @@ def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_resid
     [, residual (N,)]): an inlier (residual <= tau, weight > 0) gets the rigid flow R p + t - p, any other point its input
     flow bit for bit.  status 0 (fewer than 3 points, or no weight): R = I, t = 0, refined = flow.  out: a contiguous [N, 3]
     float32 tensor that takes the refined flow (it must not overlap flow).  No autograd, no host synchronisation."""
-    if isinstance(iters, bool) or not isinstance(iters, int) or not 0 <= iters <= 16:
-        raise _lib.HplError('rigid_fit: iters = %r (an int in 0 .. 16)' % (iters,))
+    _int_in('rigid_fit', 'iters', iters, 0, 16)
     tau = float(tau)
     if not (tau > 0 and tau < float('inf')):
         raise _lib.HplError('rigid_fit: tau = %r (finite and > 0)' % (tau,))
     pc, pc_ld = _soa3(pc, 'pc', 'rigid_fit')
     N, dev = pc.shape[1], pc.device
-    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
-            (tuple(flow.shape) != (3, N) and tuple(flow.shape) != (N, 3)):
-        raise _lib.HplError('rigid_fit: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
-            N, N, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
-    if flow.requires_grad:
-        raise _lib.HplError('rigid_fit has no autograd: flow requires grad')
-    if tuple(flow.shape) != (3, N):
-        flow = flow.t()
-    if N > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N) or
-                  (flow.stride(0) == 1 and flow.stride(1) < 3 and N > 1)):
-        flow = flow.contiguous()
+    flow = _flow_view(flow, N, dev, 'rigid_fit')
     if weight is not None:
         if not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32 or weight.device != dev \
                 or weight.requires_grad:
             raise _lib.HplError('rigid_fit: weight must be a (%d,) float32 tensor on %s without grad' % (N, dev))
         weight = weight.contiguous()
-    pp = [0, N] if prefix is None else [int(x) for x in prefix]
-    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != N or any(b < a for a, b in zip(pp, pp[1:])):
-        raise _lib.HplError('rigid_fit: the prefix holds B + 1 <= 65 non-decreasing entries from 0 to N = %d, got %s' % (N, pp))
+    pp = _prefix(prefix, N, 'rigid_fit')
     B = len(pp) - 1
     if out is not None:
         if not torch.is_tensor(out) or tuple(out.shape) != (N, 3) or out.dtype != torch.float32 or out.device != dev or \
@@ -505,7 +524,7 @@ def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_resid
         if nbytes < 0:
             raise _lib.HplError('rigid_fit: %d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)' % (B, N))
         st = stream()
-        ws = _rigid_workspace(dev, st, nbytes)
+        ws = _workspace('rigid_fit', dev, st, nbytes)
         check(lib.hpl_rigid_fit(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), ptr(weight), B,
                                 (ctypes.c_int64 * (B + 1))(*pp), iters, tau, Rt.data_ptr(), stats.data_ptr(), ptr(residual),
                                 out.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_rigid_fit')
@@ -514,20 +533,6 @@ def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_resid
 
 
 # --------------------------------------------------------------------------- moving objects from flow
-_SEGMENT_WS = {}
-
-
-def _segment_workspace(device, st, nbytes):
-    """Per-(device, stream) scratch of hpl_motion_segment, one buffer per size class (the next power of two), as
-    _rigid_workspace keeps them."""
-    size = 1 << max(12, int(nbytes - 1).bit_length())
-    key = (device, st, size)
-    ws = _SEGMENT_WS.get(key)
-    if ws is None:
-        ws = _SEGMENT_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
-    return ws
-
-
 def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_points=5, max_objects=256, prefix=None, out=None):
     """hpl_motion_segment on the current stream: the points whose residual against a rigid fit exceeds tau
     (the movers), grouped into the connected components of the graph that links two movers of a pair within eps metres of
@@ -548,29 +553,16 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
             raise _lib.HplError('motion_segment: %s = %r (%s > 0)' % (name, v, 'any value' if inf_ok else 'finite and'))
         return v
     tau, eps, dv = scalar(tau, 'tau'), scalar(eps, 'eps'), scalar(dv, 'dv', True)
-    for v, name, hi in ((min_points, 'min_points', 2 ** 31 - 1), (max_objects, 'max_objects', 4096)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
-            raise _lib.HplError('motion_segment: %s = %r (an int in 1 .. %d)' % (name, v, hi))
+    _int_in('motion_segment', 'min_points', min_points, 1, 2 ** 31 - 1)
+    _int_in('motion_segment', 'max_objects', max_objects, 1, 4096)
     pc, pc_ld = _soa3(pc, 'pc', 'motion_segment')
     N, dev = pc.shape[1], pc.device
-    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
-            (tuple(flow.shape) != (3, N) and tuple(flow.shape) != (N, 3)):
-        raise _lib.HplError('motion_segment: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
-            N, N, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
-    if flow.requires_grad:
-        raise _lib.HplError('motion_segment has no autograd: flow requires grad')
-    if tuple(flow.shape) != (3, N):
-        flow = flow.t()
-    if N > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N) or
-                  (flow.stride(0) == 1 and flow.stride(1) < 3 and N > 1)):
-        flow = flow.contiguous()
+    flow = _flow_view(flow, N, dev, 'motion_segment')
     if not torch.is_tensor(residual) or tuple(residual.shape) != (N,) or residual.dtype != torch.float32 or \
             residual.device != dev or residual.requires_grad:
         raise _lib.HplError('motion_segment: residual must be a (%d,) float32 tensor on %s without grad' % (N, dev))
     residual = residual.contiguous()
-    pp = [0, N] if prefix is None else [int(x) for x in prefix]
-    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != N or any(b < a for a, b in zip(pp, pp[1:])):
-        raise _lib.HplError('motion_segment: the prefix holds B + 1 <= 65 non-decreasing entries from 0 to N = %d, got %s' % (N, pp))
+    pp = _prefix(prefix, N, 'motion_segment')
     B = len(pp) - 1
     if out is not None:
         if not torch.is_tensor(out) or tuple(out.shape) != (N,) or out.dtype != torch.int32 or out.device != dev or \
@@ -592,7 +584,7 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
     if nbytes < 0:
         raise _lib.HplError('motion_segment: %d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)' % (B, N))
     st = stream()
-    ws = _segment_workspace(dev, st, nbytes)
+    ws = _workspace('motion_segment', dev, st, nbytes)
     check(lib.hpl_motion_segment(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), residual.data_ptr(), B,
                                  (ctypes.c_int64 * (B + 1))(*pp), tau, eps, dv, min_points, max_objects, labels.data_ptr(),
                                  info.data_ptr(), motion.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st),
@@ -601,20 +593,6 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
 
 
 # --------------------------------------------------------------------------- ground removal
-_GROUND_WS = {}
-
-
-def _ground_workspace(device, st, nbytes):
-    """Per-(device, stream) scratch of hpl_ground_fit, one buffer per size class (the next power of two), as
-    _rigid_workspace keeps them."""
-    size = 1 << max(12, int(nbytes - 1).bit_length())
-    key = (device, st, size)
-    ws = _GROUND_WS.get(key)
-    if ws is None:
-        ws = _GROUND_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
-    return ws
-
-
 def ground_min_cos(max_tilt_deg):
     """The float32 cosine hpl_ground_fit takes for a largest tilt in degrees (0 <= tilt < 90)."""
     import math
@@ -637,9 +615,8 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
     uint8, keep_idx (N,) int32: per cloud from prefix[b] on the packed indices of its kept points, ascending, then -1
     [, votes (B, hyps) int32, -1 an invalid hypothesis][, height (N,) float32, NaN at a non-finite point]).  status 0 (no valid
     hypothesis, fewer than 3 points): plane 0, nothing ground, every index kept.  No autograd, no host synchronisation."""
-    for name, v, lo, hi in (('hyps', hyps, 1, 1024), ('refine', refine, 0, 8)):
-        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
-            raise _lib.HplError('ground_fit: %s = %r (an int in %d .. %d)' % (name, v, lo, hi))
+    _int_in('ground_fit', 'hyps', hyps, 1, 1024)
+    _int_in('ground_fit', 'refine', refine, 0, 8)
     tau, cut = float(tau), float(cut)
     if not (tau > 0 and tau < float('inf')):
         raise _lib.HplError('ground_fit: tau = %r (finite and > 0)' % (tau,))
@@ -652,14 +629,11 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
         upv = []
     if len(upv) != 3 or not all(abs(x) < float('inf') for x in upv) or not any(upv):
         raise _lib.HplError('ground_fit: up = %r (three finite numbers, not all zero)' % (up,))
-    for name, v in (('seed', seed), ('call', call)):
-        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v < 1 << 64:
-            raise _lib.HplError('ground_fit: %s = %r (an int in 0 .. 2^64 - 1)' % (name, v))
+    _int_in('ground_fit', 'seed', seed, 0, 2 ** 64 - 1)
+    _int_in('ground_fit', 'call', call, 0, 2 ** 64 - 1)
     pc, pc_ld = _soa3(pc, 'pc', 'ground_fit')
     N, dev = pc.shape[1], pc.device
-    pp = [0, N] if prefix is None else [int(x) for x in prefix]
-    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != N or any(b < a for a, b in zip(pp, pp[1:])):
-        raise _lib.HplError('ground_fit: the prefix holds B + 1 <= 65 non-decreasing entries from 0 to N = %d, got %s' % (N, pp))
+    pp = _prefix(prefix, N, 'ground_fit')
     B = len(pp) - 1
     lib = _lib.load()
     votes = height = None
@@ -686,7 +660,7 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
         if nbytes < 0:
             raise _lib.HplError('ground_fit: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (B, N))
         st = stream()
-        ws = _ground_workspace(dev, st, nbytes)
+        ws = _workspace('ground_fit', dev, st, nbytes)
         check(lib.hpl_ground_fit(pc.data_ptr(), pc_ld, B, (ctypes.c_int64 * (B + 1))(*pp), (ctypes.c_float * 3)(*upv), min_cos,
                                  hyps, tau, refine, cut, seed, call, plane.data_ptr(), stats.data_ptr(), ptr(votes), ptr(height),
                                  ground.data_ptr(), keep.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_ground_fit')
@@ -699,27 +673,6 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
 
 
 # --------------------------------------------------------------------------- self-supervised loss
-_SELFSUP_WS = {}
-
-
-def _selfsup_workspace(device, st, nbytes):
-    """Per-(device, stream) scratch of hpl_selfsup_loss, one buffer per size class (the next power of two), as
-    _rigid_workspace keeps them."""
-    size = 1 << max(12, int(nbytes - 1).bit_length())
-    key = (device, st, size)
-    ws = _SELFSUP_WS.get(key)
-    if ws is None:
-        ws = _SELFSUP_WS[key] = torch.empty(size, dtype=torch.uint8, device=device)
-    return ws
-
-
-def _prefix(prefix, n, who, what):
-    pp = [0, n] if prefix is None else [int(x) for x in prefix]
-    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != n or any(b < a for a, b in zip(pp, pp[1:])):
-        raise _lib.HplError('%s: %s holds B + 1 <= 65 non-decreasing entries from 0 to %d, got %s' % (who, what, n, pp))
-    return pp
-
-
 def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None, prefix2=None, need_grad=True,
                  return_neighbors=False, out=None):
     """hpl_selfsup_loss on the current stream: per pair the Chamfer distance between the warped cloud
@@ -734,8 +687,7 @@ def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None,
     input).  Float64 sums in a fixed order: the same bits for a pair alone and in any batch.  This is the raw op (a tensor that
     requires grad raises HplError; SelfSupLossFn is the autograd form); no host synchronisation, no read-back."""
     who = 'selfsup_loss'
-    if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 8:
-        raise _lib.HplError('%s: k = %r (an int in 0 .. 8)' % (who, k))
+    _int_in(who, 'k', k, 0, 8)
     try:
         w_chamfer, w_smooth = float(w_chamfer), float(w_smooth)
     except (TypeError, ValueError):
@@ -749,17 +701,7 @@ def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None,
     N1, N2, dev = pc1.shape[1], pc2.shape[1], pc1.device
     if pc2.device != dev:
         raise _lib.HplError('%s: pc1 on %s, pc2 on %s' % (who, dev, pc2.device))
-    if not torch.is_tensor(flow) or flow.dim() != 2 or flow.dtype != torch.float32 or flow.device != dev or \
-            (tuple(flow.shape) != (3, N1) and tuple(flow.shape) != (N1, 3)):
-        raise _lib.HplError('%s: flow must be a (3, %d) or (%d, 3) float32 tensor on %s, got %s' % (
-            who, N1, N1, dev, (tuple(flow.shape), flow.dtype, flow.device) if torch.is_tensor(flow) else type(flow)))
-    if flow.requires_grad:
-        raise _lib.HplError('%s is the raw op: flow requires grad (SelfSupLossFn is the autograd form)' % who)
-    if tuple(flow.shape) != (3, N1):
-        flow = flow.t()
-    if N1 > 0 and (min(flow.stride()) < 1 or (flow.stride(1) == 1 and flow.stride(0) < N1) or
-                   (flow.stride(0) == 1 and flow.stride(1) < 3 and N1 > 1)):
-        flow = flow.contiguous()
+    flow = _flow_view(flow, N1, dev, who, '%s is the raw op: flow requires grad (SelfSupLossFn is the autograd form)' % who)
     p1, p2 = _prefix(prefix1, N1, who, 'prefix1'), _prefix(prefix2, N2, who, 'prefix2')
     if len(p1) != len(p2):
         raise _lib.HplError('%s: prefix1 lists %d pairs, prefix2 %d' % (who, len(p1) - 1, len(p2) - 1))
@@ -787,7 +729,7 @@ def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None,
             raise _lib.HplError('%s: %d pairs of %d / %d points together, k = %d are outside the limits (64 pairs, counts < 2^31 / 3, '
                                 'k N1 < 2^31)' % (who, B, N1, N2, k))
         st = stream()
-        ws = _selfsup_workspace(dev, st, nbytes)
+        ws = _workspace(who, dev, st, nbytes)
         check(lib.hpl_selfsup_loss(pc1.data_ptr(), ld1, flow.data_ptr(), flow.stride(0), flow.stride(1), pc2.data_ptr(), ld2, B,
                                    (ctypes.c_int64 * (B + 1))(*p1), (ctypes.c_int64 * (B + 1))(*p2), k, w_chamfer, w_smooth,
                                    loss.data_ptr(), ptr(dflow), ptr(nn12), ptr(nn21), ptr(nbr) if k > 0 else None, ws.data_ptr(),

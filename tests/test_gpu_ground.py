@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import ground_oracle as G
+from batch64 import counts64
 from hplflownet_amd import _lib, data, flownet, ops
 
 pytestmark = pytest.mark.gpu
@@ -222,6 +223,29 @@ def test_a_cloud_has_the_same_bits_anywhere():
         busy = run(view, prefix, **kw)
         side.synchronize()
         assert all(np.array_equal(first[k], busy[k], equal_nan=True) for k in first)
+
+
+def test_a_batch_of_64_clouds_equals_its_clouds():
+    """B = 64 (tests/batch64.py): every cloud's outputs are the bits of that cloud run alone with prefix = [0, n]; votes and
+    winners are the restatement's, the refined planes of the clouds of 300 points and more lie within the bar of
+    test_refinement_against_the_restatement, and a cloud of fewer than 3 points has status 0 in both runs."""
+    counts = counts64()
+    parts = [cloud(max(n, 300), 100 + i)[:, :n] for i, n in enumerate(counts)]
+    pc, prefix = np.concatenate(parts, axis=1), prefix_of(parts)
+    kw = dict(hyps=65, refine=2, seed=3, call=12)
+    got, want = run(pc, prefix, **kw), G.ground_fit(pc, prefix, **kw)
+    assert np.array_equal(got['votes'], want['votes']) and np.array_equal(got['stats'][:, :3], want['stats'][:, :3])
+    same_classification(pc, prefix, got, 0.3)
+    for b, n in enumerate(counts):
+        alone = run(parts[b], [0, n], **kw)
+        assert bits(got, prefix[b], prefix[b + 1], b) == bits(alone, 0, n, 0), b
+        if n < 3:
+            assert got['stats'][b].tolist() == alone['stats'][0].tolist() == [0, -1, 0, n]
+        if n >= 300:
+            assert want['rounds'][b] == 2 and got['stats'][b, 0] == 1
+            w = want['plane64'][b]
+            assert np.abs(got['plane'][b, :3].astype(np.float64) - w[:3]).max() <= 2.0 ** -22, b
+            assert abs(float(got['plane'][b, 3]) - w[3]) / max(1.0, abs(w[3])) <= 2.0 ** -22, b
 
 
 # ----------------------------------------------------------------------------- remove_ground, reader

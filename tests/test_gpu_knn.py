@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from batch64 import counts64, prefix_of
 from hplflownet_amd._lib import HplError
 from knn_oracle import interpolate64, knn_search
 from test_gpu_dense_flow import GOLD, dev, ft3d_tree, make, pair, random_queries
@@ -172,6 +173,34 @@ def test_ragged_batches_equal_their_pairs(B):
         assert torch.equal(torch.where(i1 >= 0, i1 + rp[b], i1), own)
     assert int((idx[:, qp[1]:qp[1] + 20] == 0).sum()) == 0                             # the planted point is never returned
     assert bool((idx[2, qp[B - 1]:] == -1).all()) and bool(torch.isinf(d2[2, qp[B - 1]:]).all())
+
+
+def test_a_batch_of_64_pairs_equals_its_pairs():
+    """B = 64 (tests/batch64.py): every pair's outputs are the bits of that pair run alone with its own prefixes, and the
+    restatement's.  An empty pair has no queries and no points (queries without points are refused)."""
+    from hplflownet_amd import ops
+    qs = counts64()
+    ns = [0 if n == 0 else 1 + (7 * i) % 500 for i, n in enumerate(qs)]
+    ns[1] = 2                                              # a pair with fewer than k = 3 points
+    rng = np.random.RandomState(64)
+    refs = [cloud(rng, n, -5, 5) for n in ns]
+    qrs = [cloud(rng, n, -5, 5) for n in qs]
+    vals = [rng.uniform(-2, 2, (n, 3)).astype(np.float32) for n in ns]
+    rp, qp = prefix_of(ns), prefix_of(qs)
+    ref, val, q = np.concatenate(refs, 1), np.concatenate(vals, 0), np.concatenate(qrs, 1)
+    out, idx, d2 = ops.knn_interpolate(dev(ref), dev(val), dev(q), k=3, eps=EPS, ref_prefix=rp, q_prefix=qp,
+                                       return_neighbors=True)
+    torch.cuda.synchronize()
+    check_neighbours(ref, val, q, 3, idx, d2, out, rp, qp, what='B = 64')
+    for b in range(64):
+        if qs[b] == 0:
+            continue
+        sl = slice(qp[b], qp[b + 1])
+        o1, i1, s1 = ops.knn_interpolate(dev(refs[b]), dev(vals[b]), dev(qrs[b]), k=3, eps=EPS, ref_prefix=[0, ns[b]],
+                                         q_prefix=[0, qs[b]], return_neighbors=True)
+        assert torch.equal(o1.view(torch.int32), out[sl].view(torch.int32)) and torch.equal(s1, d2[:, sl]), b
+        assert torch.equal(torch.where(i1 >= 0, i1 + rp[b], i1), idx[:, sl]), b
+    assert bool((idx[2, qp[1]:qp[2]] == -1).all())
 
 
 def test_coverage_form():

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+from batch64 import counts64, prefix_of
 from rigid_oracle import base_weights, fit, rotation, scene, weights
 from test_rigid_cpu import CASES, mirror_scene
 
@@ -153,6 +154,26 @@ def test_ragged_batches_equal_their_pairs(weighted):
             assert same((R[b], t[b], stats[b]), (R2[j], t2[j], stats2[j]))
             assert same((refined[prefix[b]:prefix[b + 1]],), (refined2[pre[j]:pre[j + 1]],))
     assert stats2[1].tolist() == [0, 0, 0, 0] and torch.equal(R2[1].cpu(), torch.eye(3)) and not bool(t2[1].any())
+
+
+def test_a_batch_of_64_pairs_equals_its_pairs():
+    """B = 64 (tests/batch64.py): every pair's outputs are the bits of that pair run alone with prefix = [0, n], and its fit
+    is the restatement's within the bars of the ragged test above; a pair of fewer than 3 points has status 0."""
+    counts = counts64()
+    prefix = prefix_of(counts)
+    parts = [scene(n, 200 + i) for i, n in enumerate(counts)]
+    p, f = np.concatenate([x[0] for x in parts], 1), np.concatenate([x[1] for x in parts], 1)
+    R, t, stats, refined, residual = run(p, f, None, 4, prefix=prefix)
+    for b, n in enumerate(counts):
+        sl = slice(prefix[b], prefix[b + 1])
+        one = run(p[:, sl], f[:, sl], None, 4, prefix=[0, n])
+        assert same(one, (R[b:b + 1], t[b:b + 1], stats[b:b + 1], refined[sl], residual[sl])), b
+        o = fit(p[:, sl], f[:, sl], None, 4, TAU)
+        assert float(stats[b, 0]) == o['status'] == (1 if n >= 3 else 0), b
+        assert np.abs(R[b].cpu().numpy() - o['R']).max() <= 1e-6 and abs(float(stats[b, 1]) - o['share']) <= 2.0 ** -23, b
+        if n < 3:
+            assert torch.equal(R[b].cpu(), torch.eye(3)) and not bool(t[b].any())
+            assert same((refined[sl],), (dev(f[:, sl].T),)), b
 
 
 def test_strided_inputs_are_read_in_place():

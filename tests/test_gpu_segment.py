@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import rigid_oracle
+from batch64 import counts64, prefix_of
 from segment_oracle import SCENE_KW, scene, segment, segment_batch
 
 pytestmark = pytest.mark.gpu
@@ -175,6 +176,25 @@ def test_ragged_batch_equals_its_pairs():
     for j, b in zip((0, 2, 3), order):
         assert same((labels[prefix[b]:prefix[b + 1]], info[b], motion[b], stats[b]), (l2[pre[j]:pre[j + 1]], i2[j], m2[j], s2[j]))
     assert s2[1].tolist() == [0, 0, 0, 0] and i2[1, 0].tolist() == [-1, 0] and not bool(m2[1].any())
+
+
+def test_a_batch_of_64_pairs_equals_its_pairs():
+    """B = 64 (tests/batch64.py): the oracle's outputs, and every pair's are the bits of that pair run alone with
+    prefix = [0, n]."""
+    counts = counts64()
+    prefix = prefix_of(counts)
+    parts = [scene(n, 1 + (i % 2)) if n >= 300 else [x[..., 300 - n:] for x in scene(300, 1 + (i % 2))[:3]]     # (a short pair:
+             for i, n in enumerate(counts)]                                                                   # the tail of a scene)
+    p, f = np.concatenate([x[0] for x in parts], 1), np.concatenate([x[1] for x in parts], 1)
+    r = np.concatenate([x[2] for x in parts])
+    kw = dict(min_points=3, max_objects=64, **SCENE_KW)
+    labels, info, motion, stats = got = run(p, f, r, prefix=prefix, **kw)
+    check(got, p, f, r, prefix, what='B = 64', **kw)
+    for b, n in enumerate(counts):
+        sl = slice(prefix[b], prefix[b + 1])
+        one = run(p[:, sl], f[:, sl], r[sl], prefix=[0, n], **kw)
+        assert same(one, (labels[sl], info[b:b + 1], motion[b:b + 1], stats[b:b + 1])), b
+    assert int(stats[40, 1]) > 0 and int(stats[50, 1]) > 0 and int(stats[34, 1]) > 0      # objects on both sides of the step
 
 
 def test_degenerate_inputs():

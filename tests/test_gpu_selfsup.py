@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from batch64 import counts64, prefix_of
 from selfsup_oracle import selfsup
 
 pytestmark = pytest.mark.gpu
@@ -195,6 +196,14 @@ def batch_of(order, seed=21):
     return np.concatenate(xs, 1), np.concatenate(fs, 1), np.concatenate(qs, 1), p1, p2
 
 
+def piece(res, pp1, pp2, b):
+    """Pair b's outputs of a batch, its indices relative to the pair's first points."""
+    loss, dflow, nn12, nn21, nbr = res
+    s1, s2 = slice(pp1[b], pp1[b + 1]), slice(pp2[b], pp2[b + 1])
+    rel = lambda t, off: torch.where(t >= 0, t - off, t)          # noqa: E731
+    return (loss[b], dflow[s1], rel(nn12[s1], pp2[b]), rel(nn21[s2], pp1[b]), rel(nbr[:, s1], pp1[b]))
+
+
 def test_ragged_batch_against_the_restatement_and_bit_stable():
     """B = 4 ragged: an empty pair in the middle, a pair with N2 = 0, a pair of 2 points with k = 8.  Every pair's outputs are
     the same bits alone and in a batch of another order."""
@@ -209,16 +218,28 @@ def test_ragged_batch_against_the_restatement_and_bit_stable():
     xo, fo, qo, o1, o2 = batch_of(other)
     goto = run(xo, fo, qo, k, 0.75, 1.5, o1, o2)
 
-    def piece(res, pp1, pp2, b):
-        loss, dflow, nn12, nn21, nbr = res
-        s1, s2 = slice(pp1[b], pp1[b + 1]), slice(pp2[b], pp2[b + 1])
-        rel = lambda t, off: torch.where(t >= 0, t - off, t)          # noqa: E731
-        return (loss[b], dflow[s1], rel(nn12[s1], pp2[b]), rel(nn21[s2], pp1[b]), rel(nbr[:, s1], pp1[b]))
     for b, i in enumerate(order):
         xa, fa, qa = cloud(PAIRS[i][0], PAIRS[i][1], 21 + i)
         alone = run(xa, fa, qa, k, 0.75, 1.5)
         assert same(piece(got, p1, p2, b), piece(alone, [0, PAIRS[i][0]], [0, PAIRS[i][1]], 0)), i
         assert same(piece(got, p1, p2, b), piece(goto, o1, o2, other.index(i))), i
+
+
+def test_a_batch_of_64_pairs_equals_its_pairs():
+    """B = 64 (tests/batch64.py; pc2's sizes differ from pc1's, one pair has no pc2, and the two pairs of several workgroups
+    swap their sizes): the restatement's outputs, and every pair's are the bits of that pair run alone with its own prefixes."""
+    k = 8
+    n1 = counts64()
+    n2 = [0 if n == 0 else 1 + (11 * i) % 300 for i, n in enumerate(n1)]
+    n2[3], n2[40], n2[50] = 0, n1[50], n1[40]
+    clouds = [cloud(a, b, 640 + i) for i, (a, b) in enumerate(zip(n1, n2))]
+    x, f, q = (np.concatenate([c[j] for c in clouds], 1) for j in range(3))
+    p1, p2 = prefix_of(n1), prefix_of(n2)
+    got = run(x, f, q, k, 0.75, 1.5, p1, p2)
+    check(got, selfsup(x, f, q, k, 0.75, 1.5, p1, p2), 'B = 64', p1)
+    for b, (xa, fa, qa) in enumerate(clouds):
+        alone = run(xa, fa, qa, k, 0.75, 1.5, [0, n1[b]], [0, n2[b]])
+        assert same(piece(got, p1, p2, b), piece(alone, [0, n1[b]], [0, n2[b]], 0)), b
 
 
 # ----------------------------------------------------------------------------- non-finite inputs
