@@ -504,7 +504,7 @@ extern "C" int hpl_lattice_advance(hpl_lattice *b, int *done) {
         }
         ++b->stat_fallbacks;
         if (b->batch > 1) {
-            // a batch outgrew a bound: it is rebuilt on the fused path under the default bounds (16 x the batch's points per
+            // a batch outgrew a bound: it is rebuilt on the fused path under the default bounds (18 x the batch's points per
             // level), in the same arena if it fits; else HPL_ENOMEM, and the caller begins again with those bounds
             bool tight = false;
             for (int L = 0; L < b->spec.n_levels; ++L) tight = tight || b->bounds[L] > 0;

@@ -348,7 +348,7 @@ class LatticePipeline(object):
         if self.native:
             nb = self.gen.native_builder()
             if nb.fused and not any(nb.seen):
-                # no pair observed yet: every level is bounded at 16 x the cloud size (~1 GB of arena per build at N = 8 192).
+                # no pair observed yet: every level is bounded at 18 x the cloud size (~1 GB of arena per build at N = 8 192).
                 # The first build runs alone; its counts tighten the bounds (~0.26 GB) before further pairs are enqueued.
                 depth = 1
         while len(self._inflight) < depth and self._next < self._end:
@@ -628,7 +628,7 @@ class NativeBuilder(object):
         self.bytes_per_point = 6000            # arena hint of the staged driver, doubled on HPL_ENOMEM
         self.n_levels = n
         # fused builds: per-level vertex bounds (per cloud) = twice the largest count seen so far, rounded up to a power of
-        # two (so that the arena layout changes rarely); 0 = the library's default of 16 x the cloud size
+        # two (so that the arena layout changes rarely); 0 = the library's default of 18 x the cloud size + 64
         self.bounds = [0] * 8
         self.seen = [0] * 8
         self.fallbacks = 0

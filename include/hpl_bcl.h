@@ -798,7 +798,7 @@ typedef struct hpl_lattice hpl_lattice;   /* one pair under construction per bui
 hpl_lattice *hpl_lattice_create(const hpl_lattice_spec *spec /* HOST */);
 void hpl_lattice_destroy(hpl_lattice *b);
 /* Fused builds size every array by a bound: a level's vertices per cloud <= min(4 x its input points, bounds[L]), bounds[L]
- * = 0 meaning 16 x max(n0, n1).  hpl_lattice_arena_bytes: the arena a build of (n0, n1) points needs under the current bounds
+ * = 0 meaning 18 x max(n0, n1) + 64.  hpl_lattice_arena_bytes: the arena a build of (n0, n1) points needs under the current bounds
  * (0 for a staged builder: its arena is a guess that HPL_ENOMEM corrects).  A pair that outgrows a bound is rebuilt by the
  * staged driver inside the same hpl_lattice_advance protocol (hpl_lattice_stats counts it), so bounds only cost memory and
  * idle workgroups -- e.g. twice the largest counts seen so far.  hpl_lattice_stats: out[0] = kernel launches of the last

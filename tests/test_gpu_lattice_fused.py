@@ -89,18 +89,14 @@ def test_fused_equals_staged_bit_exact(nsc, kind, n1, n2, monkeypatch):
 def test_fused_equals_oracle():
     """straight against the C oracle (itself pinned to the reference's golden vectors), N = 1024 frustum"""
     import hplflownet_amd as H
-    from oracle import lattice_oracle
+    from lattice_fuzz import assert_equals_oracle
     args = types.SimpleNamespace(dim=3, scales_filter_map=SCALES_FILTER_MAP, evaluate=True, use_leaky=True,
                                  bcn_use_bias=True, bcn_use_norm=True, last_relu=False, DEVICE='cuda')
     gen = H.GenerateDataUnsymmetric(args, device=DEV)
     assert gen.native_builder().fused
     pc1, pc2, _ = synthetic_pair(1024, 0)
     lat = gen.build_native(dev(pc1), dev(pc2))
-    gd = lattice_oracle.generate_data(pc1, pc2, SCALES_FILTER_MAP)
-    for L, (x, d) in enumerate(zip(H.to_reference_format(lat), gd)):
-        for k, v in d.items():
-            got = x[k].cpu().numpy() if torch.is_tensor(x[k]) else x[k]
-            assert np.array_equal(np.asarray(got).reshape(-1), np.asarray(v).reshape(-1)), (L, k)
+    assert_equals_oracle(lat, pc1, pc2, 'N = 1024 frustum')
 
 
 def test_degenerate_clouds(monkeypatch):

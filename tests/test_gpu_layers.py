@@ -314,6 +314,7 @@ def test_device_lattice_fuzz_vs_oracle():
     tiny coordinates): every table of the GPU lattice equals the C oracle bit for bit."""
     import hplflownet_amd as H
     from hypothesis import given, settings, strategies as st
+    from lattice_fuzz import fuzz_pair
     from oracle import lattice_oracle as LO
     gen = H.GenerateDataUnsymmetric(types.SimpleNamespace(dim=3, scales_filter_map=SCALES_FILTER_MAP), device=DEV)
 
@@ -321,26 +322,7 @@ def test_device_lattice_fuzz_vs_oracle():
     @given(st.integers(1, 300), st.integers(1, 300), st.integers(0, 2 ** 31 - 1),
            st.sampled_from(['cloud', 'dup', 'line', 'plane', 'far', 'tiny']))
     def check(n1, n2, seed, kind):
-        rng = np.random.RandomState(seed)
-        p1 = rng.uniform(-8, 8, (n1, 3)).astype(np.float32)
-        p1[:, 2] = rng.uniform(1.5, 35, n1)
-        p2 = rng.uniform(-8, 8, (n2, 3)).astype(np.float32)
-        p2[:, 2] = rng.uniform(1.5, 35, n2)
-        if kind == 'dup':
-            p1[:] = p1[rng.randint(0, max(1, n1 // 4), n1)]
-            p2[: min(n1, n2)] = p1[: min(n1, n2)]
-        elif kind == 'line':
-            p1[:, :2] = 0.0
-            p2[:, 1:] = p2[0, 1:]
-        elif kind == 'plane':
-            p1[:, 2] = 10.0
-            p2[:, 0] = -1.0
-        elif kind == 'far':
-            p1 *= 40.0
-            p2 *= 40.0
-        elif kind == 'tiny':
-            p1 *= 1e-3
-            p2 *= 1e-3
+        p1, p2 = fuzz_pair(kind, n1, n2, seed)
         _, _, _, lat = gen([p1, p2, np.zeros_like(p1)])
         gd = LO.generate_data(p1, p2, SCALES_FILTER_MAP)
         for l, (x, y) in enumerate(zip(H.to_reference_format(lat), gd)):
