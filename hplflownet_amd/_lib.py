@@ -144,6 +144,8 @@ _SIGNATURES = {
     'hpl_weight_relayout': (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i64, c_i64,
                                            c_i64, c_vp, c_vp, c_i64, c_i64, c_vp]),
     'hpl_weight_relayout_batch': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_i64, c_vp, c_vp]),
+    'hpl_weight_fold': (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int,
+                                       c_vp, c_vp, ctypes.c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
     'hpl_weight_split3': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp]),
     'hpl_weight_split3_batch': (ctypes.c_int, [c_vp, ctypes.c_int, c_i64, ctypes.c_int, c_vp]),
     'hpl_weight_split2h': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]),

@@ -333,8 +333,9 @@ def _conv_of(m):
     return m.conv if isinstance(m, _ConvReLU) else m
 
 
-def _run_conv_stack(x, stack, table, M, F, use_leaky, out=None):
-    """x [rows, C] -> [M, O_last]: first conv gathers through `table` (F taps), the rest are 1x1."""
+def _run_conv_stack(x, stack, table, M, F, use_leaky, out=None, w0=None):
+    """x [rows, C] -> [M, O_last]: first conv gathers through `table` (F taps), the rest are 1x1.  w0: the weight the first
+    conv runs on instead of its own (ops.FoldedWeight.weight: the producer's 1x1 folded in)."""
     n = len(stack)
     for i, m in enumerate(stack):
         conv = _conv_of(m)
@@ -342,7 +343,7 @@ def _run_conv_stack(x, stack, table, M, F, use_leaky, out=None):
         o = out if i == n - 1 else None
         if i == 0:
             groups = table.groups() if conv.in_channels >= GROUPS_MIN_CHANNELS else None
-            x = ops.gconv(x, conv.weight, conv.bias, table.t, M, F, act=act,
+            x = ops.gconv(x, conv.weight if w0 is None else w0, conv.bias, table.t, M, F, act=act,
                           bwd_mode=table.bwd_mode(x.shape[0]) if torch.is_grad_enabled() else 'scatter',
                           out=o, slope=_slope(use_leaky),
                           row_perm=table.perm if groups is None else None,     # (the passes bring their own orders)
@@ -380,10 +381,13 @@ class BilateralConvFlex(nn.Module):
     def get_filter_size(self):
         return self.filter_size
 
-    def forward_cl(self, x, in_cloud, blur, out_cloud, out=None, keep=None):
+    def forward_cl(self, x, in_cloud, blur, out_cloud, out=None, keep=None, w0=None, folded=False):
         """Channel-last core.  x [N_in | H, C_in]; blur: NbrTable [15, H]; clouds: ops.CloudTables.  keep (a list, slicing
         layers): the vertex matrix the slice reads is appended to it -- in front of a trailing bias-only 1x1 when there is one
-        (flownet.DenseFlow); the same launches either way."""
+        (flownet.DenseFlow); the same launches either way.
+        The folded inference forward (no autograd): w0 replaces the first conv's weight (x then carries the
+        layer above's pre-1x1 rows and a ones part); folded: this layer's own trailing bias-only 1x1 and its biases live in
+        its consumer's weights, so it runs conv15 -> slice and nothing else."""
         H = blur.t.shape[1]
         if self.do_splat:
             if in_cloud.H != H:
@@ -398,6 +402,13 @@ class BilateralConvFlex(nn.Module):
             s = x
         bias = (self.bias if self.use_bias else None) if self.do_slice else None
         mods = list(self.blur_conv)
+        if folded:
+            if torch.is_grad_enabled() or not self.do_slice or len(mods) < 2 or isinstance(mods[-1], _ConvReLU):
+                raise _lib.HplError('the folded form is the inference forward of a slicing layer that ends in a bias-only 1x1')
+            y = _run_conv_stack(s, mods[:-1], blur, H, self.filter_size, self.use_leaky, w0=w0)
+            if keep is not None:
+                keep.append(y)
+            return ops.slice_raw(y, out_cloud.bary, out_cloud.off, out_cloud.N, out=out)
         if (self.do_slice and len(mods) >= 2 and not isinstance(mods[-1], _ConvReLU) and out_cloud.N < H):
             # Reordering.  The last conv is a bias-only 1x1 (no activation) and the slice is linear, so
             # slice(W y + b) = W slice(y) + b * sum_r(bary_r): run the 1x1 conv on the N_out sliced rows

@@ -50,13 +50,15 @@ __global__ void k_copy_cols4(const float4 *__restrict__ src, int64_t lds4, float
 }
 
 // el_minus_gr tables -> the first four columns of several concatenation buffers, one launch for the whole forward
-// (the tables are lattice outputs: every one of these copies can run before the first layer)
+// (the tables are lattice outputs: every one of these copies can run before the first layer); a job with `ones` also writes the
+// constant part 1, 0, 0, 0 into the four columns behind them (the input column that carries a folded bias)
 constexpr int EMG_JOBS = 24;
 struct EmgJobs {
     const float4 *src[EMG_JOBS];
     float *dst[EMG_JOBS];
     int64_t ldd[EMG_JOBS];
     int64_t rows[EMG_JOBS];
+    int ones[EMG_JOBS];
     int n;
 };
 __global__ void k_copy_emg_batch(const EmgJobs j) {
@@ -64,12 +66,16 @@ __global__ void k_copy_emg_batch(const EmgJobs j) {
     const float4 *src = j.src[job];
     float *dst = j.dst[job];
     const int64_t ldd = j.ldd[job], rows = j.rows[job];
+    const bool ones = j.ones[job] != 0;
     const bool vec = (ldd % 4 == 0) && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0);
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
         const float4 v = src[r];
         float *d = dst + r * ldd;
         if (vec) *reinterpret_cast<float4 *>(d) = v;
         else { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
+        if (!ones) continue;
+        if (vec) *reinterpret_cast<float4 *>(d + 4) = make_float4(1.f, 0.f, 0.f, 0.f);
+        else { d[4] = 1.f; d[5] = 0.f; d[6] = 0.f; d[7] = 0.f; }
     }
 }
 
@@ -226,7 +232,8 @@ struct Runner {
             if ((rc = view(op.a, A, "gconv input"))) return rc;
             if ((rc = amax_of(op.a, A, A.rows, op.C, cur_a_amax, guarded(op)))) return rc;
             // a wide launch's result usually feeds the next wide launch (the 1x1 convs behind a blur conv): its epilogue reduces it
-            if (!side && op.out.buf >= 0 && op.N >= 128) cur_y_amax = amax_slot();
+            // (HPL_FLAG_NOYAMAX: the program knows that none does -- the folded Up convs, whose reader is the slice)
+            if (!side && op.out.buf >= 0 && op.N >= 128 && !(op.flags & HPL_FLAG_NOYAMAX)) cur_y_amax = amax_slot();
             return HPL_OK;
         }
         if (op.kind == HPL_OP_WGRAD) {
@@ -467,10 +474,21 @@ struct Runner {
             const float *src;
             int64_t lds;
             if (op.a.buf == -1) {                 // el_minus_gr of the level: external table [rows][4]
-                HPL_REQUIRE(op.level >= 0 && op.level < n_levels && op.C == 4, "hpl_plan_run: emg copy at level %d", op.level);
+                HPL_REQUIRE(op.level >= 0 && op.level < n_levels && (op.C == 4 || op.C == 8), "hpl_plan_run: emg copy at level %d", op.level);
                 src = lv[op.level].emg_pair;
                 lds = 4;
                 HPL_REQUIRE(rows <= lv[op.level].n0 + lv[op.level].n1, "hpl_plan_run: emg copy of %lld rows", (long long)rows);
+                if (op.C == 8) {                  // el_minus_gr | 1, 0, 0, 0: the batched kernel with this one job
+                    HPL_REQUIRE(!(op.flags & HPL_FLAG_ACCUM) && Y.rows >= rows && Y.cols >= 8, "hpl_plan_run: emg copy output too small");
+                    if (rows == 0) return HPL_OK;
+                    EmgJobs jobs;
+                    jobs.src[0] = reinterpret_cast<const float4 *>(src);
+                    jobs.dst[0] = Y.p; jobs.ldd[0] = Y.ld; jobs.rows[0] = rows; jobs.ones[0] = 1;
+                    jobs.n = 1;
+                    k_copy_emg_batch<<<dim3((unsigned)imin(cdiv(rows, 256), 64), 1), 256, 0, s>>>(jobs);
+                    HPL_CHECK_LAUNCH("hpl_plan_run (copy)");
+                    return HPL_OK;
+                }
             } else {
                 if ((rc = view(op.a, A, "copy input"))) return rc;
                 HPL_REQUIRE(A.rows >= rows && A.cols >= op.C, "hpl_plan_run: copy input too small");
@@ -816,7 +834,7 @@ extern "C" int hpl_plan_run_range(hpl_plan *plan, const hpl_level_tables *levels
             View Y;
             if ((rc = r.view(op.out, Y, "copy output"))) return rc;
             const int64_t rows = symv(sym, op.m_sym);
-            HPL_REQUIRE(op.level >= 0 && op.level < n_levels && op.C == 4 && Y.cols >= 4 && Y.rows >= rows &&
+            HPL_REQUIRE(op.level >= 0 && op.level < n_levels && (op.C == 4 || op.C == 8) && Y.cols >= op.C && Y.rows >= rows &&
                             rows <= levels[op.level].n0 + levels[op.level].n1,
                         "hpl_plan_run: emg copy of %lld rows at level %d", (long long)rows, op.level);
             if (rows == 0) continue;
@@ -824,6 +842,7 @@ extern "C" int hpl_plan_run_range(hpl_plan *plan, const hpl_level_tables *levels
             jobs.dst[jobs.n] = Y.p;
             jobs.ldd[jobs.n] = Y.ld;
             jobs.rows[jobs.n] = rows;
+            jobs.ones[jobs.n] = op.C == 8;
             most = most > rows ? most : rows;
             if (++jobs.n == EMG_JOBS) flush();
         }

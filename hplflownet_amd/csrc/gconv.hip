@@ -1122,7 +1122,80 @@ __global__ void __launch_bounds__(256) k_weight_unlayout_batch(const hpl_relayou
         __syncthreads();
     }
 }
+// Fold of a bias-only 1x1 conv into its consumer's weight (hpl_weight_fold): one thread per element of out [O][Cout][F], f fastest
+// (the stores and the reads of W are runs of F floats, the reads of Wb follow the output column).  The products of two floats are
+// exact in double; the sum runs in the order of k, so a folded weight is a function of its inputs alone.  Once per weight epoch.
+__global__ void __launch_bounds__(256) k_weight_fold(const float *__restrict__ W, int O, int C, int F, int up0, int up_w,
+                                                     const float *__restrict__ Wb, int Cb, const float *__restrict__ bias_a,
+                                                     const float *__restrict__ bias_b, int ones_col, float *__restrict__ out, int Cout) {
+    const int64_t total = (int64_t)O * Cout * F;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int f = (int)(i % F);
+        const int64_t oc = i / F;
+        int c = (int)(oc % Cout);
+        const int o = (int)(oc / Cout);
+        const float *w = W + ((int64_t)o * C + up0) * F + f;          // W[o][up0 + k][f] at w[k * F]
+        float v;
+        if (ones_col >= 0 && c >= ones_col && c < ones_col + 4) {
+            v = 0.f;
+            if (c == ones_col) {
+                double acc = 0.0;
+                for (int k = 0; k < up_w; ++k) {
+                    const float b = bias_a ? (bias_b ? bias_a[k] + bias_b[k] : bias_a[k]) : bias_b[k];
+                    acc = fma((double)w[(int64_t)k * F], (double)b, acc);
+                }
+                v = (float)acc;
+            }
+        } else {
+            if (ones_col >= 0 && c >= ones_col + 4) c -= 4;
+            if (c < up0) v = W[((int64_t)o * C + c) * F + f];
+            else if (c < up0 + Cb) {
+                const float *wb = Wb + (c - up0);
+                double acc = 0.0;
+                for (int k = 0; k < up_w; ++k) acc = fma((double)w[(int64_t)k * F], (double)wb[(int64_t)k * Cb], acc);
+                v = (float)acc;
+            } else v = W[((int64_t)o * C + (c - Cb + up_w)) * F + f];
+        }
+        out[i] = v;
+    }
+}
+
+// the bias of a folded dense layer: out_bias[o] = own_bias[o] + sum_k W[o][up0 + k] b_tot[k]   (F == 1)
+__global__ void k_weight_fold_bias(const float *__restrict__ W, int O, int C, int up0, int up_w, const float *__restrict__ bias_a,
+                                   const float *__restrict__ bias_b, const float *__restrict__ own_bias, float *__restrict__ out_bias) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= O) return;
+    double acc = own_bias ? (double)own_bias[o] : 0.0;
+    if (bias_a || bias_b)
+        for (int k = 0; k < up_w; ++k) {
+            const float b = bias_a ? (bias_b ? bias_a[k] + bias_b[k] : bias_a[k]) : bias_b[k];
+            acc = fma((double)W[(int64_t)o * C + up0 + k], (double)b, acc);
+        }
+    out_bias[o] = (float)acc;
+}
 }  // namespace
+
+extern "C" int hpl_weight_fold(const float *W, int O, int C, int F, int up0, int up_w, const float *Wb, int Cb, const float *bias_a,
+                               const float *bias_b, int ones_col, float *out, int64_t out_elems, const float *own_bias,
+                               float *out_bias, hplStream stream) {
+    HPL_REQUIRE(W && Wb && out && O > 0 && C > 0 && F > 0 && Cb > 0, "hpl_weight_fold: bad arguments");
+    HPL_REQUIRE(up0 >= 0 && up_w > 0 && up0 + up_w <= C, "hpl_weight_fold: columns %d + %d outside the %d of the weight", up0, up_w, C);
+    const bool has_b = bias_a || bias_b;
+    HPL_REQUIRE(ones_col < 0 || (has_b && ones_col <= up0), "hpl_weight_fold: a ones part needs a bias and sits in front of the folded columns");
+    HPL_REQUIRE(!out_bias || F == 1, "hpl_weight_fold: a folded bias belongs to a dense layer (F == 1)");
+    HPL_REQUIRE(!has_b || ones_col >= 0 || out_bias, "hpl_weight_fold: the producer's bias needs a ones part or a folded bias");
+    const int Cout = C - up_w + Cb + (ones_col >= 0 ? 4 : 0);
+    HPL_REQUIRE(out_elems == (int64_t)O * Cout * F, "hpl_weight_fold: the folded weight has %lld elements, got room for %lld",
+                (long long)((int64_t)O * Cout * F), (long long)out_elems);
+    const int grid = (int)imin(cdiv(out_elems, 256), 16384);
+    k_weight_fold<<<grid, 256, 0, to_stream(stream)>>>(W, O, C, F, up0, up_w, Wb, Cb, bias_a, bias_b, ones_col, out, Cout);
+    HPL_CHECK_LAUNCH("hpl_weight_fold");
+    if (out_bias) {
+        k_weight_fold_bias<<<(O + 255) / 256, 256, 0, to_stream(stream)>>>(W, O, C, up0, up_w, bias_a, bias_b, own_bias, out_bias);
+        HPL_CHECK_LAUNCH("hpl_weight_fold (bias)");
+    }
+    return HPL_OK;
+}
 
 extern "C" int hpl_weight_unlayout_batch(const hpl_relayout_job *jobs, int njobs, const int64_t *prefix, int64_t total,
                                          const float *src, hplStream stream) {

@@ -191,8 +191,8 @@ class DeviceLattice(object):
 
 def _assemble(rows, parts, device):
     """Concatenate channel blocks into one [rows, sum C] matrix.  A part is (C, tensor) or
-    (C, callable(out_view) -> tensor).  Without autograd the blocks are written in place
-    (no cat copy for callables); with autograd this is a plain torch.cat."""
+    (C, callable(out_view) -> tensor), or (4, 'ones'): the constant part 1, 0, 0, 0 of a folded bias (inference only).
+    Without autograd the blocks are written in place (no cat copy for callables); with autograd this is a plain torch.cat."""
     if torch.is_grad_enabled():
         return torch.cat([src(None) if callable(src) else src for _, src in parts], dim=1)
     total = sum(c for c, _ in parts)
@@ -202,6 +202,9 @@ def _assemble(rows, parts, device):
         view = buf[:, col:col + c]
         if callable(src):
             src(view)
+        elif isinstance(src, str):
+            view.zero_()
+            view[:, 0].fill_(1.0)
         else:
             view.copy_(src)
         col += c
@@ -210,6 +213,7 @@ def _assemble(rows, parts, device):
 
 # ----------------------------------------------------------------------------- the two models
 _PLANS = weakref.WeakKeyDictionary()        # model -> plan.ForwardPlan (kept outside the module: deepcopy / state_dict safe)
+_FOLDS = weakref.WeakKeyDictionary()        # model -> {L: ops.FoldedWeight of the consumer of bcn{L+1}_}: they go with the model
 
 
 class _FlowNetBase(nn.Module):
@@ -282,6 +286,42 @@ class _FlowNetBase(nn.Module):
         Up conv that gathers through the level's blur table is wide enough for the tap-group passes."""
         from .bcl import GROUPS_MIN_CHANNELS
         return [getattr(self, 'bcn%d_' % (L + 1)).num_input >= GROUPS_MIN_CHANNELS for L in range(self.NLEV)]
+
+    def fold_up(self):
+        """True when the inference forward on a device-built lattice runs folded: every Up stack ends in a
+        bias-only 1x1 conv behind at least one other conv, and HPL_FOLD_UP is not 0."""
+        if not ops.FOLD_UP:
+            return False
+        for L in range(self.NLEV):
+            layer = getattr(self, 'bcn%d_' % (L + 1))
+            mods = list(layer.blur_conv)
+            if not layer.do_slice or len(mods) < 2 or isinstance(mods[-1], _ConvReLU):
+                return False
+            w = mods[-1].weight
+            if w.shape[0] != w.shape[1]:          # (the `up` block keeps its width: the layers' num_input stay what they are)
+                return False
+        return True
+
+    def up_fold(self, L, ensure=True):
+        """The folded weight of the consumer of Up layer bcn{L+1}_ (ops.FoldedWeight, current): L >= 1: of the 15-tap conv of
+        bcn{L}_ (its `up` block behind el_minus_gr and, with a bias to carry, the ones part); L == 0: of conv2, with its bias.
+        One per consumer, kept with the model; ensure=False: allocated, not computed (a program is emitted without a device)."""
+        prod = getattr(self, 'bcn%d_' % (L + 1))
+        tail = prod.blur_conv[-1]
+        lb = prod.bias if prod.use_bias else None
+        up_w = tail.weight.shape[0]
+        if L == 0:
+            c2 = self.conv2.conv
+            src, args = (c2.weight, tail.weight, tail.bias, lb, c2.bias), (1, 0, up_w, -1, True)
+        else:
+            cons = _conv_of(getattr(self, 'bcn%d_' % L).blur_conv[0])
+            ones = 4 if (tail.bias is not None or lb is not None) else -1
+            src, args = (cons.weight, tail.weight, tail.bias, lb, None), (cons.weight.shape[2], 4, up_w, ones, False)
+        mine = _FOLDS.setdefault(self, {})
+        ent = mine.get(L)
+        if ent is None or not ent.made_of(src, args):          # first use, or a parameter was replaced: new tensors
+            ent = mine[L] = ops.FoldedWeight(src[0], args[0], args[1], args[2], src[1], src[2], src[3], args[3], src[4], args[4])
+        return ent.ensure() if ensure else ent
 
     def forward_plan(self):
         """The native plan of this model's inference forward (built on first use, rebuilt when a parameter was
@@ -419,25 +459,40 @@ class _FlowNetBase(nn.Module):
                     down[ci].append(feats[ci])
                 if L >= 2:
                     prev = self._corr(L, lat, feats, prev, corrs, dev)
+        # the folded form (the launches of plan.build_program(fold=True)): an Up layer runs conv15 -> slice and hands its
+        # pre-1x1 rows down; its 1x1 and biases are in the weights of the conv that reads them
+        fold = pair and not torch.is_grad_enabled() and self.fold_up()
         up = None        # callable(out_view) producing the previous Up output, or None
         up_c = 0
+        wf = None        # folded: the ops.FoldedWeight the layer's 15-tap conv runs on
         for L in reversed(range(nlev)):
             lv = lat.levels[L]
             layer = getattr(self, 'bcn%d_' % (L + 1))
             if L == nlev - 1:
                 parts = [(corrs[L].shape[1], corrs[L]), (down[0][L].shape[1], down[0][L])]
             else:
-                parts = [(4, lat.levels[L + 1].emg[0]), (up_c, up)]
+                parts = [(4, lat.levels[L + 1].emg[0])]
+                if wf is not None and wf.args[3] >= 0:
+                    parts.append((4, 'ones'))
+                parts.append((up_c, up))
                 if L >= 2:
                     parts.append((corrs[L].shape[1], corrs[L]))
                 parts.append((down[0][L].shape[1], down[0][L]))
             x = _assemble(lv.H[0], parts, dev)
 
-            def produce(out, layer=layer, x=x, lv=lv, keep=self._dense_keep if L == 0 else None):
-                return layer.forward_cl(x, None, lv.blur[0], lv.clouds[0], out=out, keep=keep)
+            def produce(out, layer=layer, x=x, lv=lv, keep=self._dense_keep if L == 0 else None,
+                        w0=wf.weight if wf is not None else None):
+                return layer.forward_cl(x, None, lv.blur[0], lv.clouds[0], out=out, keep=keep, w0=w0, folded=fold)
             up, up_c = produce, layer.num_output[-1]
-        y = up(None)                                           # [N, HEAD_IN]
-        y = pointwise_conv(y, self.conv2.conv, True, self.use_leaky)
+            if fold:
+                up_c = layer.blur_conv[-1].weight.shape[1]
+                wf = self.up_fold(L)
+        y = up(None)                                           # [N, HEAD_IN]; folded: bcn1_'s pre-1x1 rows
+        if fold:
+            y = ops.gconv(y, wf.weight, wf.bias, None, y.shape[0], 1, act=ops.ACT_LEAKY, bwd_mode='dense',
+                          slope=ops.LEAKY_RATE if self.use_leaky else 0.0)
+        else:
+            y = pointwise_conv(y, self.conv2.conv, True, self.use_leaky)
         y = pointwise_conv(y, self.conv3.conv, True, self.use_leaky)
         y = pointwise_conv(y, self.conv4, False, self.use_leaky)
         if ragged:

@@ -897,6 +897,91 @@ def weight_relayout(W, R, Q, F, sr, sq, sf, base=0, fmap=None):
     return Wt
 
 
+#: HPL_FOLD_UP=0: the inference forward keeps the Up layers' trailing bias-only 1x1 convs as launches of their own (the
+#: program and the Python path of before the fold); read once, for A/B runs
+FOLD_UP = os.environ.get('HPL_FOLD_UP', '1') != '0'
+
+
+def weight_fold(W, F, up0, up_w, Wb, bias_a=None, bias_b=None, ones_col=-1, own_bias=None, dense_bias=False, out=None,
+                out_bias=None):
+    """hpl_weight_fold: the consumer weight W ((O, C, F, 1) or (O, C, 1), the parameter's own layout) with its columns
+    [up0, up0 + up_w) multiplied by the producer's bias-only 1x1 Wb ((up_w, Cb, 1[, 1])), the producer's bias bias_a + bias_b
+    carried by a four-column ones part inserted at column ones_col (>= 0) or, dense_bias (F == 1), by the folded bias
+    own_bias + W[:, up] b.  Sums in double, rounded once; deterministic.  -> (folded weight, folded bias or None)."""
+    O = W.shape[0]
+    C = W.numel() // (O * F)
+    Cb = Wb.numel() // up_w
+    if Wb.shape[0] != up_w or W.dtype is not torch.float32 or Wb.dtype is not torch.float32 or not (W.is_contiguous() and Wb.is_contiguous()):
+        raise _lib.HplError('weight_fold: contiguous float32 weights, the 1x1 with %d output channels; got %s / %s'
+                            % (up_w, tuple(W.shape), tuple(Wb.shape)))
+    for b in (bias_a, bias_b):
+        if b is not None and (b.numel() != up_w or not b.is_contiguous()):
+            raise _lib.HplError('weight_fold: a bias of %d entries, got %s' % (up_w, tuple(b.shape)))
+    if own_bias is not None and (own_bias.numel() != O or not own_bias.is_contiguous()):
+        raise _lib.HplError('weight_fold: the consumer\'s bias has %d entries, got %s' % (O, tuple(own_bias.shape)))
+    Cout = C - up_w + Cb + (4 if ones_col >= 0 else 0)
+    shape = (O, Cout) + tuple(W.shape[2:])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=W.device)
+    if dense_bias and out_bias is None:
+        out_bias = torch.empty((O,), dtype=torch.float32, device=W.device)
+    if tuple(out.shape) != shape or not out.is_contiguous() or (out_bias is not None and out_bias.numel() != O):
+        raise _lib.HplError('weight_fold: the folded weight is %s, got %s' % (shape, tuple(out.shape)))
+    check(_lib.load().hpl_weight_fold(ptr(W), O, C, F, up0, up_w, ptr(Wb), Cb, ptr(bias_a), ptr(bias_b), ones_col, ptr(out),
+                                      out.numel(), ptr(own_bias), ptr(out_bias), stream()), 'hpl_weight_fold')
+    return out, out_bias
+
+
+class FoldedWeight(object):
+    """A consumer's weight with the producer's bias-only 1x1 folded in (weight_fold), kept current: `weight` (and `bias` of a
+    folded dense layer) are allocated once and rewritten IN PLACE whenever one of the parameters they are made of has a new
+    version (or invalidate_weight_cache() ran), so the images made of them -- the native plan's bank, _cached_relayout of the
+    Python path -- refresh the way they do for a parameter.  The native plan and the Python path share one of these per
+    consumer (flownet._FlowNetBase.up_fold keeps them with the model): the same tensor, hence the same launches on the same bits."""
+
+    def __init__(self, W, F, up0, up_w, Wb, bias_a, bias_b, ones_col, own_bias, dense_bias):
+        self.src = (W, Wb, bias_a, bias_b, own_bias)
+        self.args = (F, up0, up_w, ones_col, dense_bias)
+        self.ptrs = self._ptrs()
+        self._keep = [None if p is None else p.detach() for p in self.src]      # the storages stay: their addresses are not reused
+        O = W.shape[0]
+        Cout = W.numel() // (O * F) - up_w + Wb.numel() // up_w + (4 if ones_col >= 0 else 0)
+        self.weight = torch.empty((O, Cout) + tuple(W.shape[2:]), dtype=torch.float32, device=W.device)
+        self.bias = torch.empty((O,), dtype=torch.float32, device=W.device) if dense_bias else None
+        self._sig = None
+        self._ev = self._stream = None
+
+    def _ptrs(self):
+        return tuple(None if p is None else p.data_ptr() for p in self.src)
+
+    def made_of(self, src, args):
+        return args == self.args and all(a is b for a, b in zip(src, self.src)) and self._ptrs() == self.ptrs
+
+    def ensure(self):
+        """Current values on the current stream -> self."""
+        sig = (weight_epoch(),) + tuple(None if p is None else p._version for p in self.src)
+        if sig != self._sig:
+            F, up0, up_w, ones_col, dense_bias = self.args
+            W, Wb, ba, bb, own = [None if p is None else p.detach() for p in self.src]
+            with torch.no_grad():
+                self.weight, self.bias = weight_fold(W, F, up0, up_w, Wb, ba, bb, ones_col, own, dense_bias, out=self.weight,
+                                                     out_bias=self.bias)
+            if self._sig is not None:                 # rewritten through its pointer: tell the caches keyed on the version
+                torch.autograd.graph.increment_version(self.weight)
+                if self.bias is not None:
+                    torch.autograd.graph.increment_version(self.bias)
+            self._sig = sig
+            self._ev = torch.cuda.Event()
+            self._ev.record()
+            self._stream = stream()
+        elif self._ev is not None and stream() != self._stream:
+            if self._ev.query():
+                self._ev = None
+            else:
+                torch.cuda.current_stream().wait_event(self._ev)
+        return self
+
+
 class SplitW(object):
     """Split image of a weight image: `planes` uint8 [P, k_rows/8 * ldw * 16] in MFMA B-fragment order -- P = 3: bf16 planes
     hi / mid / lo with Wt == hi + mid + lo exactly (hpl_weight_split3); P = 2: fp16 planes hi / lo of Wt * s, s the power of

@@ -26,6 +26,7 @@ from .flownet import DeviceLattice, PairBlur
 
 OP_GCONV, OP_SPLAT, OP_SLICE, OP_COPY, OP_LOAD = 1, 2, 3, 4, 5
 OP_GSUM, OP_INVERT = 16, 17
+F_NOYAMAX = 64        # HPL_FLAG_NOYAMAX
 TBL_NONE, TBL_BLUR_PAIR, TBL_BLUR0, TBL_CORR1, TBL_CORR2, TBL_REGULAR, TBL_CSR_PAIR, TBL_CSR_C0, TBL_CLOUD0 = range(9)
 ORD_NONE, ORD_PERM, ORD_GROUPS = 0, 1, 2
 SYM_ZERO, SYM_N0, SYM_N1, SYM_NP, SYM_LEVEL0 = -1, 0, 1, 2, 8
@@ -82,6 +83,7 @@ class _Program(object):
         self.combined = []          # (tensor, (param a, param b))
         self.meta = []              # per op: what train_plan needs to write its gradient (None: no gradient flows through it)
         self.wmeta = {}             # weight index -> (param, C, O, F, Ctot, c0)
+        self.folds = []             # ops.FoldedWeight of the folded form: refreshed in front of the bank's images
 
     def buf(self, rows_sym, cols):
         self.bufs.append((rows_sym, cols))
@@ -176,9 +178,9 @@ def _dense(P, x, conv, act, slope, M, out=None, rows_sym=None):
 
 
 def _conv_stack(P, x, mods, M, rows_sym, F, level, table, order, slope, out=None, reg_stride=SYM_ZERO, wide_tag=False,
-                out2=None, rows2=SYM_ZERO):
+                out2=None, rows2=SYM_ZERO, w0=None, flags=0):
     """bcl._run_conv_stack: first conv through `table` (F taps), the rest 1x1; returns the output ref.  out2 / rows2:
-    second destination of the LAST conv (_Program.gconv)."""
+    second destination of the LAST conv (_Program.gconv).  w0: the (folded) weight the first conv runs on; flags: of the LAST conv."""
     n = len(mods)
     for i, m in enumerate(mods):
         conv = _conv_of(m)
@@ -187,12 +189,15 @@ def _conv_stack(P, x, mods, M, rows_sym, F, level, table, order, slope, out=None
         final = i == n - 1
         o = out if (final and out is not None) else P.buf(rows_sym, O)
         second = dict(out2=out2, rows2=rows2) if (final and out2 is not None) else {}
+        if final and flags:
+            second['flags'] = flags
         if i == 0:
-            Ctot = conv.weight.numel() // (O * F)
+            w = conv.weight if w0 is None else w0
+            Ctot = w.numel() // (O * F)
             ordr = order
             if table == TBL_BLUR0:        # Up conv: tap-group passes for wide layers, else the single-pass order
                 ordr = ORD_GROUPS if conv.in_channels >= GROUPS_MIN_CHANNELS else ORD_PERM
-            P.gconv(x, o, M, Ctot, O, P.weight(conv.weight, Ctot, O, F, Ctot, 0), bias=P.bias(conv.bias), act=act,
+            P.gconv(x, o, M, Ctot, O, P.weight(w, Ctot, O, F, Ctot, 0), bias=P.bias(conv.bias), act=act,
                     slope=slope, F=F, level=level, table=table, order=ordr, reg_stride=reg_stride,
                     tag=TAG_WIDE_BLUR if (wide_tag and conv.in_channels >= GROUPS_MIN_CHANNELS) else TAG_OTHER, **second)
         else:
@@ -208,15 +213,23 @@ def _corr_width(model, L):
     return 64 if model.REFINE else getattr(model, 'corr%d' % (L - 1)).num_output[-1]
 
 
-def build_program(model, bank):
-    """The pair-batched inference forward of flownet._FlowNetBase.forward, op by op.  The input matrix of every Up
-    layer (the reference's torch.cat of el_minus_gr | upper Up output | correlation | Down features) is allocated up
+def build_program(model, bank, fold=False):
+    """The pair-batched inference forward of flownet._FlowNetBase.forward, op by op.  fold (ForwardPlan: model.fold_up()): the
+    folded form of DESIGN.md §23 -- an Up layer that ends in a bias-only 1x1 runs conv15 -> slice, its 1x1 and biases are in
+    the weights of the conv that reads its rows (model.up_fold) and a ones part (1, 0, 0, 0) beside el_minus_gr carries the
+    bias; False: every conv a launch of its own, the two orders of an Up layer under HPL_COND_SHRINK (training).
+    The input matrix of every Up layer (the reference's torch.cat of el_minus_gr | upper Up output | correlation | Down features) is allocated up
     front and every part is WRITTEN THERE BY ITS PRODUCER: the Up layer above and the correlation layer store straight
     into their columns, the Down layer's last conv stores its cloud-1 rows there as a second destination, the
     el_minus_gr columns are filled by one batched launch (csrc/executor.hip) -- no copy launches."""
     P = _Program(bank)
     nlev = model.NLEV
     sl = _slope(model.use_leaky)
+    folds = {}            # L -> ops.FoldedWeight of the consumer of bcn{L+1}_ (allocated here, computed by the plan: no launch)
+    if fold:
+        for L in range(nlev):
+            folds[L] = model.up_fold(L, ensure=False)
+        P.folds = [folds[L] for L in range(nlev)]
     # ---- the Up layers' input matrices: xb[L] = [H0(L), parts], cols[L] = {part: (column offset, width)}
     xb, cols = {}, {}
     up_w = None
@@ -224,7 +237,10 @@ def build_program(model, bank):
         layer = getattr(model, 'bcn%d_' % (L + 1))
         parts = []
         if L < nlev - 1:
-            parts += [('emg', 4), ('up', up_w)]
+            parts.append(('emg', 4))
+            if fold and folds[L + 1].args[3] >= 0:
+                parts.append(('ones', 4))
+            parts.append(('up', up_w))
         if L >= 2:
             parts.append(('corr', _corr_width(model, L)))
         parts.append(('down', getattr(model, 'bcn%d' % (L + 1)).num_output[-1]))
@@ -234,9 +250,9 @@ def build_program(model, bank):
         for kind, w in parts:
             cols[L][kind] = (col, w)
             col += w
-        assert col == layer.num_input, (L, col, layer.num_input)
+        assert col - cols[L].get('ones', (0, 0))[1] == layer.num_input, (L, col, layer.num_input)
         xb[L] = P.buf(lsym(L, S_H0), col)
-        up_w = layer.num_output[-1]
+        up_w = layer.blur_conv[-1].weight.shape[1] if fold else layer.num_output[-1]      # folded: the rows in front of the 1x1
 
     def part(L, kind):
         return xb[L].columns(*cols[L][kind])
@@ -270,27 +286,43 @@ def build_program(model, bank):
     # ---- Up path: every layer writes into the 'up' columns of the level below
     for L in reversed(range(nlev)):
         layer = getattr(model, 'bcn%d_' % (L + 1))
+        w0 = folds[L + 1].weight if (fold and L < nlev - 1) else None
         if L < nlev - 1:
-            P.copy(None, part(L, 'emg'), lsym(L, S_H0), 4, level=L + 1)     # el_minus_gr of cloud 1 at level L+1
+            if 'ones' in cols[L]:                # el_minus_gr | 1, 0, 0, 0 in one copy
+                P.copy(None, xb[L].columns(cols[L]['emg'][0], 8), lsym(L, S_H0), 8, level=L + 1)
+            else:
+                P.copy(None, part(L, 'emg'), lsym(L, S_H0), 4, level=L + 1)     # el_minus_gr of cloud 1 at level L+1
         if L > 0:
-            _up_layer(P, (layer, L), xb[L], part(L - 1, 'up'), sl)
+            _up_layer(P, (layer, L), xb[L], part(L - 1, 'up'), sl, fold, w0)
     # the last Up layer writes a fresh [N0, HEAD_IN] matrix
     layer = getattr(model, 'bcn1_')
-    ybuf = P.buf(SYM_N0, layer.num_output[-1])
-    _up_layer(P, (layer, 0), xb[0], ybuf, sl)
-    y = _dense(P, ybuf, model.conv2.conv, True, sl, SYM_N0, rows_sym=SYM_N0)
+    ybuf = P.buf(SYM_N0, up_w)
+    _up_layer(P, (layer, 0), xb[0], ybuf, sl, fold, folds[1].weight if fold else None)
+    if fold:              # conv2 on bcn1_'s pre-1x1 rows: weight W2 Wb, bias W2 b_tot + b2
+        f, O2 = folds[0], model.conv2.conv.weight.shape[0]
+        y = P.buf(SYM_N0, O2)
+        P.gconv(ybuf, y, SYM_N0, up_w, O2, P.weight(f.weight, up_w, O2, 1, up_w, 0), bias=P.bias(f.bias), act=1, slope=sl)
+    else:
+        y = _dense(P, ybuf, model.conv2.conv, True, sl, SYM_N0, rows_sym=SYM_N0)
     y = _dense(P, y, model.conv3.conv, True, sl, SYM_N0, rows_sym=SYM_N0)
     _dense(P, y, model.conv4, False, sl, SYM_N0, out=_R(BUF_OUT, 3))
     return P
 
 
-def _up_layer(P, layer_L, xb, out, sl):
+def _up_layer(P, layer_L, xb, out, sl, fold=False, w0=None):
     """bcl.BilateralConvFlex.forward_cl for an Up layer (no splat, slice).  When the last conv is a bias-only 1x1
     and the slice shrinks the row count (input points < vertices: decided per pair, HPL_COND_SHRINK) the 1x1 conv
-    runs AFTER the slice on the sliced rows; otherwise the full stack, then slice + bias."""
+    runs AFTER the slice on the sliced rows; otherwise the full stack, then slice + bias.  fold: that 1x1 and the biases
+    are in the consumer's weights: one sequence, the stack without it -> slice; w0: the folded weight of the first conv."""
     layer, L = layer_L[0], layer_L[1]
     H0, IN0 = lsym(L, S_H0), lsym(L, S_IN0)
     mods = list(layer.blur_conv)
+    if fold:
+        # (the slice reads the result, no wide launch does: its largest magnitude is not reduced)
+        y = _conv_stack(P, xb, mods[:-1], H0, H0, layer.filter_size, L, TBL_BLUR0, ORD_PERM, sl, wide_tag=L <= 1, w0=w0,
+                        flags=F_NOYAMAX)
+        P.slice(y, out, L, IN0, mods[-1].weight.shape[1])
+        return
     bias = layer.bias if (layer.use_bias and layer.do_slice) else None
     wide = L <= 1                      # profiling class of the two big stencil convs (bcn1_, bcn2_)
     reorder = len(mods) >= 2 and not isinstance(mods[-1], _ConvReLU)
@@ -482,7 +514,10 @@ class ForwardPlan(object):
         self._fence = {}
 
     def _program(self, model):
-        return build_program(model, self.bank)
+        P = build_program(model, self.bank, fold=model.fold_up())
+        for f in P.folds:
+            f.ensure()
+        return P
 
     def __del__(self):
         try:
@@ -534,6 +569,8 @@ class ForwardPlan(object):
             for ev in self._fence.values():
                 if ev is not None and not ev.query():
                     cur.wait_event(ev)
+            for f in self.prog.folds:             # the folded weights first: the bank's images are made of them
+                f.ensure()
             self.bank.refresh()
             for img, w3 in self._split3.values():
                 ops.weight_split3(img, out=w3)

@@ -370,7 +370,7 @@ class TrainPlan(ForwardPlan):
 
     # ---- program: forward (plan.build_program) + loss + backward, then the un-layout ops where their buckets are complete
     def _program(self, model):
-        P = build_program(model, self.bank)
+        P = build_program(model, self.bank, fold=False)       # (the backward needs the two factors of an Up layer apart)
         self.n_fwd = len(P.ops)
         self._n_fwd_jobs, self._n_fwd_weights = len(self.bank.jobs), len(P.weights)      # what the forward needs of the bank
         B = _Backward(P, model, self.params)

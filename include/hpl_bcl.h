@@ -152,6 +152,21 @@ typedef struct hpl_relayout_job {
 int hpl_weight_relayout_batch(const hpl_relayout_job *jobs /* DEVICE */, int njobs,
                               const int64_t *prefix /* DEVICE, njobs + 1 */, int64_t total, float *dst,
                               hplStream stream);
+/* Fold of a bias-only 1x1 conv into the conv that reads its result.  W is the consumer's weight in the
+ * parameter's own layout [O][C][F] (Conv2d (O,C,F,1) / Conv1d (O,C,1)); its columns [up0, up0 + up_w) read
+ * Wb u + b_tot, Wb [up_w][Cb] the producer's trailing 1x1 and b_tot = bias_a + bias_b (either or both may be NULL; both
+ * given: their fp32 sum).  out [O][Cout][F], same layout, reads u instead:
+ *   columns of W before the up block: copied;  up block: out[o][up0' + j][f] = sum_k W[o][up0 + k][f] Wb[k][j], j < Cb;
+ *   columns behind it: copied;  ones_col >= 0 (<= up0, needs b_tot): four columns are inserted at ones_col, the first
+ *   holds sum_k W[o][up0 + k][f] b_tot[k] -- the weight of a constant-1 input column --, the other three are zero.
+ * Cout = C - up_w + Cb + (ones_col >= 0 ? 4 : 0); out_elems = O * Cout * F (checked).
+ * out_bias (F == 1 only; [O]): own_bias[o] (NULL: 0) + sum_k W[o][up0 + k] b_tot[k] -- the bias of a folded dense layer.
+ * A b_tot that neither ones_col nor out_bias takes up is refused.  Every sum runs in double in the order of k and is
+ * rounded to fp32 once; no atomics: the same inputs give the same bits. */
+int hpl_weight_fold(const float *W, int O, int C, int F, int up0, int up_w, const float *Wb, int Cb,
+                    const float *bias_a, const float *bias_b, int ones_col, float *out, int64_t out_elems,
+                    const float *own_bias, float *out_bias, hplStream stream);
+
 /* mirror == 2 ("taps as column blocks"): the image is [roundup(R, 32)][ldw >= F*Q] with element (r, f*Q + q) =
  * W[base + r*sr + q*sq + f*sf] -- the operand of the scatter / regular data gradients of the correlation layer
  * (models/bnn_flow.py:202-205 backward: G[m, (f, c)] = g[m] . W[:, c, f]). */
@@ -564,6 +579,8 @@ int hpl_lattice_next_points(const int32_t *vkeys, int64_t vstride, int64_t H, fl
 #define HPL_OP_SPLAT 2        /* hpl_splat */
 #define HPL_OP_SLICE 3        /* hpl_slice */
 #define HPL_OP_COPY 4         /* out[:, cols] = a[:, cols]   (the torch.cat calls of the reference forward) */
+                              /* a.buf == -1: el_minus_gr of `level`, C == 4; C == 8: el_minus_gr | 1, 0, 0, 0 (the constant input
+                               * column of a folded bias, hpl_weight_fold) */
 #define HPL_OP_LOAD 5         /* out rows = transpose of an external (3, N) cloud (ext: 0 = pc1, 1 = pc2) */
 
 /* Training (hpl_plan_run_range): the backward of the same program as more operations of the same plan.  Each is the
@@ -589,6 +606,7 @@ int hpl_lattice_next_points(const int32_t *vkeys, int64_t vstride, int64_t H, fl
 #define HPL_FLAG_TAPS 4       /* wgrad: sum over the per-tap vertex lists of the level's cloud-1 blur table (when the run has them) */
 #define HPL_FLAG_INVERSE 16   /* HPL_OP_GSUM: see there */
 #define HPL_FLAG_SIDE 8       /* the op is a leaf of the backward graph: it may run on the side stream of hpl_plan_run_range */
+#define HPL_FLAG_NOYAMAX 64   /* gconv: no wide launch reads the result (a slice does): its largest magnitude is not reduced */
 #define HPL_FLAG_NOGUARD 32   /* gconv: the fp16-pair form of this op runs WITHOUT its range guard (hpl_gconv_desc.a_guard): the data gradients
                                  of the training program -- a quiet row of a gradient matrix is a vertex whose share of every weight gradient
                                  lies below the rounding of the sums; the guard would run their launches twice (round 6: 1.4 ms of a step) */
