@@ -211,6 +211,10 @@ _SIGNATURES = {
     'hpl_ground_fit': (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_f32), c_f32, ctypes.c_int,
                                       c_f32, ctypes.c_int, c_f32, ctypes.c_uint64, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_vp, c_vp, c_i64, c_vp]),
+    'hpl_voxel_downsample_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, ctypes.c_int]),
+    'hpl_voxel_downsample': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i64), c_f32,
+                                            ctypes.POINTER(c_f32), ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp, c_i64, c_vp]),
     'hpl_plan_create': (c_vp, [ctypes.POINTER(Op), ctypes.c_int, ctypes.POINTER(Buf), ctypes.c_int,
                                ctypes.POINTER(Weight), ctypes.c_int, ctypes.POINTER(c_vp), ctypes.c_int]),
     'hpl_plan_destroy': (None, [c_vp]),
@@ -283,6 +287,8 @@ def load_diag():
                                               ctypes.c_int64, ctypes.c_int, c_vp]
         lib.hpl_diag_chain.restype = ctypes.c_int
         lib.hpl_diag_chain.argtypes = [c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp]
+        lib.hpl_diag_sort_pairs64.restype = ctypes.c_int64
+        lib.hpl_diag_sort_pairs64.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_vp]
         _diag = lib
     return _diag
 

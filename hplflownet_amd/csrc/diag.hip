@@ -5,6 +5,8 @@
 
 #include "../../include/hpl_diag.h"
 
+#include <rocprim/device/device_radix_sort.hpp>
+
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 #define HPL_REQUIRE(cond, ...) do { if (!(cond)) return -1; } while (0)
 #define HPL_CHECK_LAUNCH(name) do { if (hipGetLastError() != hipSuccess) return -2; } while (0)
@@ -308,4 +310,17 @@ extern "C" int hpl_diag_chain(float *a, float *b, int grid, int words, int steps
     }
     HPL_CHECK_LAUNCH("hpl_diag_chain");
     return HPL_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- the voxel grid's sort alone
+extern "C" int64_t hpl_diag_sort_pairs64(const uint64_t *keys, uint64_t *keys_out, const int32_t *vals, int32_t *vals_out, int64_t n,
+                                         int bits, void *temp, int64_t temp_bytes, void *stream) {
+    if (n < 0 || bits < 1 || bits > 64) return -1;
+    size_t need = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, need, keys, keys_out, vals, vals_out, (size_t)n, 0u, (unsigned)bits, (hipStream_t) nullptr);
+    if (!temp) return (int64_t)need;
+    if (!keys || !keys_out || !vals || !vals_out || temp_bytes < (int64_t)need) return -1;
+    size_t tb = (size_t)temp_bytes;
+    return rocprim::radix_sort_pairs(temp, tb, keys, keys_out, vals, vals_out, (size_t)n, 0u, (unsigned)bits,
+                                     static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -2;
 }

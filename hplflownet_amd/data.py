@@ -337,12 +337,25 @@ class KITTI(_PairFolder):
     #: the keyword arguments of flownet.remove_ground that `ground` may hold
     GROUND_KEYS = ('up', 'max_tilt_deg', 'hyps', 'tau', 'refine', 'cut')
 
-    def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None, ground=None):
+    def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None, ground=None,
+                 voxel=None, voxel_mode='centroid'):
         """remove_ground: True -- the reference's rule, a correspondence is dropped when y < -1.4 in both clouds --, False, or
         'plane': the same pair rule on a plane fitted to each cloud on the device (flownet.remove_ground(corr=True, seed=0,
-        call=<frame number>, **ground), DESIGN.md §21: a frame's result does not depend on the order of reading)."""
-        from . import _lib
+        call=<frame number>, **ground), DESIGN.md §21: a frame's result does not depend on the order of reading).
+        voxel (None: off): after the ground removal and before the transform samples its points, the pair is put on a voxel
+        grid of that edge on the device (flownet.voxel_downsample(corr=True, voxel=voxel, mode=voxel_mode)):
+        one correspondence per occupied cell of pc1."""
+        from . import _lib, ops
         super(KITTI, self).__init__(transform, device)
+        if voxel is not None:
+            if torch.device(device).type != 'cuda':
+                raise _lib.HplError('KITTI: voxel downsamples on the device, got device %s (there is no CPU fallback)' % (device,))
+            if voxel_mode not in ops.VOXEL_MODES:
+                raise _lib.HplError('KITTI: voxel_mode = %r (%s)' % (voxel_mode, ' or '.join(repr(m) for m in ops.VOXEL_MODES)))
+            ops.voxel_args('KITTI', voxel, (0, 0, 0), voxel_mode)
+        elif voxel_mode != 'centroid':
+            raise _lib.HplError('KITTI: voxel_mode applies to voxel=<edge>')
+        self.voxel, self.voxel_mode = voxel, voxel_mode
         self.root = os.path.join(data_root, 'KITTI_processed_occ_final')
         if remove_ground not in (True, False, 'plane'):
             raise _lib.HplError('KITTI: remove_ground = %r (True, False or \'plane\')' % (remove_ground,))
@@ -391,4 +404,9 @@ class KITTI(_PairFolder):
         elif self.remove_ground:
             keep = ~((pc1[:, 1] < -1.4) & (pc2[:, 1] < -1.4))
             pc1, pc2 = pc1[keep], pc2[keep]
+        if self.voxel is not None:
+            from .flownet import voxel_downsample
+            t1, t2 = (torch.from_numpy(np.ascontiguousarray(p[:, :3].T, dtype=np.float32)).to(self.device) for p in (pc1, pc2))
+            v1, v2 = voxel_downsample(t1, t2, voxel=self.voxel, mode=self.voxel_mode, corr=True)[:2]
+            pc1, pc2 = (np.ascontiguousarray(v[0].t().cpu().numpy()) for v in (v1, v2))
         return pc1, pc2

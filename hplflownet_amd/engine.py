@@ -722,6 +722,12 @@ def parse_args(argv=None):
                     help='--dataset KITTI: how the reader removes the ground: threshold -- the reference\'s rule, a correspondence '
                          'with y < -1.4 in both clouds is dropped (default) --, or plane: the same pair rule on a plane fitted to '
                          'each cloud on the device (DESIGN.md §21)')
+    ap.add_argument('--voxel', type=float, default=None, metavar='V',
+                    help='--dataset KITTI: put every frame on a voxel grid of edge V metres (finite and > 0) on the device after '
+                         'the ground removal and before the sampling of --points: one correspondence per occupied cell '
+                         '(flownet.voxel_downsample, DESIGN.md §24); default off')
+    ap.add_argument('--voxel-mode', default=None, choices=['centroid', 'nearest'],
+                    help='--voxel: a cell becomes the mean of its points (centroid, the default) or the point nearest to it')
     ap.add_argument('--ground-tau', type=float, default=None, metavar='TAU',
                     help='--ground plane: inlier distance of the fit in metres (finite and > 0, default 0.1)')
     ap.add_argument('--ground-cut', type=float, default=None, metavar='C',
@@ -799,6 +805,12 @@ def parse_args(argv=None):
                     'hyps': 256 if a.ground_hyps is None else a.ground_hyps,
                     'max_tilt_deg': 20.0 if a.ground_tilt is None else a.ground_tilt,
                     'up': (0.0, 1.0, 0.0) if a.ground_up is None else tuple(a.ground_up)} if on else None
+    if a.voxel is not None and a.dataset != 'KITTI':
+        ap.error('--voxel applies to --dataset KITTI')
+    if a.voxel is not None and not 0 < a.voxel < float('inf'):
+        ap.error('--voxel takes a finite value > 0')
+    if a.voxel_mode is not None and a.voxel is None:
+        ap.error('--voxel-mode applies to --voxel')
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -918,7 +930,8 @@ def _real_data(a, tr, dev, rank, world):
         augment = lambda: data_mod.Augmentation(AUG_TOGETHER, AUG_PC2, DATA_PROCESS, a.points, False, seed=1 + rank)  # noqa: E731
     if a.dataset == 'KITTI':                        # evaluation only in the reference
         val = data_mod.KITTI(process(True), a.data_root, device=dev, calib_dir=a.kitti_calib,
-                             remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit)
+                             remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit, voxel=a.voxel,
+                             voxel_mode=a.voxel_mode or 'centroid')
         train = None
         if a.kitti_calib is None:
             log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')

@@ -788,6 +788,68 @@ def remove_ground(pc1, pc2, sf=None, corr=True, return_mask=False, **kw):
     return res + (masks,) if return_mask else res
 
 
+# ----------------------------------------------------------------------------- voxel-grid downsampling
+def voxel_downsample(pc1, pc2=None, sf=None, voxel=0.1, mode='centroid', corr=True, origin=(0, 0, 0), return_index=False):
+    """The pair(s) on a voxel grid of edge `voxel`, one point per occupied cell, by ONE ops.voxel_downsample call (DESIGN.md
+    §24).  pc1 / pc2 / sf in the forms remove_ground takes: (3, N) tensors (one pair), (B, 3, N) tensors, or lists of B
+    (3, N_b) tensors; pc2 and sf may be None.  mode 'centroid' (the cell's mean) or 'nearest' (the member nearest to it: the
+    output is a subset of the input).
+    corr=True (the clouds of a pair correspond point to point, so they hold as many points): pc1's cells decide; pc2 and sf
+    ride as attribute channels, so a pair stays a pair and pc2' - pc1' equals sf' up to the rounding of the means -- exactly
+    in mode 'nearest'.  At most 64 pairs a call.
+    corr=False: the 2 B clouds -- the pc1 clouds first, then the pc2 clouds -- are each voxelised on their own; sf follows pc1.
+    At most 32 pairs a call.
+    One read-back: the voxel counts.
+    -> (pc1 list of (3, V_b), pc2 list or None, sf list or None, stats (B, 4) int32 -- corr=False with pc2: (2, B, 4) --
+    [, voxel_of list, rep list]): return_index appends, per voxelised cloud (corr=False: the pc1 clouds, then the pc2 clouds),
+    voxel_of (n_b,) int64 -- every input point's column in the cloud's output, -1 for a point of no voxel -- and rep (V_b,)
+    int64, the member nearest to the mean as an index into the cloud."""
+    who = 'voxel_downsample'
+    ops.voxel_args(who, voxel, origin, mode)
+    c1 = _clouds(pc1, who, 'pc1')
+    c2 = _clouds(pc2, who, 'pc2') if pc2 is not None else None
+    fl = _clouds(sf, who, 'sf') if sf is not None else None
+    B = len(c1)
+    if (c2 is not None and len(c2) != B) or (fl is not None and (len(fl) != B or any(f.shape[1] != c.shape[1] for f, c in zip(fl, c1)))):
+        raise _lib.HplError('%s: pc1, pc2 and sf hold as many clouds, and sf as many points as pc1' % who)
+    joint = corr or c2 is None
+    if corr and c2 is not None and any(a.shape[1] != b.shape[1] for a, b in zip(c1, c2)):
+        raise _lib.HplError('%s: corr=True takes clouds that correspond point to point (as many points in pc1 and pc2)' % who)
+    if not 1 <= (B if joint else 2 * B) <= 64:
+        raise _lib.HplError('%s: %d pairs (1 .. %d a call)' % (who, B, 64 if joint else 32))
+    clouds = c1 if joint else c1 + c2
+    prefix = [0]
+    for c in clouds:
+        prefix.append(prefix[-1] + int(c.shape[1]))
+    pc = torch.cat(clouds, dim=1)
+    n1 = prefix[B]
+    riders = []
+    if joint and c2 is not None:
+        riders.append(torch.cat(c2, dim=1))
+    if fl is not None:
+        f = torch.cat(fl, dim=1)
+        riders.append(f if joint else torch.cat([f, f.new_zeros((3, prefix[-1] - n1))], dim=1))
+    attrs = torch.cat(riders, dim=0) if riders else None
+    out_pc, out_attrs, _, rep, voxel_of, stats = ops.voxel_downsample(pc, attrs, voxel=voxel, origin=origin, mode=mode, prefix=prefix)
+    V = stats[:, 0].cpu().tolist()                                              # the one read-back
+    cols = [out_pc[:, prefix[b]:prefix[b] + V[b]] for b in range(len(clouds))]
+    o1 = cols[:B]
+    o2 = None if c2 is None else cols[B:] if not joint else [out_attrs[:3, prefix[b]:prefix[b] + V[b]] for b in range(B)]
+    of = None
+    if fl is not None:
+        r0 = out_attrs.shape[0] - 3
+        of = [out_attrs[r0:, prefix[b]:prefix[b] + V[b]] for b in range(B)]
+    res = (o1, o2, of, stats if joint else stats.view(2, B, 4))
+    if return_index:
+        vo, rp = [], []
+        for b in range(len(clouds)):
+            w = voxel_of[prefix[b]:prefix[b + 1]].long()
+            vo.append(torch.where(w >= 0, w - prefix[b], w))
+            rp.append(rep[prefix[b]:prefix[b] + V[b]].long() - prefix[b])
+        res += (vo, rp)
+    return res
+
+
 # ----------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(flow, pc1, pc2, k=8, w_chamfer=1.0, w_smooth=1.0):
     """The self-supervised loss of a forward's flow in ONE ops.selfsup_loss call: Chamfer distance between

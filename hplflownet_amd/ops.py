@@ -672,6 +672,89 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
     return res
 
 
+# --------------------------------------------------------------------------- voxel-grid downsampling
+VOXEL_MODES = {'centroid': 0, 'nearest': 1}
+
+
+def voxel_args(who, voxel, origin, mode):
+    """(voxel as the float32 the library takes, origin as three floats, the mode's number) or an HplError."""
+    import struct
+    try:
+        v = struct.unpack('f', struct.pack('f', float(voxel)))[0]
+    except (TypeError, ValueError, OverflowError):
+        v = float('nan')
+    if isinstance(voxel, bool) or not (v > 0 and v < float('inf')):
+        raise _lib.HplError('%s: voxel = %r (finite and > 0 as a float32)' % (who, voxel))
+    try:
+        org = [float(x) for x in origin]
+    except (TypeError, ValueError):
+        org = []
+    if len(org) != 3 or not all(abs(x) <= 3.4028234663852886e38 for x in org):
+        raise _lib.HplError('%s: origin = %r (three finite numbers)' % (who, origin))
+    if mode not in VOXEL_MODES:
+        raise _lib.HplError('%s: mode = %r (%s)' % (who, mode, ' or '.join(repr(m) for m in VOXEL_MODES)))
+    return v, org, VOXEL_MODES[mode]
+
+
+def voxel_downsample(pc, attrs=None, voxel=0.1, origin=(0, 0, 0), mode='centroid', prefix=None, out=None):
+    """hpl_voxel_downsample on the current stream: one point per occupied cell of the grid of edge `voxel`
+    anchored at `origin` -- mode 'centroid': the mean of the cell's points; 'nearest': the member nearest to that mean, bit for
+    bit, so the output is a subset of the input.  pc (3, N) float32 (rows may be views of a wider buffer); attrs (C, N) float32,
+    C <= 8, or None: channels that are averaged (or picked) with their points; prefix (host sequence of B + 1 ints from 0 to
+    N): B <= 64 clouds, each voxelised on its own.  A cloud's voxels are numbered in ascending (cell_x, cell_y, cell_z) order;
+    voxel v of cloud b is column prefix[b] + v of every per-voxel output, and the columns behind a cloud's V_b voxels hold 0
+    (rep: -1).  A point that is not finite, or whose cell lies outside +-(2^18 - 2), belongs to no voxel.
+    -> (out_pc (3, N) float32, out_attrs (C, N) float32 or None, count (N,) int32, rep (N,) int32: the packed index of the member
+    nearest to the mean, voxel_of (N,) int32: every point's voxel column or -1 -- a per-voxel result goes back to the points
+    as values[:, voxel_of] --, stats (B, 4) int32 = (V_b, valid, non-finite, out-of-range points)).  out: a (3, N) float32
+    tensor with unit stride along the points that takes out_pc; it must not overlap pc or attrs.  The same bits for a cloud
+    alone and in any batch.  No autograd, no host synchronisation, no read-back: V_b stays on the device."""
+    who = 'voxel_downsample'
+    v, org, m = voxel_args(who, voxel, origin, mode)
+    pc, pc_ld = _soa3(pc, 'pc', who)
+    N, dev = pc.shape[1], pc.device
+    C, attr_ld = 0, 0
+    if attrs is not None:
+        if not torch.is_tensor(attrs) or attrs.dim() != 2 or attrs.shape[1] != N or attrs.dtype != torch.float32 or \
+                attrs.device != dev or not 1 <= attrs.shape[0] <= 8:
+            raise _lib.HplError('%s: attrs must be a (C, %d) float32 tensor on %s with 1 <= C <= 8, got %s' % (
+                who, N, dev, (tuple(attrs.shape), attrs.dtype, attrs.device) if torch.is_tensor(attrs) else type(attrs)))
+        if attrs.requires_grad:
+            raise _lib.HplError('%s has no autograd: attrs requires grad' % who)
+        C = attrs.shape[0]
+        if (C > 1 and attrs.stride(0) < max(N, 1)) or (N > 1 and attrs.stride(1) != 1):
+            attrs = attrs.contiguous()
+        attr_ld = max(N, 1) if C == 1 or attrs.is_contiguous() else attrs.stride(0)
+    pp = _prefix(prefix, N, who)
+    B = len(pp) - 1
+    if out is not None:
+        if not torch.is_tensor(out) or tuple(out.shape) != (3, N) or out.dtype != torch.float32 or out.device != dev or \
+                out.requires_grad or out.stride(0) < max(N, 1) or (N > 1 and out.stride(1) != 1):
+            raise _lib.HplError('%s: out must be a (3, %d) float32 tensor on %s with unit stride along the points' % (who, N, dev))
+        out_pc = out
+    else:
+        out_pc = torch.empty((3, N), dtype=torch.float32, device=dev)
+    out_ld = max(N, 1) if out_pc.is_contiguous() else out_pc.stride(0)
+    out_attrs = torch.empty((C, N), dtype=torch.float32, device=dev) if C else None
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    rep = torch.empty(N, dtype=torch.int32, device=dev)
+    voxel_of = torch.empty(N, dtype=torch.int32, device=dev)
+    if N == 0:                                   # nothing to launch: every cloud is empty
+        return out_pc, out_attrs, count, rep, voxel_of, torch.zeros((B, 4), dtype=torch.int32, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.hpl_voxel_downsample_workspace_bytes(B, N, C)
+    if nbytes < 0:
+        raise _lib.HplError('%s: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (who, B, N))
+    st = stream()
+    ws = _workspace(who, dev, st, nbytes)
+    check(lib.hpl_voxel_downsample(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, (ctypes.c_int64 * (B + 1))(*pp), v,
+                                   (ctypes.c_float * 3)(*org), m, out_pc.data_ptr(), out_ld, ptr(out_attrs), max(N, 1),
+                                   count.data_ptr(), rep.data_ptr(), voxel_of.data_ptr(), stats.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), st), 'hpl_voxel_downsample')
+    return out_pc, out_attrs, count, rep, voxel_of, stats
+
+
 # --------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None, prefix2=None, need_grad=True,
                  return_neighbors=False, out=None):

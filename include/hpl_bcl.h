@@ -1088,6 +1088,53 @@ int hpl_ground_fit(const float *pc, int64_t pc_ld, int batch, const int64_t *pre
                    float *height /* (N) or NULL */, uint8_t *ground /* (N) or NULL */, int32_t *keep_idx /* (N) or NULL */,
                    void *workspace, int64_t workspace_bytes, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Voxel-grid downsampling (csrc/voxel_grid.hip): one point per occupied cell of a grid of edge `voxel` -- the cell's centroid
+ * or the member nearest to it --, with attribute channels riding along and every point's voxel.
+ * ------------------------------------------------------------------------ */
+#define HPL_VOXEL_CENTROID 0
+#define HPL_VOXEL_NEAREST 1
+/* Workspace of hpl_voxel_downsample for `batch` clouds of n_total points together and `channels` attribute channels, in bytes
+ * (monotone in all three); -1 for a batch outside 1 .. 64, channels outside 0 .. 8 or n_total outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_voxel_downsample_workspace_bytes(int batch, int64_t n_total, int channels);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N); attr (channels, N) float32 SoA (row stride attr_ld >= N) riding along,
+ * channels 0 .. 8 (attr may be NULL with channels == 0).  batch (1 .. 64) clouds: prefix (HOST, batch + 1 ints from 0 to N,
+ * non-decreasing, empty clouds allowed) travels in the kernel arguments.  voxel > 0 finite; origin (HOST, 3 floats, finite);
+ * mode HPL_VOXEL_CENTROID or HPL_VOXEL_NEAREST.
+ * CELL: inv = 1.0 / (double)voxel; cell_k = floor(((double)x_k - (double)origin_k) * inv) for k = x, y, z, every operation in
+ * float64, rounded once, no contraction.  A point is VALID when its three coordinates are finite and |cell_k| <= 2^18 - 2 on
+ * every axis (the range of hpl_motion_segment).  A non-finite point counts in stats[b][2], a finite one out of range in
+ * stats[b][3].  Points of different clouds never share a voxel.
+ * VOXELS: a cloud's voxels are the distinct cells of its valid points, numbered 0 .. V_b - 1 in ascending lexicographic order
+ * of the signed (cell_x, cell_y, cell_z).  Voxel v of cloud b lives at packed position prefix[b] + v of every per-voxel
+ * output; the outputs have the input's capacity N (V_b <= n_b).
+ * PER VOXEL: count, the number of members.  The centroid c, per coordinate: the float64 sum of the float32 members in
+ * ascending point index, one after the other, from 0, divided by the count (as a float64) and rounded once to float32; every
+ * attribute channel is averaged the same way.  rep, the member nearest to that float32 centroid by the arithmetic of
+ * hpl_knn_interp: float32 d2 = (dx * dx + dy * dy) + dz * dz, no contraction, members in index order, the first member
+ * enters and is replaced only by a strictly smaller d2 (ties go to the smaller index); rep is an index into the packed arrays.
+ * OUTPUTS: out_pc (3, N) (row stride out_ld >= N) and out_attr (channels, N) (row stride out_attr_ld >= N): in mode CENTROID
+ * the means, in mode NEAREST the representative's coordinates and attributes bit for bit (the output is then a subset of the
+ * input).  count (N), rep (N) int32.  voxel_of (N) int32: for every input point the packed position of its voxel, -1 for a
+ * point that is not valid: a per-voxel result goes back to the points as values[:, voxel_of].  Behind a cloud's V_b voxels the
+ * rest of its range is 0 in out_pc / out_attr / count and -1 in rep.  stats [batch][4] int32: V_b, valid points, non-finite
+ * points, points out of range.  out_attr, count, rep and voxel_of may each be NULL.  A non-finite attribute of a valid point
+ * reaches its voxel's mean (it is not hidden) and no other voxel.
+ * Counts are integers (integer atomic adds commute); no floating-point atomic: a cloud's outputs are the same bits alone,
+ * anywhere in a batch and beside other work.  Stream-ordered, a fixed number of launches whose sizes depend on N, batch and
+ * channels alone, no copy back, no host synchronisation (V_b is known on the device only); no lane or workgroup waits for
+ * another.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_voxel_downsample_workspace_bytes(batch, N, channels).
+ * HPL_EINVAL before any launch (and without a device): batch, channels, mode, voxel or origin out of range or NaN; a prefix
+ * that does not start at 0 or decreases; a row stride below N; null pc / prefix / origin / out_pc / stats / workspace, null
+ * attr with channels > 0; misaligned arrays; a workspace that is too small or misaligned; N >= 2^31 / 3; an output overlapping
+ * an input.  N == 0 is a no-op. */
+int hpl_voxel_downsample(const float *pc, int64_t pc_ld, const float *attr, int64_t attr_ld, int channels, int batch,
+                         const int64_t *prefix /* HOST */, float voxel, const float *origin /* HOST, 3 */, int mode,
+                         float *out_pc, int64_t out_ld, float *out_attr, int64_t out_attr_ld, int32_t *count, int32_t *rep,
+                         int32_t *voxel_of, int32_t *stats /* [batch][4] */, void *workspace, int64_t workspace_bytes,
+                         hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif

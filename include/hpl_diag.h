@@ -36,6 +36,12 @@ int hpl_diag_splat_atomic(const float *feat, int64_t ldf, int C, const float *ba
  * the result of step steps - 1 is in (steps odd ? b : a): every element = its start value + steps.  tools/bench_chain.py. */
 int hpl_diag_chain(float *a, float *b, int grid, int words, int steps, unsigned *bar, int mode, void *stream);
 
+/* The sort of hpl_voxel_downsample alone (tools/voxel_bench.py: the floor of that call): rocPRIM's stable radix sort of n
+ * (64-bit key, int32 value) pairs over the key bits 0 .. bits - 1.  temp NULL: returns the temporary bytes the sort needs;
+ * otherwise 0, -1 (bad argument, temp_bytes too small) or -2 (HIP). */
+int64_t hpl_diag_sort_pairs64(const uint64_t *keys, uint64_t *keys_out, const int32_t *vals, int32_t *vals_out, int64_t n, int bits,
+                              void *temp, int64_t temp_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
