@@ -29,6 +29,12 @@ is a property of the reader (`has_cameras`), and every sample it returns carries
 utils/geometry.py:project_3d_to_2d); KITTI has `P_rect_02` of `calib_cam_to_cam/<frame>.txt` (utils/geometry.py:15-31), read
 from `calib_dir` at construction -- without it the reader has no cameras.
 
+* `KITTIRaw` / `FlyingThings3DRaw`: the same readers over the RAW downloads -- disparity, optical-flow and occlusion maps --
+  which the reference turns into the processed trees offline (data_preprocess/process_kitti.py,
+  process_flyingthings3d_subset.py).  Here the frames are back-projected on the device when they are read
+  (flownet.frames_from_kitti / frames_from_ft3d), bit for bit what the scripts save; `read_png`, `read_pfm` and
+  `read_flo` read the raw files (data_preprocess/IO.py, kitti_utils.py:29-36) without scipy or pypng.
+
 The reference asserts the canonical sample counts (19 640 / 3 824 / 200) and exits; here a
 mismatch is reported by `check_counts()` and left to the caller.  No dataset is available in the
 build environment: the readers are exercised on synthetic directory trees of the same layout
@@ -42,7 +48,7 @@ import numpy as np
 import torch
 
 __all__ = ['ProcessData', 'Augmentation', 'DeviceProcessData', 'DeviceAugmentation', 'FlyingThings3DSubset', 'KITTI', 'Sample',
-           'read_kitti_camera']
+           'read_kitti_camera', 'read_kitti_P', 'read_png', 'read_pfm', 'read_flo', 'KITTIRaw', 'FlyingThings3DRaw']
 
 #: (f, cx, cy, constx, consty, constz) of every FlyingThings3D frame (utils/geometry.py:59 defaults)
 FT3D_CAMERA = (-1050.0, 479.5, 269.5, 0.0, 0.0, 0.0)
@@ -63,6 +69,103 @@ def read_kitti_camera(path):
                 P = np.array([float(v) for v in line.split()[1:]], dtype=np.float32).reshape(3, 4)
                 return tuple(float(v) for v in (-P[0, 0], P[0, 2], P[1, 2], P[0, 3], P[1, 3], P[2, 3]))
     raise ValueError('%s has no P_rect_02 line' % path)
+
+
+def read_kitti_P(path):
+    """P_rect_02 of a KITTI calib_cam_to_cam file as process_kitti.py:19-26 reads it: a float32 (3, 4) matrix (the first such
+    line, as read_kitti_camera)."""
+    with open(path) as fd:
+        for line in fd:
+            if line.startswith('P_rect_02'):
+                return np.array([float(v) for v in line.split()[1:]], dtype=np.float32).reshape(3, 4)
+    raise ValueError('%s has no P_rect_02 line' % path)
+
+
+def read_png(path):
+    """A PNG's raw sample values: uint8 or uint16 array (H, W) (greyscale) or (H, W, 3) (RGB) -- KITTI's disparity maps are
+    16-bit grey, its flow maps 16-bit RGB, which Pillow cannot return.  Colour types 0 and 2 at depths 8 and 16, not
+    interlaced; anything else is refused by name.  The chunks are parsed and inflated here; the row filters are undone by the
+    library (hpl_png_unfilter, host only)."""
+    import struct
+    import zlib
+    from . import ops
+    with open(path, 'rb') as fd:
+        blob = fd.read()
+    if blob[:8] != b'\x89PNG\r\n\x1a\n':
+        raise ValueError('%s is not a PNG file' % path)
+    at, header, idat, ended = 8, None, [], False
+    while at + 12 <= len(blob) and not ended:
+        n, kind = struct.unpack('>I4s', blob[at:at + 8])
+        body = blob[at + 8:at + 8 + n]
+        if len(body) != n or at + 12 + n > len(blob):
+            raise ValueError('%s: chunk %s is cut short' % (path, kind.decode('latin-1')))
+        if zlib.crc32(kind + body) & 0xffffffff != struct.unpack('>I', blob[at + 8 + n:at + 12 + n])[0]:
+            raise ValueError('%s: chunk %s fails its CRC' % (path, kind.decode('latin-1')))
+        if kind == b'IHDR':
+            if n != 13:
+                raise ValueError('%s: IHDR of %d bytes' % (path, n))
+            header = struct.unpack('>IIBBBBB', body)
+        elif kind == b'IDAT':
+            idat.append(body)
+        elif kind == b'IEND':
+            ended = True
+        at += 12 + n
+    if header is None or not idat or not ended:
+        raise ValueError('%s: no IHDR, IDAT or IEND chunk' % path)
+    width, height, depth, colour, compression, filtering, interlace = header
+    if colour not in (0, 2) or depth not in (8, 16):
+        raise ValueError('%s: colour type %d at %d bits (read_png takes greyscale (0) and RGB (2) at 8 or 16 bits)' % (path, colour, depth))
+    if interlace != 0 or compression != 0 or filtering != 0:
+        raise ValueError('%s: interlace %d, compression %d, filter method %d (read_png takes non-interlaced PNGs of method 0)' % (
+            path, interlace, compression, filtering))
+    if width == 0 or height == 0:
+        raise ValueError('%s: %d x %d pixels' % (path, width, height))
+    channels = 3 if colour == 2 else 1
+    bpp = channels * depth // 8
+    stride = 1 + width * bpp
+    raw = zlib.decompress(b''.join(idat))
+    if len(raw) != height * stride:
+        raise ValueError('%s: %d bytes of image data, %d x %d pixels of %d bytes need %d' % (path, len(raw), width, height, bpp, height * stride))
+    rows = np.ascontiguousarray(ops.png_unfilter(raw, height, stride, bpp))
+    px = rows if depth == 8 else rows.view('>u2').astype(np.uint16)
+    return px.reshape(height, width) if channels == 1 else px.reshape(height, width, 3)
+
+
+def read_pfm(path):
+    """A PFM image as data_preprocess/IO.py:33-68 reads it: float32 (H, W) ('Pf') or (H, W, 3) ('PF'), the file's bottom-up rows
+    turned top-down, little-endian when the scale is negative and big-endian otherwise."""
+    import re
+    with open(path, 'rb') as fd:
+        kind = fd.readline().rstrip()
+        if kind not in (b'PF', b'Pf'):
+            raise ValueError('%s is not a PFM file' % path)
+        dims = re.match(r'^(\d+)\s(\d+)\s$', fd.readline().decode('ascii', 'replace'))
+        if not dims:
+            raise ValueError('%s: malformed PFM header' % path)
+        width, height = int(dims.group(1)), int(dims.group(2))
+        try:
+            scale = float(fd.readline().decode('ascii', 'replace').rstrip())
+        except ValueError:
+            raise ValueError('%s: malformed PFM header' % path)
+        shape = (height, width, 3) if kind == b'PF' else (height, width)
+        data = np.frombuffer(fd.read(), dtype='<f4' if scale < 0 else '>f4')
+    if data.size != int(np.prod(shape)):
+        raise ValueError('%s: %d values for %d x %d pixels' % (path, data.size, width, height))
+    return np.ascontiguousarray(np.flipud(data.reshape(shape)), dtype=np.float32)
+
+
+def read_flo(path):
+    """A Middlebury .flo file as data_preprocess/IO.py:100-115 reads it: float32 (H, W, 2)."""
+    with open(path, 'rb') as fd:
+        blob = fd.read()
+    if blob[:4] != b'PIEH':
+        raise ValueError('%s: flow file header does not contain PIEH' % path)
+    if len(blob) < 12:
+        raise ValueError('%s is cut short' % path)
+    width, height = (int(v) for v in np.frombuffer(blob, '<i4', 2, 4))
+    if width < 0 or height < 0 or len(blob) - 12 < 8 * width * height:
+        raise ValueError('%s: %d bytes for %d x %d pixels' % (path, len(blob) - 12, width, height))
+    return np.frombuffer(blob, '<f4', 2 * width * height, 12).reshape(height, width, 2).astype(np.float32)
 
 
 class ProcessData(object):
@@ -277,6 +380,10 @@ class _PairFolder(object):
     def load(self, path):
         raise NotImplementedError
 
+    def _load_pair(self, path):
+        """The frame's two [n, 3] float32 clouds as the processed tree stores them (the raw readers compute them instead)."""
+        return np.load(os.path.join(path, 'pc1.npy')), np.load(os.path.join(path, 'pc2.npy'))
+
     def camera_of(self, path):
         """The camera of the frame in directory `path`, None if the reader has none."""
         return None
@@ -311,17 +418,19 @@ class FlyingThings3DSubset(_PairFolder):
     def __init__(self, train, transform, data_root, full=False, device='cuda'):
         super(FlyingThings3DSubset, self).__init__(transform, device)
         self.train = train
-        self.root = os.path.join(data_root, 'FlyingThings3D_subset_processed_35m', 'train' if train else 'val')
         self.canonical = 19640 if train else 3824
-        dirs = _leaf_dirs(self.root)
+        dirs = self._sample_dirs(data_root)
         self._found = len(dirs)
         self.samples = dirs if full else dirs[::4]
         if not self.samples:
             raise RuntimeError('Found 0 files in subfolders of: ' + self.root)
 
+    def _sample_dirs(self, data_root):
+        self.root = os.path.join(data_root, 'FlyingThings3D_subset_processed_35m', 'train' if self.train else 'val')
+        return _leaf_dirs(self.root)
+
     def load(self, path):
-        pc1 = np.load(os.path.join(path, 'pc1.npy'))
-        pc2 = np.load(os.path.join(path, 'pc2.npy'))
+        pc1, pc2 = self._load_pair(path)
         for pc in (pc1, pc2):           # the subset stores x and z with the opposite sign
             pc[..., 0] *= -1
             pc[..., -1] *= -1
@@ -356,7 +465,6 @@ class KITTI(_PairFolder):
         elif voxel_mode != 'centroid':
             raise _lib.HplError('KITTI: voxel_mode applies to voxel=<edge>')
         self.voxel, self.voxel_mode = voxel, voxel_mode
-        self.root = os.path.join(data_root, 'KITTI_processed_occ_final')
         if remove_ground not in (True, False, 'plane'):
             raise _lib.HplError('KITTI: remove_ground = %r (True, False or \'plane\')' % (remove_ground,))
         self.ground = dict(ground or {})
@@ -369,7 +477,7 @@ class KITTI(_PairFolder):
         elif self.ground:
             raise _lib.HplError('KITTI: ground applies to remove_ground=\'plane\'')
         self.remove_ground = remove_ground
-        dirs = _leaf_dirs(self.root)
+        dirs = self._sample_dirs(data_root)
         self._found = len(dirs)
         if mapping_file is not None:
             with open(mapping_file) as fd:
@@ -391,9 +499,12 @@ class KITTI(_PairFolder):
     def camera_of(self, path):
         return self.cameras[os.path.basename(path)] if self.cameras is not None else None
 
+    def _sample_dirs(self, data_root):
+        self.root = os.path.join(data_root, 'KITTI_processed_occ_final')
+        return _leaf_dirs(self.root)
+
     def load(self, path):
-        pc1 = np.load(os.path.join(path, 'pc1.npy'))
-        pc2 = np.load(os.path.join(path, 'pc2.npy'))
+        pc1, pc2 = self._load_pair(path)
         if self.remove_ground == 'plane':
             from .flownet import remove_ground
             name = os.path.basename(path)
@@ -410,3 +521,110 @@ class KITTI(_PairFolder):
             v1, v2 = voxel_downsample(t1, t2, voxel=self.voxel, mode=self.voxel_mode, corr=True)[:2]
             pc1, pc2 = (np.ascontiguousarray(v[0].t().cpu().numpy()) for v in (v1, v2))
         return pc1, pc2
+
+
+def _saved(cloud):
+    """A (3, n) device cloud as the [n, 3] float32 host array the reference's scripts save."""
+    return np.ascontiguousarray(cloud.t().cpu().numpy())
+
+
+def _need_device(who, device):
+    if torch.device(device).type != 'cuda':
+        from . import _lib
+        raise _lib.HplError('%s back-projects its frames on the device, got device %s (there is no CPU fallback)' % (who, device))
+
+
+#: the directories of a raw FlyingThings3D-subset split and their files' extensions, as process_flyingthings3d_subset.py:33-38
+#: names them: disparity, its occlusions, disparity change, flow, its occlusions
+FT3D_RAW_LAYOUT = ((('disparity', 'left'), '.pfm'), (('disparity_occlusions', 'left'), '.png'),
+                   (('disparity_change', 'left', 'into_future'), '.pfm'), (('flow', 'left', 'into_future'), '.flo'),
+                   (('flow_occlusions', 'left', 'into_future'), '.png'))
+
+
+def read_ft3d_raw_frame(split_root, name):
+    """(disparity, disparity change, flow, disparity occlusions, flow occlusions) of frame `name` below a raw split directory,
+    in the order flownet.frames_from_ft3d takes them."""
+    paths = [os.path.join(split_root, *parts) + os.sep + name + ext for parts, ext in FT3D_RAW_LAYOUT]
+    disp, occ1, dchange, flow, occ2 = read_pfm(paths[0]), read_png(paths[1]), read_pfm(paths[2]), read_flo(paths[3]), read_png(paths[4])
+    for p, o in ((paths[1], occ1), (paths[4], occ2)):
+        if o.dtype != np.uint8 or o.ndim != 2:
+            raise ValueError('%s: an occlusion mask is an 8-bit greyscale PNG, got %s %s' % (p, o.dtype, o.shape))
+    return disp, dchange, flow, occ1, occ2
+
+
+def read_kitti_raw_frame(raw_root, name):
+    """(disp_occ_0, disp_occ_1, flow_occ) raw values of KITTI scene-flow frame `name` (NNNNNN) below `raw_root`/training."""
+    out = []
+    for sub, shape in (('disp_occ_0', 2), ('disp_occ_1', 2), ('flow_occ', 3)):
+        p = os.path.join(raw_root, 'training', sub, name + '_10.png')
+        x = read_png(p)
+        if x.dtype != np.uint16 or x.ndim != shape:
+            raise ValueError('%s: %s is a 16-bit %s PNG, got %s %s' % (p, sub, 'greyscale' if shape == 2 else 'RGB', x.dtype, x.shape))
+        out.append(x)
+    return tuple(out)
+
+
+def _listed(directory, ext):
+    if not os.path.isdir(directory):
+        raise FileNotFoundError('%s is not a directory' % directory)
+    return sorted(f[:-len(ext)] for f in os.listdir(directory) if f.endswith(ext))
+
+
+def _missing(paths, what):
+    gone = [p for p in paths if not os.path.isfile(p)]
+    if gone:
+        raise FileNotFoundError('%s: %d file(s) missing: %s' % (what, len(gone), ', '.join(gone[:8]) + (' ...' if len(gone) > 8 else '')))
+
+
+class FlyingThings3DRaw(FlyingThings3DSubset):
+    """FlyingThings3DSubset over the RAW subset: `raw_root`/{train,val}/ holding the five directories of FT3D_RAW_LAYOUT.  Every
+    frame is back-projected on the device when it is read (flownet.frames_from_ft3d) and yields exactly what
+    FlyingThings3DSubset yields for the tree process_flyingthings3d_subset.py would have written -- with --only_save_near_pts
+    for near=-35. (the published FlyingThings3D_subset_processed_35m), without it for near=None."""
+
+    def __init__(self, train, transform, raw_root, near=-35., full=False, device='cuda'):
+        _need_device('FlyingThings3DRaw', device)
+        self.near = near
+        super(FlyingThings3DRaw, self).__init__(train, transform, raw_root, full=full, device=device)
+
+    def _sample_dirs(self, raw_root):
+        self.root = os.path.join(raw_root, 'train' if self.train else 'val')
+        lead, ext = FT3D_RAW_LAYOUT[2]
+        names = _listed(os.path.join(self.root, *lead), ext)           # (the reference lists disparity_change, :66-67)
+        _missing([os.path.join(self.root, *parts) + os.sep + nm + e for nm in names for parts, e in FT3D_RAW_LAYOUT],
+                 'FlyingThings3DRaw: ' + self.root)
+        return [os.path.join(self.root, nm) for nm in names]       # (no directories: a sample's path only carries its name)
+
+    def _load_pair(self, path):
+        from .flownet import frames_from_ft3d
+        pc1, pc2 = frames_from_ft3d([read_ft3d_raw_frame(self.root, os.path.basename(path))], near=self.near, device=self.device)[:2]
+        return _saved(pc1[0]), _saved(pc2[0])
+
+
+class KITTIRaw(KITTI):
+    """KITTI over the RAW scene-flow download: `raw_root`/training/{disp_occ_0,disp_occ_1,flow_occ}/NNNNNN_10.png and the frames'
+    calib_cam_to_cam files in `calib_dir` (NNNNNN.txt; they also give the cameras of the 2D metrics).  Every frame is
+    back-projected on the device when it is read (flownet.frames_from_kitti) and yields exactly what KITTI yields
+    for the tree process_kitti.py would have written; the keywords are KITTI's."""
+
+    def __init__(self, transform, raw_root, calib_dir, remove_ground=True, mapping_file=None, device='cuda', ground=None,
+                 voxel=None, voxel_mode='centroid'):
+        _need_device('KITTIRaw', device)
+        if calib_dir is None or not os.path.isdir(calib_dir):
+            raise FileNotFoundError('KITTIRaw: calib_dir %r is not a directory (the back-projection needs every frame\'s P_rect_02)' % (calib_dir,))
+        super(KITTIRaw, self).__init__(transform, raw_root, remove_ground=remove_ground, mapping_file=mapping_file, device=device,
+                                       calib_dir=calib_dir, ground=ground, voxel=voxel, voxel_mode=voxel_mode)
+        self.P = {nm: read_kitti_P(os.path.join(calib_dir, nm + '.txt')) for nm in (os.path.basename(d) for d in self.samples)}
+
+    def _sample_dirs(self, raw_root):
+        self.root = os.path.join(raw_root, 'training')
+        names = [nm[:-3] for nm in _listed(os.path.join(self.root, 'disp_occ_0'), '.png') if nm.endswith('_10')]
+        _missing([os.path.join(self.root, sub, nm + '_10.png') for nm in names for sub in ('disp_occ_1', 'flow_occ')],
+                 'KITTIRaw: ' + self.root)
+        return [os.path.join(self.root, nm) for nm in names]       # (no directories: a sample's path only carries its number)
+
+    def _load_pair(self, path):
+        from .flownet import frames_from_kitti
+        name = os.path.basename(path)
+        pc1, pc2 = frames_from_kitti([read_kitti_raw_frame(os.path.dirname(self.root), name) + (self.P[name],)], device=self.device)[:2]
+        return _saved(pc1[0]), _saved(pc2[0])

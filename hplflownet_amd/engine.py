@@ -675,6 +675,10 @@ def parse_args(argv=None):
                          'batch is W x B pairs')
     ap.add_argument('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI'])
     ap.add_argument('--data-root', default=None)
+    ap.add_argument('--raw-root', default=None, metavar='DIR',
+                    help='--dataset KITTI|FlyingThings3DSubset: read the RAW download below DIR (disparity, optical-flow and '
+                         'occlusion maps) instead of a processed tree below --data-root, back-projecting every frame on the '
+                         'device as it is read (data.KITTIRaw / FlyingThings3DRaw, DESIGN.md §25); KITTI needs --kitti-calib')
     ap.add_argument('--kitti-calib', default=None, metavar='DIR',
                     help='--dataset KITTI: directory of KITTI\'s calib_cam_to_cam/<frame>.txt files; the camera (P_rect_02) of each '
                          'frame gives the 2D metrics EPE2D / Acc2D (without it KITTI evaluation reports the four 3D metrics)')
@@ -748,6 +752,13 @@ def parse_args(argv=None):
         ap.error('--ragged applies to --evaluate with --batch-size >= 2')
     if a.kitti_calib is not None and (a.dataset != 'KITTI' or not os.path.isdir(a.kitti_calib)):
         ap.error('--kitti-calib takes an existing directory and applies to --dataset KITTI')
+    if a.raw_root is not None:
+        if a.dataset == 'synthetic' or not os.path.isdir(a.raw_root):
+            ap.error('--raw-root takes an existing directory and applies to --dataset FlyingThings3DSubset|KITTI')
+        if a.data_root is not None:
+            ap.error('--raw-root and --data-root exclude each other')
+        if a.dataset == 'KITTI' and a.kitti_calib is None:
+            ap.error('--raw-root with --dataset KITTI needs --kitti-calib DIR (every frame\'s P_rect_02)')
     if a.device_transforms and a.dataset == 'synthetic':
         ap.error('--device-transforms applies to --dataset FlyingThings3DSubset|KITTI (synthetic pairs have no transform)')
     if a.dense and (not a.evaluate or a.dataset == 'synthetic'):
@@ -929,12 +940,16 @@ def _real_data(a, tr, dev, rank, world):
         process = lambda less: data_mod.ProcessData(DATA_PROCESS, a.points, less, seed=0)                       # noqa: E731
         augment = lambda: data_mod.Augmentation(AUG_TOGETHER, AUG_PC2, DATA_PROCESS, a.points, False, seed=1 + rank)  # noqa: E731
     if a.dataset == 'KITTI':                        # evaluation only in the reference
-        val = data_mod.KITTI(process(True), a.data_root, device=dev, calib_dir=a.kitti_calib,
-                             remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit, voxel=a.voxel,
-                             voxel_mode=a.voxel_mode or 'centroid')
+        kitti = data_mod.KITTIRaw if a.raw_root is not None else data_mod.KITTI
+        val = kitti(process(True), a.raw_root if a.raw_root is not None else a.data_root, device=dev, calib_dir=a.kitti_calib,
+                    remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit, voxel=a.voxel,
+                    voxel_mode=a.voxel_mode or 'centroid')
         train = None
         if a.kitti_calib is None:
             log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')
+    elif a.raw_root is not None:
+        val = data_mod.FlyingThings3DRaw(False, process(bool(a.evaluate)), a.raw_root, device=dev)
+        train = None if a.evaluate else data_mod.FlyingThings3DRaw(True, augment(), a.raw_root, device=dev)
     else:
         val = data_mod.FlyingThings3DSubset(False, process(bool(a.evaluate)), a.data_root, device=dev)
         train = None if a.evaluate else data_mod.FlyingThings3DSubset(True, augment(), a.data_root, device=dev)

@@ -850,6 +850,73 @@ def voxel_downsample(pc1, pc2=None, sf=None, voxel=0.1, mode='centroid', corr=Tr
     return res
 
 
+# ----------------------------------------------------------------------------- frames from raw maps
+def _pack_planes(who, frames, specs, device):
+    """frames: a list of tuples of per-frame arrays (numpy or tensors), plane k of shape (H, W) + specs[k][1] and a dtype in
+    specs[k][0] -> (packed device tensors, one per plane, heights, widths)."""
+    import numpy as np
+    if not isinstance(frames, (list, tuple)) or not 1 <= len(frames) <= 64 or any(
+            not isinstance(fr, (list, tuple)) or len(fr) < len(specs) for fr in frames):
+        raise _lib.HplError('%s: a list of 1 .. 64 frames, each a tuple of %d arrays' % (who, len(specs)))
+    hh, ww = [], []
+    for fr in frames:
+        shp = tuple(fr[0].shape)
+        if len(shp) != 2:
+            raise _lib.HplError('%s: a frame\'s first array is (H, W), got %s' % (who, shp))
+        hh.append(shp[0])
+        ww.append(shp[1])
+    packed = []
+    for k, (dtypes, tail) in enumerate(specs):
+        parts = []
+        for b, fr in enumerate(frames):
+            x = fr[k]
+            if not torch.is_tensor(x):
+                x = torch.from_numpy(np.ascontiguousarray(x))
+            if x.dtype not in dtypes or tuple(x.shape) != (hh[b], ww[b]) + tail:
+                raise _lib.HplError('%s: array %d of frame %d must be %s of shape %s, got %s %s' % (
+                    who, k, b, ' / '.join(str(d) for d in dtypes), (hh[b], ww[b]) + tail, x.dtype, tuple(x.shape)))
+            parts.append(x.reshape((-1,) + tail))
+        packed.append(parts)
+    return [torch.cat(parts, dim=0).to(device) for parts in packed], hh, ww
+
+
+def _frame_views(pc1, pc2, pixel, counts, hh, ww):
+    n = counts.cpu().tolist()                                                       # the one read-back
+    o1, o2, px, p0 = [], [], [], 0
+    for b in range(len(hh)):
+        o1.append(pc1[:, p0:p0 + n[b]])
+        o2.append(pc2[:, p0:p0 + n[b]])
+        px.append(pixel[p0:p0 + n[b]])
+        p0 += hh[b] * ww[b]
+    return o1, o2, px, n
+
+
+def frames_from_kitti(frames, baseline=0.54, device='cuda'):
+    """The corresponding clouds of KITTI scene-flow frames from their raw maps by ONE ops.frames_from_kitti call (DESIGN.md
+    §25).  frames: a list of 1 .. 64 tuples (disp1 (H, W) uint16, disp2 (H, W) uint16, flow (H, W, 3) uint16, P (3, 4)) -- the
+    raw values of disp_occ_0, disp_occ_1 and flow_occ as data.read_png returns them and the frame's P_rect_02 --, numpy arrays
+    or tensors; the frames may differ in size.  One read-back: the counts.
+    -> (pc1 list of (3, n_b) float32 views, pc2 list, pixel list of (n_b,) int32 -- i * W + j of every correspondence, in
+    ascending order --, counts list): pc1[b].T is the pc1.npy the reference's process_kitti.py saves for the frame, bit for bit."""
+    who = 'frames_from_kitti'
+    (d1, d2, fl), hh, ww = _pack_planes(who, frames, [(ops._U16, ()), (ops._U16, ()), (ops._U16, (3,))], device)
+    pc1, pc2, pixel, counts = ops.frames_from_kitti(d1, d2, fl, [fr[3] for fr in frames], hh, ww, baseline=baseline)
+    return _frame_views(pc1, pc2, pixel, counts, hh, ww)
+
+
+def frames_from_ft3d(frames, near=None, f=-1050.0, cx=479.5, cy=269.5, device='cuda'):
+    """The corresponding clouds of FlyingThings3D-subset frames from their raw maps by ONE ops.frames_from_ft3d call (DESIGN.md
+    §25).  frames: a list of 1 .. 64 tuples (disparity (H, W) float32, disparity change (H, W) float32, flow (H, W, 2) float32,
+    disparity occlusions (H, W) uint8, flow occlusions (H, W) uint8).  near: None or the near cut (-35.).  One read-back.
+    -> as frames_from_kitti: pc1[b].T is the pc1.npy the reference's process_flyingthings3d_subset.py saves (x and z with the
+    sign it saves; data.FlyingThings3DRaw flips them as the reference's reader does)."""
+    who = 'frames_from_ft3d'
+    f32, u8 = (torch.float32,), (torch.uint8,)
+    (d, dc, fl, o1, o2), hh, ww = _pack_planes(who, frames, [(f32, ()), (f32, ()), (f32, (2,)), (u8, ()), (u8, ())], device)
+    pc1, pc2, pixel, counts = ops.frames_from_ft3d(d, dc, fl, o1, o2, hh, ww, f=f, cx=cx, cy=cy, near=near)
+    return _frame_views(pc1, pc2, pixel, counts, hh, ww)
+
+
 # ----------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(flow, pc1, pc2, k=8, w_chamfer=1.0, w_smooth=1.0):
     """The self-supervised loss of a forward's flow in ONE ops.selfsup_loss call: Chamfer distance between

@@ -755,6 +755,136 @@ def voxel_downsample(pc, attrs=None, voxel=0.1, origin=(0, 0, 0), mode='centroid
     return out_pc, out_attrs, count, rep, voxel_of, stats
 
 
+# --------------------------------------------------------------------------- frames from raw maps
+def _frames_plane(who, name, t, dtypes, shape, dev):
+    """A packed per-pixel device tensor of the given shape and one of the dtypes, contiguous (a view that starts anywhere in a
+    wider buffer is taken as it is)."""
+    if not torch.is_tensor(t) or t.dtype not in dtypes or tuple(t.shape) != shape or not t.is_cuda or (dev is not None and t.device != dev):
+        raise _lib.HplError('%s: %s must be a %s %s device tensor%s, got %s' % (
+            who, name, shape, ' / '.join(str(d) for d in dtypes), '' if dev is None else ' on %s' % dev,
+            (tuple(t.shape), t.dtype, t.device) if torch.is_tensor(t) else type(t)))
+    if t.requires_grad:
+        raise _lib.HplError('%s has no autograd: %s requires grad' % (who, name))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _frames_sizes(who, heights, widths):
+    """(heights, widths, prefix) as host lists of a batch of 1 .. 64 frames, or an HplError."""
+    try:
+        hh, ww = [int(h) for h in heights], [int(w) for w in widths]
+    except (TypeError, ValueError):
+        hh, ww = [], [0]
+    if len(hh) != len(ww) or not 1 <= len(hh) <= 64 or any(not 0 <= v < 2 ** 31 for v in hh + ww):
+        raise _lib.HplError('%s: heights and widths hold the sizes (>= 0) of the same 1 .. 64 frames, got %r and %r' % (who, heights, widths))
+    pp = [0]
+    for h, w in zip(hh, ww):
+        pp.append(pp[-1] + h * w)
+    return hh, ww, pp
+
+
+def _frames_outputs(who, out, N, B, dev):
+    """(out_pc1, ld, out_pc2, ld, pixel, counts) of a frames call; out: None or a pair of (3, N) float32 tensors with unit stride
+    along the pixels (rows may be views of a wider buffer)."""
+    if out is None:
+        out = (torch.empty((3, N), dtype=torch.float32, device=dev), torch.empty((3, N), dtype=torch.float32, device=dev))
+    if not isinstance(out, (list, tuple)) or len(out) != 2 or any(
+            not torch.is_tensor(o) or tuple(o.shape) != (3, N) or o.dtype != torch.float32 or o.device != dev or o.requires_grad or
+            o.stride(0) < max(N, 1) or (N > 1 and o.stride(1) != 1) for o in out):
+        raise _lib.HplError('%s: out must be a pair of (3, %d) float32 tensors on %s with unit stride along the pixels' % (who, N, dev))
+    lds = [max(N, 1) if o.is_contiguous() else o.stride(0) for o in out]
+    pixel = torch.empty(N, dtype=torch.int32, device=dev)
+    counts = torch.zeros(B, dtype=torch.int32, device=dev) if N == 0 else torch.empty(B, dtype=torch.int32, device=dev)
+    return out[0], lds[0], out[1], lds[1], pixel, counts
+
+
+def _frames_workspace(who, lib, B, N, dev, st):
+    nbytes = lib.hpl_frames_workspace_bytes(B, N)
+    if nbytes < 0:
+        raise _lib.HplError('%s: %d frames of %d pixels together are outside the limits (64 frames, N < 2^31 / 3)' % (who, B, N))
+    return _workspace(who, dev, st, nbytes)
+
+
+_U16 = (torch.uint16, torch.int16)          # (the same bits: a PNG's raw values)
+
+
+def frames_from_kitti(disp1, disp2, flow, P, heights, widths, baseline=0.54, out=None):
+    """hpl_frames_from_kitti on the current stream: the corresponding clouds of a batch of KITTI scene-flow
+    frames from their raw PNG values, as the reference's process_kitti.py computes them, bit for bit.  disp1, disp2 (N,) uint16
+    (or int16 of the same bits) device tensors: the packed disp_occ_0 / disp_occ_1 values of B <= 64 frames of heights[b] x
+    widths[b] pixels, row-major, one frame behind the other; flow (N, 3) uint16: the flow_occ values (u, v, mask); P: B (3, 4)
+    or (12,) P_rect_02 matrices (host, float32 values); baseline in metres.
+    -> (pc1 (3, N) float32, pc2 (3, N), pixel (N,) int32, counts (B,) int32): frame b's valid correspondences are columns
+    prefix[b] .. prefix[b] + counts[b] (prefix = the running sum of heights * widths) in ascending pixel index, pixel their
+    i * width + j; the rest of a frame's range is 0 (pixel: -1).  out: a pair of (3, N) float32 tensors with unit stride along
+    the pixels that take pc1 and pc2; they must not overlap the inputs.  No autograd, no host synchronisation, no read-back."""
+    import numpy as np
+    who = 'frames_from_kitti'
+    hh, ww, pp = _frames_sizes(who, heights, widths)
+    B, N = len(hh), pp[-1]
+    disp1 = _frames_plane(who, 'disp1', disp1, _U16, (N,), None)
+    dev = disp1.device
+    disp2 = _frames_plane(who, 'disp2', disp2, _U16, (N,), dev)
+    flow = _frames_plane(who, 'flow', flow, _U16, (N, 3), dev)
+    try:
+        Pm = np.ascontiguousarray(np.asarray([np.asarray(p, dtype=np.float32).reshape(12) for p in P], dtype=np.float32))
+    except (TypeError, ValueError):
+        Pm = np.zeros((0, 12), np.float32)
+    if Pm.shape != (B, 12):
+        raise _lib.HplError('%s: P holds the (3, 4) P_rect_02 of each of the %d frames' % (who, B))
+    o1, ld1, o2, ld2, pixel, counts = _frames_outputs(who, out, N, B, dev)
+    lib = _lib.load()
+    st = stream()
+    ws = _frames_workspace(who, lib, B, N, dev, st)
+    check(lib.hpl_frames_from_kitti(disp1.data_ptr(), disp2.data_ptr(), flow.data_ptr(), B, (ctypes.c_int32 * B)(*hh),
+                                    (ctypes.c_int32 * B)(*ww), (ctypes.c_int64 * (B + 1))(*pp),
+                                    Pm.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), float(baseline), o1.data_ptr(), ld1,
+                                    o2.data_ptr(), ld2, pixel.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), st),
+          'hpl_frames_from_kitti')
+    return o1, o2, pixel, counts
+
+
+def frames_from_ft3d(disp, dchange, flow, occ1, occ2, heights, widths, f=-1050.0, cx=479.5, cy=269.5, near=None, out=None):
+    """hpl_frames_from_ft3d on the current stream: the corresponding clouds of a batch of FlyingThings3D-subset
+    frames as the reference's process_flyingthings3d_subset.py computes them, bit for bit (x and z keep the sign the reference
+    SAVES; its dataset reader flips them on load, and so does data.FlyingThings3DRaw).  disp, dchange (N,) float32 packed device
+    tensors: disparity and disparity change of B <= 64 frames of heights[b] x widths[b] pixels; flow (N, 2) float32; occ1, occ2
+    (N,) uint8: the disparity and flow occlusion masks (0 = visible).  near: None, or the near cut of --only_save_near_pts
+    (-35.): a correspondence is kept only when z1 > near and z2 > near.
+    -> (pc1, pc2, pixel, counts) and out as frames_from_kitti."""
+    who = 'frames_from_ft3d'
+    hh, ww, pp = _frames_sizes(who, heights, widths)
+    B, N = len(hh), pp[-1]
+    disp = _frames_plane(who, 'disp', disp, (torch.float32,), (N,), None)
+    dev = disp.device
+    dchange = _frames_plane(who, 'dchange', dchange, (torch.float32,), (N,), dev)
+    flow = _frames_plane(who, 'flow', flow, (torch.float32,), (N, 2), dev)
+    occ1 = _frames_plane(who, 'occ1', occ1, (torch.uint8,), (N,), dev)
+    occ2 = _frames_plane(who, 'occ2', occ2, (torch.uint8,), (N,), dev)
+    if near is not None and not float(near) == float(near):
+        raise _lib.HplError('%s: near = %r (None or a number)' % (who, near))
+    o1, ld1, o2, ld2, pixel, counts = _frames_outputs(who, out, N, B, dev)
+    lib = _lib.load()
+    st = stream()
+    ws = _frames_workspace(who, lib, B, N, dev, st)
+    check(lib.hpl_frames_from_ft3d(disp.data_ptr(), dchange.data_ptr(), flow.data_ptr(), occ1.data_ptr(), occ2.data_ptr(), B,
+                                   (ctypes.c_int32 * B)(*hh), (ctypes.c_int32 * B)(*ww), (ctypes.c_int64 * (B + 1))(*pp), float(f),
+                                   float(cx), float(cy), 0 if near is None else 1, 0.0 if near is None else float(near),
+                                   o1.data_ptr(), ld1, o2.data_ptr(), ld2, pixel.data_ptr(), counts.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), st), 'hpl_frames_from_ft3d')
+    return o1, o2, pixel, counts
+
+
+def png_unfilter(raw, height, stride, bpp):
+    """hpl_png_unfilter (host only): `raw`, the inflated IDAT stream of a non-interlaced PNG -- height rows of a filter byte and
+    stride - 1 data bytes --, with the row filters undone -> numpy uint8 (height, stride - 1)."""
+    import numpy as np
+    if len(raw) != height * stride:
+        raise _lib.HplError('png_unfilter: %d bytes for %d rows of %d' % (len(raw), height, stride))
+    rows = np.frombuffer(raw, dtype=np.uint8).copy().reshape(height, stride)
+    check(_lib.load().hpl_png_unfilter(rows.ctypes.data, height, stride, bpp), 'hpl_png_unfilter')
+    return rows[:, 1:]
+
+
 # --------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None, prefix2=None, need_grad=True,
                  return_neighbors=False, out=None):

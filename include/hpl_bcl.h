@@ -1135,6 +1135,69 @@ int hpl_voxel_downsample(const float *pc, int64_t pc_ld, const float *attr, int6
                          int32_t *voxel_of, int32_t *stats /* [batch][4] */, void *workspace, int64_t workspace_bytes,
                          hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Frames from raw maps (csrc/frames.hip): corresponding point clouds from disparity and optical-flow maps, the valid
+ * correspondences of every frame compacted in pixel order.
+ * ------------------------------------------------------------------------ */
+/* BOTH ENTRIES take a ragged batch of frames: batch 1 .. 64; height[b], width[b] HOST int32, each >= 0; prefix HOST, batch + 1
+ * ints from 0 to N: frame b owns pixels prefix[b] .. prefix[b + 1] of every packed per-pixel array, row-major, with
+ * prefix[b + 1] - prefix[b] == height[b] * width[b] (empty frames allowed); N < 2^31 / 3.  Pixel (i, j) of a frame -- row i,
+ * column j -- has the index i * width + j.
+ * OUTPUTS: out_pc1, out_pc2 (3, N) float32 SoA (row strides out1_ld, out2_ld >= N); pixel (N) int32 or NULL; counts [batch]
+ * int32.  Frame b's valid correspondences sit at packed positions prefix[b] .. prefix[b] + counts[b] in ascending pixel index
+ * -- the order of numpy's boolean-mask indexing, so a frame's clouds are the arrays the reference's preprocessing scripts save,
+ * transposed --, pixel holds their i * width + j; the rest of the frame's range is 0 in the clouds and -1 in pixel.
+ * Counts are integers; a frame's outputs are the same bits alone, anywhere in a batch and beside other work.  Stream-ordered,
+ * three launches whose sizes depend on batch and the prefix alone (count per workgroup, a scan of the workgroup counts inside
+ * each frame, emit), no copy back, no host synchronisation (counts[b] is known on the device only); no lane or workgroup
+ * waits for another.
+ * workspace: DEVICE, 4-byte aligned, >= hpl_frames_workspace_bytes(batch, N).
+ * HPL_EINVAL before any launch (and without a device): batch out of range; a null array (pixel alone may be NULL); a negative
+ * height or width; a prefix that does not start at 0, decreases or disagrees with height * width; N >= 2^31 / 3; a row stride
+ * below N; misaligned arrays (2 bytes for the uint16 arrays, 4 for the float32 and int32 ones); a workspace that is too small
+ * or misaligned; a row stride above 2^40; an output overlapping an input, another output or the workspace (row by row: views
+ * that interleave inside one buffer are fine); and what each entry adds below.  N == 0 is a no-op (counts is not written). */
+/* Workspace of either entry for `batch` frames of n_total pixels together, in bytes (monotone in both); -1 for a batch outside
+ * 1 .. 64 or n_total outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_frames_workspace_bytes(int batch, int64_t n_total);
+/* KITTI scene flow (kitti_utils.pixel2xyz / disp_2_depth / load_disp / load_op_flow and process_kitti.py of the reference).
+ * disp1, disp2 (N) uint16: the raw values of the disp_occ_0 / disp_occ_1 PNGs; flow [N][3] uint16: the raw values of the
+ * flow_occ PNG, interleaved (u, v, mask) as the file has them; P HOST [batch][12] float32: each frame's P_rect_02, row-major
+ * 3 x 4; baseline (0.54).  Refused as well: a P with P01, P10, P20 or P21 != 0 or P00 != P11 (the reference asserts these),
+ * a P00 that is zero or not finite, a baseline that is not finite.
+ * Per pixel (i, j) of frame b with raw values r1, r2, (u, v, m), every operation in float32, rounded once, no contraction:
+ *   valid = r1 > 0 && r2 > 0 && m == 1
+ *   fb = P00 * (float)baseline;  z_k = fb / ((float)r_k / 256 + 1e-5f)
+ *   px1 = (float)j, py1 = (float)i;  px2 = (float)j + ((float)u - 32768) / 64, py2 = (float)i + ((float)v - 32768) / 64
+ *   X = -(((px * (z + P23)) - ((P02 * z) + P03)) / P00);  Y = -(((py * (z + P23)) - ((P12 * z) + P13)) / P00);  Z = z
+ * with (px1, py1, z_1) for pc1 and (px2, py2, z_2) for pc2. */
+int hpl_frames_from_kitti(const uint16_t *disp1, const uint16_t *disp2, const uint16_t *flow /* [N][3] */, int batch,
+                          const int32_t *height /* HOST */, const int32_t *width /* HOST */, const int64_t *prefix /* HOST */,
+                          const float *P /* HOST [batch][12] */, float baseline, float *out_pc1, int64_t out1_ld, float *out_pc2,
+                          int64_t out2_ld, int32_t *pixel /* (N) or NULL */, int32_t *counts /* [batch] */, void *workspace,
+                          int64_t workspace_bytes, hplStream stream);
+/* FlyingThings3D subset (flyingthings3d_utils.pixel2pc / next_pixel2pc and process_flyingthings3d_subset.py of the reference).
+ * disp, dchange (N) float32: disparity and disparity change; flow [N][2] float32 interleaved (x, y); occ1, occ2 (N) uint8: the
+ * disparity and flow occlusion masks; f, cx, cy (-1050, 479.5, 269.5); use_near 0 or 1, near_z the near cut (-35).  Refused as
+ * well: use_near outside 0 / 1, a NaN near_z with use_near.
+ * Per pixel (i, j) with px = (float)j, py = (float)i, flow (fx, fy), every operation in float32, rounded once, no contraction:
+ *   nf = (float)(-(double)f);  d1 = disp, d2 = disp + dchange;  z_k = nf / d_k
+ *   x1 = (-(px - cx)) / d1, y1 = (py - cy) / d1;  x2 = (-((px - cx) + fx)) / d2, y2 = ((py - cy) + fy) / d2
+ *   valid = occ1 == 0 && occ2 == 0, with use_near also z1 > near_z && z2 > near_z (a NaN depth is dropped)
+ * A zero disparity gives the IEEE infinity or NaN that numpy gives, and it is kept unless the near cut drops it.  The sign
+ * flip of x and z that the dataset reader applies is the reader's (data.FlyingThings3DRaw). */
+int hpl_frames_from_ft3d(const float *disp, const float *dchange, const float *flow /* [N][2] */, const uint8_t *occ1,
+                         const uint8_t *occ2, int batch, const int32_t *height /* HOST */, const int32_t *width /* HOST */,
+                         const int64_t *prefix /* HOST */, float f, float cx, float cy, int use_near, float near_z, float *out_pc1,
+                         int64_t out1_ld, float *out_pc2, int64_t out2_ld, int32_t *pixel /* (N) or NULL */,
+                         int32_t *counts /* [batch] */, void *workspace, int64_t workspace_bytes, hplStream stream);
+/* HOST only: undoes the PNG row filters in place (data.read_png inflates with zlib and calls this).  rows: `height` rows of
+ * `stride` bytes, each a filter-type byte (0 None, 1 Sub, 2 Up, 3 Average, 4 Paeth) followed by stride - 1 data bytes; bpp: the
+ * bytes of a whole pixel, 1 .. 8 (the distance to the byte "to the left").  The filter bytes are left as they are.
+ * HPL_EINVAL: height < 0, stride < 1, bpp outside 1 .. 8, null rows with height > 0, or a filter byte above 4 (the rows before
+ * it are already unfiltered). */
+int hpl_png_unfilter(uint8_t *rows, int64_t height, int64_t stride, int bpp);
+
 #ifdef __cplusplus
 }
 #endif
