@@ -230,6 +230,9 @@ _SIGNATURES = {
     'hpl_plan_run': (ctypes.c_int, [c_vp, ctypes.POINTER(LevelTables), ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'hpl_plan_run_range': (ctypes.c_int, [c_vp, ctypes.POINTER(LevelTables), ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
                                           c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    'hpl_plan_run_range_loss': (ctypes.c_int, [c_vp, ctypes.POINTER(LevelTables), ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                               c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.POINTER(c_i64), c_vp, ctypes.c_int, c_vp]),
     'hpl_plan_run_batch': (ctypes.c_int, [c_vp, ctypes.POINTER(LevelTables), ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64,
                                           c_vp]),
     'hpl_plan_batch_extra_bytes': (c_i64, [ctypes.POINTER(LevelTables), ctypes.c_int]),
@@ -238,6 +241,7 @@ _SIGNATURES = {
                                         ctypes.POINTER(c_vp), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_vp),
                                         ctypes.POINTER(c_i64), c_vp, c_vp, c_vp, c_vp]),
     'hpl_epe3d_pairs': (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, c_i64, c_vp, c_vp]),
+    'hpl_pair_grad': (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     'hpl_flow_metrics': (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     'hpl_transform_pair': (ctypes.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp,
                                           c_vp, c_i64, c_vp]),

@@ -171,6 +171,10 @@ struct Runner {
     hplStream hs;
     const float *sf = nullptr;              // training: target flow (3, n0) and the loss scalar of HPL_OP_EPE3D
     float *loss = nullptr;
+    int loss_kind = HPL_LOSS_ROWS;          // what HPL_OP_EPE3D computes (hpl_plan_run_range_loss), and the pairs it computes it over
+    int batch = 1, loss_stride = 1;
+    const float *pair_loss = nullptr;
+    const float *dflow = nullptr;
     hipStream_t main_s = nullptr, side_s = nullptr;
     bool side_busy = false;                 // side-stream work the main stream has not waited for yet
     float *amax_base = nullptr;             // AMAX_SLOTS scalars in the workspace (cleared when a run starts at op 0)
@@ -587,8 +591,14 @@ struct Runner {
         }
         case HPL_OP_EPE3D: {
             if ((rc = view(op.out, Y, "epe3d gradient"))) return rc;
-            HPL_REQUIRE(sf && loss, "hpl_plan_run_range: the program holds a loss op but no target flow / loss pointer was given");
+            HPL_REQUIRE(loss && (sf || loss_kind == HPL_LOSS_GRAD),
+                        "hpl_plan_run_range: the program holds a loss op but no target flow / loss pointer was given");
             HPL_REQUIRE(Y.ld == 3 && Y.rows >= sym[HPL_SYM_N0], "hpl_plan_run: the loss gradient is a dense [N0][3] matrix");
+            if (loss_kind == HPL_LOSS_GRAD) {
+                // (the forward range comes before pair_loss / dflow exist: they are checked here, where they are read)
+                HPL_REQUIRE(pair_loss && dflow, "hpl_plan_run_range_loss: HPL_LOSS_GRAD needs pair_loss and dflow");
+                return hpl_pair_grad(dflow, sym[HPL_SYM_N0], batch, pair_loss, loss_stride, Y.p, loss, hs);
+            }
             return hpl_epe3d(out, sf, sym[HPL_SYM_N0], Y.p, loss, hs);
         }
         case HPL_OP_VCOPY:
@@ -765,7 +775,25 @@ extern "C" int hpl_plan_set_unlayout(hpl_plan *plan, const hpl_relayout_job *job
 extern "C" int hpl_plan_run_range(hpl_plan *plan, const hpl_level_tables *levels, int n_levels, const float *pc1, const float *pc2,
                                   const float *sf, float *out, float *loss, void *workspace, int64_t workspace_bytes, hplStream stream,
                                   hplStream side_stream, int op_begin, int op_end, int join) {
+    return hpl_plan_run_range_loss(plan, levels, n_levels, pc1, pc2, sf, out, loss, workspace, workspace_bytes, stream, side_stream,
+                                   op_begin, op_end, join, HPL_LOSS_ROWS, 1, nullptr, nullptr, 1, nullptr);
+}
+
+extern "C" int hpl_plan_run_range_loss(hpl_plan *plan, const hpl_level_tables *levels, int n_levels, const float *pc1, const float *pc2,
+                                       const float *sf, float *out, float *loss, void *workspace, int64_t workspace_bytes,
+                                       hplStream stream, hplStream side_stream, int op_begin, int op_end, int join, int loss_kind,
+                                       int batch, const int64_t *prefix, float *pair_loss, int loss_stride, const float *dflow) {
     HPL_REQUIRE(plan && pc1 && pc2 && out && workspace, "hpl_plan_run: null argument");
+    HPL_REQUIRE(loss_kind == HPL_LOSS_ROWS || loss_kind == HPL_LOSS_GRAD,
+                "hpl_plan_run_range_loss: loss kind %d", loss_kind);
+    if (loss_kind != HPL_LOSS_ROWS) {
+        HPL_REQUIRE(batch >= 1 && batch <= 64 && prefix && loss_stride >= 1,
+                    "hpl_plan_run_range_loss: loss kind %d over %d pairs (1 .. 64) needs their prefix and a loss stride >= 1 (%d)", loss_kind,
+                    batch, loss_stride);
+        HPL_REQUIRE(levels && prefix[0] == 0 && prefix[batch] == levels[0].n0,
+                    "hpl_plan_run_range_loss: the prefix runs from %lld to %lld, the lattice has %lld points", (long long)prefix[0],
+                    (long long)prefix[batch], levels ? (long long)levels[0].n0 : -1ll);
+    }
     HPL_REQUIRE(op_begin >= 0 && op_begin <= op_end && op_end <= (int)plan->ops.size(), "hpl_plan_run_range: ops [%d, %d) of %d", op_begin,
                 op_end, (int)plan->ops.size());
     int64_t sym[MAX_SYMS];
@@ -786,6 +814,8 @@ extern "C" int hpl_plan_run_range(hpl_plan *plan, const hpl_level_tables *levels
     float *splitk = reinterpret_cast<float *>(w);
     Runner r{*plan, levels, n_levels, sym, {pc1, pc2}, out, splitk, to_stream(stream), stream};
     r.sf = sf; r.loss = loss;
+    r.loss_kind = loss_kind; r.batch = batch; r.loss_stride = loss_stride;
+    r.pair_loss = pair_loss; r.dflow = dflow;
     r.main_s = to_stream(stream);
     r.side_s = side_stream ? to_stream(side_stream) : nullptr;
     r.amax_base = reinterpret_cast<float *>(w + SPLITK_WS_BYTES);

@@ -152,10 +152,12 @@ class Trainer(object):
         self._side = torch.cuda.Stream(device=self.device, priority=-1) if self.device.type == 'cuda' else None
         # the training step as one native program (train_plan.TrainPlan: forward + loss + backward enqueued by a handful of C calls,
         # gradients in one flat arena the all-reduce runs on); HPL_NATIVE_TRAIN=0 / native_step=False keep the autograd path
+        # loss='selfsup' runs on the autograd path unless native_step is an explicit True: the native program then takes the
+        # pairs' losses and gradients from hpl_selfsup_loss between its forward and its backward
+        asked = native_step is True
         if native_step is None:
             native_step = os.environ.get('HPL_NATIVE_TRAIN', '1') != '0'
-        # (the self-supervised loss runs on the autograd path: the native program's loss op takes a ground-truth flow)
-        self.native_step = bool(native_step) and self.device.type == 'cuda' and loss == 'epe3d'
+        self.native_step = bool(native_step) and self.device.type == 'cuda' and (loss == 'epe3d' or asked)
         self.tplan = None
         self.native_steps = 0
 
@@ -169,13 +171,13 @@ class Trainer(object):
         """One optimiser step on one pair (main.py:203-217) -> the loss (device tensor, not synchronised)."""
         if getattr(lat, 'batch', 1) > 1 or getattr(lat, 'ragged', False):
             raise HplError('train_step takes one pair: a lattice of %d pairs is for batched inference (validate)' % lat.batch)
-        if self.native_step and self.tplan is None:
-            from .train_plan import TrainPlan
-            if self.reducer is None:
-                self.reducer = parallel.GradAllReducer(self.model.parameters(), overlap=False)
-            self.tplan = TrainPlan(self.model, reducer=self.reducer)
+        self._native_plan()
         if self.tplan is not None:
-            r = self.tplan.step(pc1, pc2, sf, lat)
+            if self.loss == 'selfsup':               # (a batch of one pair: pair_losses[0] is its L)
+                r = self.tplan.step_batch(pc1[None], pc2[None], None, lat, 'selfsup', self.selfsup)
+                r = None if r is None else (r[0], r[2])
+            else:
+                r = self.tplan.step(pc1, pc2, sf, lat)
             if r is not None:
                 self.tplan.finish()
                 if not self.tplan.adam_step(self.opt):         # one launch over the flat arrays (hpl_adam_flat)
@@ -204,13 +206,9 @@ class Trainer(object):
         B = check_batch_step(pc1, pc2, sf, lat)
         if B == 1:
             return self.train_step(pc1[0], pc2[0], sf[0], lat).reshape(1)
-        if self.native_step and self.tplan is None:
-            from .train_plan import TrainPlan
-            if self.reducer is None:
-                self.reducer = parallel.GradAllReducer(self.model.parameters(), overlap=False)
-            self.tplan = TrainPlan(self.model, reducer=self.reducer)
+        self._native_plan()
         if self.tplan is not None:
-            r = self.tplan.step_batch(pc1, pc2, sf, lat)
+            r = self.tplan.step_batch(pc1, pc2, sf, lat, self.loss, self.selfsup)
             if r is not None:
                 self.tplan.finish()
                 if not self.tplan.adam_step(self.opt):
@@ -220,8 +218,20 @@ class Trainer(object):
             self.tplan.gflat.zero_()                 # the native program refuses the batch: autograd adds into the same arena
         else:
             self.opt.zero_grad(set_to_none=True)
-        # pair by pair on single-pair training lattices, each loss scaled by 1 / B: the same mean-over-pairs gradient, then ONE
-        # all-reduce (in the native program's bucket order) and ONE optimiser step -- ranks keep posting the same collectives
+        return self._per_pair_fallback(pc1, pc2, sf, B)
+
+    def _native_plan(self):
+        """The native training program, made at the first step that wants it."""
+        if self.native_step and self.tplan is None:
+            from .train_plan import TrainPlan
+            if self.reducer is None:
+                self.reducer = parallel.GradAllReducer(self.model.parameters(), overlap=False)
+            self.tplan = TrainPlan(self.model, reducer=self.reducer)
+
+    def _per_pair_fallback(self, pc1, pc2, sf, B):
+        """The autograd path of a batch: pair by pair on single-pair training lattices, each loss scaled by 1 / B -- the same
+        mean-over-pairs gradient --, then ONE all-reduce (in the native program's bucket order) and ONE optimiser step: ranks
+        keep posting the same collectives."""
         losses = []
         for b in range(B):
             lb = self._single_lattice(pc1[b], pc2[b])
@@ -673,6 +683,9 @@ def parse_args(argv=None):
                     help='training: pairs per native step (1 .. 64, default 1); consecutive pairs with equal point counts share '
                          'one batched lattice build and one step, whose gradient is the mean over them.  With W ranks the global '
                          'batch is W x B pairs')
+    ap.add_argument('--selfsup-native', action='store_true',
+                    help='--loss selfsup: run the step as the native training program (its loss and gradient from '
+                         'hpl_selfsup_loss between the forward and the backward) instead of the autograd path')
     ap.add_argument('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI'])
     ap.add_argument('--data-root', default=None)
     ap.add_argument('--raw-root', default=None, metavar='DIR',
@@ -715,7 +728,7 @@ def parse_args(argv=None):
     ap.add_argument('--loss', default='epe3d', choices=['epe3d', 'selfsup'],
                     help='training loss: epe3d against the ground-truth flow (default), or selfsup: Chamfer distance between the '
                          'warped cloud and pc2 plus the smoothness of the flow over the k nearest neighbours -- no flow label is '
-                         'read; it runs on the autograd path (DESIGN.md §20)')
+                         'read; it runs on the autograd path (DESIGN.md §20) unless --selfsup-native is given')
     ap.add_argument('--selfsup-k', type=int, default=None, metavar='K',
                     help='--loss selfsup: neighbours of the smoothness graph (1 .. 8, default 8)')
     ap.add_argument('--selfsup-chamfer-weight', type=float, default=None, metavar='W',
@@ -795,6 +808,8 @@ def parse_args(argv=None):
     for v, name in ((a.selfsup_chamfer_weight, '--selfsup-chamfer-weight'), (a.selfsup_smooth_weight, '--selfsup-smooth-weight')):
         if v is not None and (not on or not 0 <= v < float('inf')):
             ap.error('%s takes a finite value >= 0 and applies to --loss selfsup' % name)
+    if a.selfsup_native and not on:
+        ap.error('--selfsup-native applies to --loss selfsup')
     a.selfsup = {'k': 8 if a.selfsup_k is None else a.selfsup_k,
                  'w_chamfer': 1.0 if a.selfsup_chamfer_weight is None else a.selfsup_chamfer_weight,
                  'w_smooth': 1.0 if a.selfsup_smooth_weight is None else a.selfsup_smooth_weight} if on else None
@@ -835,7 +850,8 @@ def main(argv=None):
     rank, world, local_rank = parallel.init_distributed()
     dev = torch.device('cuda', local_rank)
     torch.cuda.set_device(dev)
-    tr = Trainer(a.arch, dev, lr=a.lr, distributed=world > 1, rank=rank, init=a.init, loss=a.loss, selfsup=a.selfsup)
+    tr = Trainer(a.arch, dev, lr=a.lr, distributed=world > 1, rank=rank, init=a.init, loss=a.loss, selfsup=a.selfsup,
+                 native_step=True if a.selfsup_native else None)
     if a.resume:
         tr.resume(a.resume, load_optimizer=not a.evaluate)
     if a.dataset != 'synthetic':

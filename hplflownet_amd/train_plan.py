@@ -311,6 +311,15 @@ def check_batch_step(pc1, pc2, sf, lat):
     return B
 
 
+LOSS_GRAD = 2          # HPL_LOSS_GRAD (include/hpl_bcl.h)
+
+
+def check_loss(loss, who):
+    if loss not in ('epe3d', 'selfsup'):
+        raise _lib.HplError('%s: loss is \'epe3d\' or \'selfsup\', got %r' % (who, loss))
+    return loss
+
+
 class TrainPlan(ForwardPlan):
     """One model's training step as a native program.  `step(pc1, pc2, sf, lattice)` enqueues forward, loss, backward and the
     un-layout of every weight gradient; the parameters' `.grad` are views of `self.gflat` (do NOT call zero_grad(set_to_none=True)
@@ -549,9 +558,12 @@ class TrainPlan(ForwardPlan):
         self._keep = (p1, p2, s, lat)
         return out.t().unsqueeze(0), self.loss
 
-    def _enqueue(self, arr, n, p1, p2, s, rows, after_forward=None):
+    def _enqueue(self, arr, n, p1, p2, s, rows, after_forward=None, pairs=None):
         """Forward, loss and backward of one (3, rows) pair of clouds -- a lone pair, or a batch staged pair-major -- on the
-        current stream -> the flow [rows][3]; after_forward(flow) is issued between the forward range and the backward."""
+        current stream -> the flow [rows][3]; after_forward(flow) is issued between the forward range and the backward.
+        pairs = [kind, prefix (c_int64 array of B + 1), pair_loss, loss_stride, dflow]: the loss op takes the mean over these pairs
+        from what after_forward left in pair_loss / dflow (hpl_plan_run_range_loss, LOSS_GRAD; s may be None); None: EPE3D, the
+        mean over the rows."""
         need = self._lib.hpl_plan_workspace_bytes(self.handle, arr, n)
         if need < 0:
             raise _lib.HplError('hpl_plan_workspace_bytes: %s' % self._lib.hpl_last_error().decode())
@@ -570,8 +582,14 @@ class TrainPlan(ForwardPlan):
         n_ops = len(self.prog.ops)
 
         def run(lo, hi, join):
-            check(self._lib.hpl_plan_run_range(self.handle, arr, n, ptr(p1), ptr(p2), ptr(s), ptr(out), ptr(self.loss), ws.data_ptr(),
-                                               ws.numel(), st, side, lo, hi, join), 'hpl_plan_run_range')
+            if pairs is None:
+                check(self._lib.hpl_plan_run_range(self.handle, arr, n, ptr(p1), ptr(p2), ptr(s), ptr(out), ptr(self.loss),
+                                                   ws.data_ptr(), ws.numel(), st, side, lo, hi, join), 'hpl_plan_run_range')
+                return
+            kind, prefix, pair_loss, stride, dflow = pairs
+            check(self._lib.hpl_plan_run_range_loss(self.handle, arr, n, ptr(p1), ptr(p2), ptr(s), ptr(out), ptr(self.loss),
+                                                    ws.data_ptr(), ws.numel(), st, side, lo, hi, join, kind, len(prefix) - 1, prefix,
+                                                    ptr(pair_loss), stride, ptr(dflow)), 'hpl_plan_run_range_loss')
         run(0, self.n_fwd, 0)
         if after_forward is not None:
             after_forward(out)
@@ -614,7 +632,7 @@ class TrainPlan(ForwardPlan):
         return best
 
     @torch.no_grad()
-    def step_batch(self, pc1, pc2, sf, lat):
+    def step_batch(self, pc1, pc2, sf, lat, loss='epe3d', selfsup=None):
         """One training step over B pairs: pc1, sf (B, 3, N1), pc2 (B, 3, N2) device tensors and a lattice of
         lattice.GenerateDataUnsymmetric.build_native_batch(..., for_training=True) with the same B -> (flow (B, 3, N1), loss
         tensor [1] = the mean of the pairs' EPE3D, pair_losses [B]), or None when the lattice needs the autograd path.
@@ -622,9 +640,14 @@ class TrainPlan(ForwardPlan):
         The batch is one pair of pair-major clouds whose tables link no two pairs: the program of step() runs
         on it unchanged.  Its HPL_OP_EPE3D takes the mean over all B x N1 rows, which for pairs of equal N1 is the mean of the
         per-pair losses, and its row gradient 1 / B of each pair's own: the gradients are the mean over the pairs, as W ranks of
-        one pair each average them.  hpl_epe3d_pairs reports the per-pair losses.  B = 1 is step()."""
-        B = check_batch_step(pc1, pc2, sf, lat)
-        if B == 1:
+        one pair each average them.  hpl_epe3d_pairs reports the per-pair losses.  B = 1 is step().
+
+        loss='selfsup' (selfsup: ops.selfsup_loss's k / w_chamfer / w_smooth; sf may be None, it is never read): the
+        same program with hpl_selfsup_loss between its forward and its backward -- the loss is the mean of the pairs'
+        self-supervised losses, pair_losses their L, the gradient the mean over the pairs.  B = 1 takes this path too."""
+        selfsup_loss = check_loss(loss, 'step_batch') == 'selfsup'
+        B = check_batch_step(pc1, pc2, pc1 if selfsup_loss and sf is None else sf, lat)
+        if B == 1 and not selfsup_loss:
             r = self.step(pc1, pc2, sf, lat)
             return None if r is None else (r[0], r[1], r[1].clone())
         tb = self.tables(lat)
@@ -638,6 +661,8 @@ class TrainPlan(ForwardPlan):
         if size > self.MAX_MATRIX_BYTES:
             raise _lib.HplError('step_batch: %d pairs of %d points make a %d x %d matrix of %.2f GiB; the kernels address matrices '
                                 'below 2 GiB (32-bit offsets): use fewer pairs per batch' % (B, n1, rows, cols, size / 2.0 ** 30))
+        if selfsup_loss:
+            return self._step_selfsup(arr, n, B, n1, n2, pc1, pc2, lat, selfsup)
         p1, p2, s = (x if x.is_contiguous() and x.dtype == torch.float32 else x.contiguous().float() for x in (pc1, pc2, sf))
         key = (B, n1, n2)
         if getattr(self, '_stage', None) is None or self._stage[0] != key:
@@ -652,6 +677,28 @@ class TrainPlan(ForwardPlan):
         out = self._enqueue(arr, n, s1, s2, ssf, B * n1, losses)
         self._keep = (p1, p2, s, s1, s2, ssf, lat)
         return out.view(B, n1, 3).transpose(1, 2), self.loss, pair_loss
+
+    def _step_selfsup(self, arr, n, B, n1, n2, pc1, pc2, lat, selfsup):
+        """step_batch under the self-supervised loss: between the forward and the backward hpl_selfsup_loss
+        reads the staged clouds and the program's flow (in place) and leaves every pair's (L, C12, C21, S) and dL / dflow; the
+        loss op (HPL_LOSS_GRAD) hands them on as the mean over the B pairs."""
+        p1, p2 = (x if x.is_contiguous() and x.dtype == torch.float32 else x.contiguous().float() for x in (pc1, pc2))
+        if B == 1:
+            s1, s2 = p1[0], p2[0]
+        else:
+            s1, s2 = (torch.empty((3, B * m), dtype=torch.float32, device=p1.device) for m in (n1, n2))
+            check(self._lib.hpl_batch_stage(B, n1, n2, ptr(p1), ptr(p2), None, ptr(s1), ptr(s2), None, stream()), 'hpl_batch_stage')
+        o = dict(selfsup or {})
+        prefix1, prefix2 = [b * n1 for b in range(B + 1)], [b * n2 for b in range(B + 1)]
+        dflow = torch.empty((B * n1, 3), dtype=torch.float32, device=p1.device)
+        pairs = [LOSS_GRAD, (ctypes.c_int64 * (B + 1))(*prefix1), None, 4, dflow]          # (pair_loss: column L of the [B][4] result)
+
+        def losses(flow):
+            pairs[2] = ops.selfsup_loss(s1, flow, s2, o.get('k', 8), o.get('w_chamfer', 1.0), o.get('w_smooth', 1.0), prefix1, prefix2,
+                                        need_grad=True, out=dflow)[0]
+        out = self._enqueue(arr, n, s1, s2, None, B * n1, losses, pairs=pairs)
+        self._keep = (p1, p2, s1, s2, lat)
+        return out.view(B, n1, 3).transpose(1, 2), self.loss, pairs[2][:, 0]
 
     def finish(self):
         """Wait for the all-reduces (several ranks) and divide: after this the .grad views hold the step's gradients."""

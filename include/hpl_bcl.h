@@ -387,6 +387,16 @@ int hpl_epe3d(const float *pred, const float *sf, int64_t N, float *grad, float 
  * pred [batch x n][3] and sf (3, batch x n) pair-major; pair_loss[b] (DEVICE, batch floats) = hpl_epe3d of pair b's rows alone,
  * bit for bit (one workgroup per pair, the same rows per thread, the same tree).  1 <= batch <= 64. */
 int hpl_epe3d_pairs(const float *pred, const float *sf, int batch, int64_t n, float *pair_loss, hplStream stream);
+/* Pair losses: the loss op of a training batch whose per-pair losses and their gradients somebody else computed
+ * (hpl_selfsup_loss).  grad[i][c] = dflow[i][c] * (1 / batch) over rows x 3 contiguous floats: the gradient of the mean over the
+ * `batch` (1 .. 64) pairs, what W ranks of one pair each average (16-byte accesses where dflow and grad reach a 16-byte boundary
+ * together, scalar before, after and otherwise).  *loss (DEVICE) = the float32 sum of pair_loss[b * loss_stride], b = 0 .. batch - 1
+ * in ascending order from 0, divided by (float)batch -- a second launch of one wave; no atomic, no workgroup waits for another
+ * (loss_stride = 4 reads column L of hpl_selfsup_loss's [batch][4] output).  grad or loss may be NULL, not both.  Stream-ordered.
+ * HPL_EINVAL before any launch (and without a device): batch outside 1 .. 64; a null dflow with grad; neither grad nor loss
+ * asked for; loss without pair_loss or with loss_stride < 1; a pointer that is not 4-byte aligned; rows < 0 or >= 2^31 / 3. */
+int hpl_pair_grad(const float *dflow, int64_t rows, int batch, const float *pair_loss, int loss_stride, float *grad, float *loss,
+                  hplStream stream);
 /* One pair of hpl_flow_metrics: n points; component k of point p of pred at pred[k * pred_sc + p * pred_sp] (elements), gt and
  * pc1 likewise -- (3, N) clouds (sc = N, sp = 1), the point-major [N][3] flow the forward writes (sc = 1, sp = 3) and column
  * slices of wider buffers are all read in place.  camera = (f, cx, cy, constx, consty, constz) of utils/geometry.py:42-65,
@@ -594,7 +604,10 @@ int hpl_lattice_next_points(const int32_t *vkeys, int64_t vstride, int64_t H, fl
 #define HPL_OP_PSUM 10        /* hpl_psum: a [F*m_sym][N] -> out [m_sym][N] */
 #define HPL_OP_REGROUP 11     /* hpl_regroup: a [m_sym][F*C] -> out [F*m_sym][C] */
 #define HPL_OP_ZERO 12        /* out = 0 */
-#define HPL_OP_EPE3D 13       /* hpl_epe3d on the run's flow / sf / loss; out = gradient [N0][3] */
+#define HPL_OP_EPE3D 13       /* the run's loss (hpl_plan_run_range_loss loss_kind; hpl_epe3d on the run's flow / sf / loss by default); out = gradient [N0][3] */
+/* loss_kind of hpl_plan_run_range_loss: what HPL_OP_EPE3D computes (1 is not assigned: it is kept for a per-pair EPE3D and refused) */
+#define HPL_LOSS_ROWS 0         /* hpl_epe3d: the mean over all N0 rows (one pair, or pairs of equal counts) */
+#define HPL_LOSS_GRAD 2         /* hpl_pair_grad: a per-pair loss and its gradient computed between the ranges (sf may be NULL) */
 #define HPL_OP_VCOPY 14       /* bias vector `bias` = bias vector `weight` (N entries): a gradient shared by two parameters */
 #define HPL_OP_UNLAYOUT 15    /* hpl_weight_unlayout_batch of bucket `aux` (hpl_plan_set_unlayout) */
 #define HPL_OP_GSUM 16        /* hpl_gather_sum: a = Z, out [m_sym][N], F = taps, table HPL_TBL_CORR2 (forward, col_step = N) or, with
@@ -740,6 +753,15 @@ int hpl_plan_run(hpl_plan *plan, const hpl_level_tables *levels /* HOST */, int 
 int hpl_plan_run_range(hpl_plan *plan, const hpl_level_tables *levels /* HOST */, int n_levels, const float *pc1,
                        const float *pc2, const float *sf, float *out, float *loss, void *workspace,
                        int64_t workspace_bytes, hplStream stream, hplStream side_stream, int op_begin, int op_end, int join);
+/* hpl_plan_run_range with the loss of HPL_OP_EPE3D chosen at run time (HPL_LOSS_*).  HPL_LOSS_GRAD: `batch`
+ * (1 .. 64) pairs whose first rows are prefix[0 .. batch] (HOST; prefix[batch] must be the run's n0); pair_loss (DEVICE) holds the
+ * per-pair losses at pair_loss[b * loss_stride] and dflow [n0][3] their gradients, both written between the forward range and
+ * the range with the loss op (they are read where that op runs); *loss becomes the mean over the pairs, the loss gradient dflow
+ * / batch; sf may be NULL.  HPL_LOSS_ROWS ignores the six and is hpl_plan_run_range. */
+int hpl_plan_run_range_loss(hpl_plan *plan, const hpl_level_tables *levels /* HOST */, int n_levels, const float *pc1,
+                            const float *pc2, const float *sf, float *out, float *loss, void *workspace, int64_t workspace_bytes,
+                            hplStream stream, hplStream side_stream, int op_begin, int op_end, int join, int loss_kind, int batch,
+                            const int64_t *prefix /* HOST */, float *pair_loss, int loss_stride, const float *dflow);
 /* The un-layout jobs of HPL_OP_UNLAYOUT: bucket i = jobs [bucket_first[i], bucket_first[i+1]) of the DEVICE tables
  * (hpl_weight_unlayout_batch); src = the gradient images (image of job j at src + prefix[j]). */
 int hpl_plan_set_unlayout(hpl_plan *plan, const hpl_relayout_job *jobs /* DEVICE */, const int64_t *prefix /* DEVICE */,

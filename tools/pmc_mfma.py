@@ -2,7 +2,7 @@
 """Executed MFMA work per kernel from a rocprofv3 --pmc run of bench.py (rocpd sqlite .db).
 
     rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
-        -d out/pmc_mfma -o m -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-overlap
+        -d out/pmc_mfma -o m -- python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-train-probe --no-overlap
     python tools/pmc_mfma.py out/pmc_mfma/m_results.db profiles/r02_mfma_pmc
 
 writes <prefix>.txt (per-kernel table) and <prefix>.json (what bench.py reads: executed GFLOP per launch of the

@@ -37,7 +37,7 @@ def main():
     hist.setdefault('round_3_split_kernel_one_barrier_form', 1110000000)
     hist.setdefault('round_5_pair_form_column_major_xcd_order', 930231343)
     d = {'_comment': 'rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (two separate passes) of `python bench.py '
-                     '--steps 3 --warmup 1 --full --no-cpu-baseline --no-overlap` (tools/pmc_traffic.py). Per launch of '
+                     '--steps 3 --warmup 1 --full --no-cpu-baseline --no-train-probe --no-overlap` (tools/pmc_traffic.py). Per launch of '
                      'the dominant stencil instance (k_gconv3w<8,4,planes>; HPL_MATH=f32: k_gconv<64,128,2,4,true,...>), averaged over its four launches per step. Counter unit KiB; FETCH_SIZE '
                      'doubled per MI355X_MICROARCH.md (gfx950 reports half the bytes of 16-B/lane reads), WRITE_SIZE as is.',
          'fetch_size_kib_per_launch_raw': fetch_kib, 'write_size_kib_per_launch': write_kib, 'launches_fetch_pass': f[fk][0],
