@@ -5,6 +5,7 @@ Public surface (mirrors the reference's operator interface for the path):
     GenerateDataUnsymmetric                                      (GPU lattice; lattice.py)
     HPLFlowNet, HPLFlowNetShallow, DeviceLattice, DenseFlow      (callers; flownet.py)
     rigid_refine                                                 (rigid motion from flow; flownet.py, ops.rigid_fit)
+    icp_register                                                 (rigid registration of a cloud pair; flownet.py, ops.icp)
     segment_motion                                               (moving objects from flow; flownet.py, ops.motion_segment)
     selfsup_loss                                                 (Chamfer + smoothness loss; flownet.py, ops.selfsup_loss)
     remove_ground                                                (fitted-plane ground removal; flownet.py, ops.ground_fit)
@@ -15,7 +16,7 @@ The arithmetic lives in libhplbcl.so (csrc/*.hip, C ABI in include/hpl_bcl.h).
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, Conv2dReLU, Conv3dReLU,  # noqa: F401
                   sparse_sum)
 from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, frames_from_ft3d, frames_from_kitti,  # noqa: F401
-                      remove_ground, rigid_refine, segment_motion, selfsup_loss, voxel_downsample)
+                      icp_register, remove_ground, rigid_refine, segment_motion, selfsup_loss, voxel_downsample)
 from .lattice import GenerateDataUnsymmetric, to_reference_format  # noqa: F401
 
 __version__ = '0.1.0'

@@ -15,6 +15,7 @@
 //
 // The arithmetic is part of the interface (include/hpl_bcl.h; tests/rigid_oracle.py restates it in numpy with an SVD).
 #include "cloud_common.h"
+#include "rigid_solve.h"        // horn_quaternion, rigid_from_sums: shared with icp.hip
 
 #include <math.h>
 
@@ -29,7 +30,6 @@ constexpr int RF_SPAN = RF_BLOCK * RF_PER_LANE;      // points per workgroup
 constexpr int RF_SUMS = 16;                          // W, Sp[3], Sq[3], Spq[9]
 constexpr int RF_STATE = 16;                         // doubles per pair: R[9], t[3], status, angle (deg), |t|, {inliers, done}
 constexpr int RF_RUNS = RF_BLOCK / RF_SUMS;          // strided runs of the solve kernel's sum
-constexpr int RF_SWEEPS = 12;
 
 struct RigidArgs {
     const float *pc;
@@ -131,33 +131,6 @@ __global__ void __launch_bounds__(RF_BLOCK) k_rigid_reduce(const RigidArgs a) {
     if (t < RF_SUMS) a.partials[(int64_t)blk * RF_SUMS + t] = red[t][0];
 }
 
-// The unit quaternion (w, x, y, z) of the proper rotation that maximises tr(R H), H = sum u (p - mp)(q - mq)^T (Horn 1987).
-__device__ void horn_quaternion(const double *H, double *quat) {
-    const double Sxx = H[0], Sxy = H[1], Sxz = H[2], Syx = H[3], Syy = H[4], Syz = H[5], Szx = H[6], Szy = H[7], Szz = H[8];
-    double A[4][4] = {{(Sxx + Syy) + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
-                      {Syz - Szy, (Sxx - Syy) - Szz, Sxy + Syx, Szx + Sxz},
-                      {Szx - Sxz, Sxy + Syx, (Syy - Sxx) - Szz, Syz + Szy},
-                      {Sxy - Syx, Szx + Sxz, Syz + Szy, (Szz - Sxx) - Syy}};
-    double V[4][4];
-    jacobi_eigen(A, V, RF_SWEEPS);
-    int best = 0;                                // the largest eigenvalue; ties go to the smaller index
-    double most = A[0][0];
-#pragma unroll
-    for (int i = 1; i < 4; ++i) {
-        best = A[i][i] > most ? i : best;
-        most = A[i][i] > most ? A[i][i] : most;
-    }
-    double n2 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        quat[k] = best == 0 ? V[k][0] : best == 1 ? V[k][1] : best == 2 ? V[k][2] : V[k][3];
-        n2 += quat[k] * quat[k];
-    }
-    const double inv = (quat[0] < 0.0 ? -1.0 : 1.0) / sqrt(n2);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) quat[k] *= inv;
-}
-
 __global__ void __launch_bounds__(RF_BLOCK) k_rigid_solve(const RigidArgs a) {
     __shared__ double run[RF_RUNS][RF_SUMS];
     __shared__ double tot[RF_SUMS];
@@ -175,33 +148,13 @@ __global__ void __launch_bounds__(RF_BLOCK) k_rigid_solve(const RigidArgs a) {
     double R[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
     double angle = 0.0, tn = 0.0;
     if (ok) {
-        double mp[3], mq[3], H[9];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) { mp[i] = tot[1 + i] / W; mq[i] = tot[4 + i] / W; }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) H[3 * i + j] = tot[7 + 3 * i + j] - W * mp[i] * mq[j];
-        double q[4];
-        horn_quaternion(H, q);
-        const double w = q[0], x = q[1], y = q[2], z = q[3];
-        R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
-        R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
-        R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
         double piv[3];
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const float v = a.pc[i * a.pc_ld + p0];
             piv[i] = isfinite(v) ? (double)v : 0.0;
         }
-        // t = mq - R mp with mp = piv + mp', mq = piv + mq'
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double rp = (R[3 * i] * (piv[0] + mp[0]) + R[3 * i + 1] * (piv[1] + mp[1])) + R[3 * i + 2] * (piv[2] + mp[2]);
-            R[9 + i] = (piv[i] + mq[i]) - rp;
-        }
-        angle = 2.0 * atan2(sqrt((x * x + y * y) + z * z), fabs(w)) * (180.0 / 3.14159265358979323846);
-        tn = sqrt((R[9] * R[9] + R[10] * R[10]) + R[11] * R[11]);
+        rigid_from_sums(tot, piv, R, angle, tn);
 #pragma unroll
         for (int i = 0; i < 12; ++i) ok = ok && isfinite(R[i]);
         if (!ok) {

@@ -306,7 +306,8 @@ class Trainer(object):
         return tot[0] / max(1.0, tot[1])             # mean loss over the global batch stream (all ranks)
 
     @torch.no_grad()
-    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None, segment=None):
+    def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None, segment=None,
+                 icp=None):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -334,7 +335,14 @@ class Trainer(object):
         segment={'eps': e, 'dv': v, 'min_points': m} (with rigid): the fit also returns its residuals and one
         ops.motion_segment call per forward groups the points above the fit's tau into moving objects.  Its integer counts stay
         on the device and come back with the read-back.  The keys gain seg_objects (objects per pair), seg_moving (the share
-        of a pair's points in objects) and seg_noise (the share labelled -2: movers in no object), means over pairs."""
+        of a pair's points in objects) and seg_noise (the share labelled -2: movers in no object), means over pairs.
+
+        icp={'iters': T, 'max_dist': d, 'tau': tau, 'init': 'identity' | 'rigid'}: behind each forward one
+        ops.icp over that forward's pairs registers pc1 onto pc2 from the clouds alone -- the ICP baseline of the scene-flow
+        papers, independent of the model's output -- or, with init='rigid' (which takes rigid), starting from that forward's
+        rigid fit: network + ICP.  The flow R p + t - p goes through one more metrics launch into an array of its own; the
+        (B, 6) statistics stay on the device and come back with the read-back.  The keys gain icp_<metric> plus icp_matched,
+        icp_rmse, icp_angle_deg, icp_trans and icp_rounds, means over pairs."""
         if dense_fill is not None and not dense:
             raise HplError('validate: dense_fill applies to dense=True')
         if rigid is not None:
@@ -345,12 +353,22 @@ class Trainer(object):
             if rigid is None:
                 raise HplError('validate: segment applies to rigid')
             segment = segment_options(segment)
+        if icp is not None:
+            if not isinstance(icp, dict) or set(icp) - {'iters', 'max_dist', 'tau', 'init'} or \
+                    icp.get('init', 'identity') not in ('identity', 'rigid'):
+                raise HplError('validate: icp takes {\'iters\': T, \'max_dist\': d, \'tau\': tau, \'init\': \'identity\' | '
+                               '\'rigid\'}, got %r' % (icp,))
+            icp_init = icp.get('init', 'identity')
+            if icp_init == 'rigid' and rigid is None:
+                raise HplError('validate: icp init \'rigid\' starts from the rigid fit: it takes rigid')
+            icp = {'iters': int(icp.get('iters', 30)), 'max_dist': float(icp.get('max_dist', 1.0)), 'tau': float(icp.get('tau', 0.3))}
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
         dkeys = ['dense_' + k for k in keys] + ['dense_coverage', 'dense_full'] if dense else []
         rkeys = ['rigid_' + k for k in keys] + list(RIGID_STATS) if rigid is not None else []
         rkeys = rkeys + list(SEGMENT_STATS) if segment is not None else rkeys
+        rkeys = rkeys + ['icp_' + k for k in keys] + list(ICP_STATS) if icp is not None else rkeys
         self.val_batches = 0
         self.val_pairs = []
         self._dense = None
@@ -370,6 +388,10 @@ class Trainer(object):
                 rstage = ops.MetricsStage(n, self.device)
                 rstats = []                              # every forward's (B, 4) fit statistics, on the device
                 sstats, scounts = [], []                 # segment: every forward's (B, 4) integer counts, on the device
+            if icp is not None:
+                isums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
+                istage = ops.MetricsStage(n, self.device)
+                istats = []                              # every forward's (B, 6) registration statistics, on the device
             nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
 
             def cameras_of(samples):
@@ -384,21 +406,31 @@ class Trainer(object):
             def add(preds, samples, batched=None):
                 ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras_of(samples), sums,
                                        nxt[0], stage)
+                fitted = None
                 if rigid is not None:
                     from .flownet import rigid_refine
                     # an equal batch goes as the forward's own (B, 3, N) tensors: its flow rows are read in place
                     pc1, flow = batched if batched is not None else ([s_[0] for s_ in samples], list(preds))
                     if segment is None:
-                        _, _, st, refined = rigid_refine(pc1, flow, **rigid)
+                        fit = rigid_refine(pc1, flow, **rigid)
+                        st, refined = fit[2], fit[3]
                     else:
                         from .flownet import segment_motion
                         fit = rigid_refine(pc1, flow, return_residual=True, **rigid)
                         st, refined = fit[2], fit[3]
                         sstats.append(segment_motion(pc1, flow, rigid=fit, tau=rigid['tau'], **segment)[3])
                         scounts.extend(int(s_[0].shape[1]) for s_ in samples)
+                    fitted = (fit[0], fit[1])
                     rstats.append(st)            # (sample order: the groups are runs of consecutive samples)
                     ops.flow_metrics_pairs(list(refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
                                            cameras_of(samples), rsums, nxt[0], rstage)
+                if icp is not None:
+                    from .flownet import icp_register
+                    res = icp_register([s_[0] for s_ in samples], [s_[1] for s_ in samples],
+                                       init=fitted if icp_init == 'rigid' else None, **icp)
+                    istats.append(res[2])
+                    ops.flow_metrics_pairs(list(res[3]), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
+                                           cameras_of(samples), isums, nxt[0], istage)
                 nxt[0] += len(samples)
 
             def add_dense(qflows, covs, samples):
@@ -418,6 +450,8 @@ class Trainer(object):
                     rwords, rst = rsums.cpu().numpy(), torch.cat(rstats).cpu().numpy()
                     if segment is not None:
                         sst = torch.cat(sstats).cpu().numpy()
+                if icp is not None:
+                    iwords, ist = isums.cpu().numpy(), torch.cat(istats).cpu().numpy()
             finally:
                 torch.cuda.current_stream(self.device).synchronize()     # the stage's copies have run before it is released
                 self._dense = self._dense_add = None
@@ -432,6 +466,10 @@ class Trainer(object):
                     v.update(zip(RIGID_STATS, (float(x) for x in rst[i, 1:])))
                     if segment is not None:
                         v.update(zip(SEGMENT_STATS, segment_fold(sst[i], scounts[i])))
+            if icp is not None:
+                for i, v in self.val_pairs:
+                    v.update({'icp_' + k: x for k, x in ops.flow_metrics_fold(iwords[i], cams).items()})
+                    v.update(zip(ICP_STATS, (float(x) for x in ist[i, 1:])))
         keys = keys + dkeys + rkeys
         agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
@@ -601,6 +639,8 @@ def segment_fold(row, points):
 
 #: validate(rigid=...): the per-pair fit statistics beside the rigid_<metric> keys (stats[1:] of ops.rigid_fit)
 RIGID_STATS = ('rigid_inliers', 'rigid_angle_deg', 'rigid_trans')
+#: validate(icp=...): the per-pair registration statistics beside the icp_<metric> keys (stats[1:] of ops.icp)
+ICP_STATS = ('icp_matched', 'icp_rmse', 'icp_angle_deg', 'icp_trans', 'icp_rounds')
 
 
 def metric_keys(data):
@@ -725,6 +765,18 @@ def parse_args(argv=None):
                     help='--segment: largest flow difference of two linked points in metres (> 0, default inf: positions alone)')
     ap.add_argument('--segment-min-points', type=int, default=None, metavar='M',
                     help='--segment: points of the smallest object (>= 1, default 5)')
+    ap.add_argument('--baseline', default=None, choices=['icp'],
+                    help='with --evaluate: behind each forward also register pc1 onto pc2 from the clouds alone by robust '
+                         'point-to-point ICP on the device and report the metrics of its flow as icp_<metric>, with icp_matched / '
+                         'icp_rmse / icp_angle_deg / icp_trans / icp_rounds (DESIGN.md §27)')
+    ap.add_argument('--icp-iters', type=int, default=None, metavar='T', help='--baseline icp: rounds at most (0 .. 64, default 30)')
+    ap.add_argument('--icp-max-dist', type=float, default=None, metavar='D',
+                    help='--baseline icp: a match is accepted within D metres (finite and > 0, default 1.0)')
+    ap.add_argument('--icp-tau', type=float, default=None, metavar='TAU',
+                    help='--baseline icp: scale of the Geman-McClure weights in metres (finite and > 0, default 0.3)')
+    ap.add_argument('--icp-init', default=None, choices=['identity', 'rigid'],
+                    help='--baseline icp: start from identity (the papers\' baseline, independent of the model; default) or from '
+                         'the fit of --rigid-refine (network + ICP)')
     ap.add_argument('--loss', default='epe3d', choices=['epe3d', 'selfsup'],
                     help='training loss: epe3d against the ground-truth flow (default), or selfsup: Chamfer distance between the '
                          'warped cloud and pc2 plus the smoothness of the flow over the k nearest neighbours -- no flow label is '
@@ -800,6 +852,23 @@ def parse_args(argv=None):
     a.segment = {'eps': 0.5 if a.segment_eps is None else a.segment_eps,
                  'dv': float('inf') if a.segment_dv is None else a.segment_dv,
                  'min_points': 5 if a.segment_min_points is None else a.segment_min_points} if a.segment else None
+    on = a.baseline == 'icp'
+    if on and not a.evaluate:
+        ap.error('--baseline applies to --evaluate')
+    if a.icp_iters is not None and (not on or not 0 <= a.icp_iters <= 64):
+        ap.error('--icp-iters takes 0 .. 64 and applies to --baseline icp')
+    if a.icp_max_dist is not None and (not on or not 0 < a.icp_max_dist < float('inf')):
+        ap.error('--icp-max-dist takes a finite value > 0 and applies to --baseline icp')
+    if a.icp_tau is not None and (not on or not 0 < a.icp_tau < float('inf')):
+        ap.error('--icp-tau takes a finite value > 0 and applies to --baseline icp')
+    if a.icp_init is not None and not on:
+        ap.error('--icp-init applies to --baseline icp')
+    if a.icp_init == 'rigid' and not a.rigid_refine:
+        ap.error('--icp-init rigid starts from the fit of --rigid-refine')
+    a.icp = {'iters': 30 if a.icp_iters is None else a.icp_iters,
+             'max_dist': 1.0 if a.icp_max_dist is None else a.icp_max_dist,
+             'tau': 0.3 if a.icp_tau is None else a.icp_tau,
+             'init': a.icp_init or 'identity'} if on else None
     on = a.loss == 'selfsup'
     if on and a.evaluate:
         ap.error('--loss applies to training (--evaluate reports the supervised metrics)')
@@ -858,7 +927,7 @@ def main(argv=None):
         return _real_data(a, tr, dev, rank, world)
     if a.evaluate:
         res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size, a.ragged,
-                          rigid=a.rigid, segment=a.segment)
+                          rigid=a.rigid, segment=a.segment, icp=a.icp)
         if rank == 0:
             print(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
@@ -985,7 +1054,7 @@ def _real_data(a, tr, dev, rank, world):
     val = _Shard(val, rank, world, cap)
     if train is None:
         res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid,
-                          segment=a.segment)
+                          segment=a.segment, icp=a.icp)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -22,7 +22,7 @@ from . import _lib, ops
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, NbrTable, _ConvReLU, _conv_of, pointwise_conv,
                   to_channel_first, to_channel_last)
 
-__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine', 'segment_motion']
+__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine', 'icp_register', 'segment_motion']
 
 
 # ----------------------------------------------------------------------------- lattice container
@@ -666,6 +666,75 @@ def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
     else:
         ref = [shape(ref[prefix[b]:prefix[b + 1]], b) for b in range(len(counts))]
     return res[:3] + (ref,) + res[4:]
+
+
+# ----------------------------------------------------------------------------- rigid registration
+def _packed_cloud(pc, counts, who, what):
+    """One cloud operand of `who` in the forms rigid_refine takes -> (pc (3, sum N_b), counts, shape): shape None for a
+    (B, 3, N) tensor, False for a packed (3, sum N_b) one (its counts are `counts`, or one pair), else the per-pair flags of
+    a list (True: the entry came as (1, 3, N_b))."""
+    if isinstance(pc, (list, tuple)):
+        if not pc or not all(torch.is_tensor(p) and p.dim() in (2, 3) for p in pc):
+            raise _lib.HplError('%s: %s is a tensor or a non-empty list of (3, N_b) tensors' % (who, what))
+        lead = [p.dim() == 3 for p in pc]
+        pcs = [p[0] if p.dim() == 3 else p for p in pc]
+        return (pcs[0] if len(pcs) == 1 else torch.cat(pcs, dim=1)), [int(p.shape[1]) for p in pcs], lead
+    if not torch.is_tensor(pc) or pc.dim() not in (2, 3):
+        raise _lib.HplError('%s: %s is a (3, N) or (B, 3, N) tensor or a list of (3, N_b) tensors' % (who, what))
+    if pc.dim() == 3:
+        B, _, n = pc.shape
+        return (pc[0] if B == 1 else pc.transpose(0, 1).reshape(3, B * n)), [int(n)] * B, None
+    total = int(pc.shape[1])
+    counts = [total] if counts is None else [int(c) for c in counts]
+    if sum(counts) != total or any(c < 0 for c in counts):
+        raise _lib.HplError('%s: the point counts %s of %s do not add up to %d points' % (who, counts, what, total))
+    return pc, counts, False
+
+
+def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
+    """The rigid registration of pc1 onto pc2 in ONE ops.icp call: per pair the motion (R, t) with
+    R pc1 + t ~ pc2, from the clouds alone.  pc1 / pc2 in the forms rigid_refine takes, each on its own: a (B, 3, N) tensor
+    (or (3, N): one pair), or a list of B (3, N_b) / (1, 3, N_b) tensors (a ragged batch; N_b of pc1 and of pc2 may differ);
+    a packed (3, sum N_b) cloud takes its pairs' counts from lat_or_counts: a ragged forward's lattice (its point_counts),
+    a sequence of counts for both clouds, or a pair (counts of pc1, counts of pc2).  B > 1 clouds are packed into one
+    (3, sum N_b) tensor first (one copy each).  init: (R (B, 3, 3), t (B, 3)) -- the first entries of a rigid_refine result --
+    or None (identity).  kw: weight (packed, pair-major), iters, max_dist, tau, tol_rot, tol_trans, return_matches of ops.icp.
+    -> (R (B, 3, 3), t (B, 3), stats (B, 6), flow[, match, dist2]), flow = R p + t - p in the form of pc1: views of one
+    [sum N_b, 3] tensor; match and dist2 stay packed."""
+    c1 = c2 = None
+    if lat_or_counts is not None:
+        if getattr(lat_or_counts, 'ragged', False):
+            c1, c2 = [int(c[0]) for c in lat_or_counts.point_counts], [int(c[1]) for c in lat_or_counts.point_counts]
+        elif hasattr(lat_or_counts, 'levels') or hasattr(lat_or_counts, 'batch'):
+            b = int(getattr(lat_or_counts, 'batch', 1) or 1)
+            c1 = c2 = b
+        elif len(lat_or_counts) == 2 and all(isinstance(c, (list, tuple)) for c in lat_or_counts):
+            c1, c2 = lat_or_counts
+        else:
+            c1 = c2 = list(lat_or_counts)
+
+    def counts_of(c, pc):                        # (an equal batch's lattice gives the number of pairs only)
+        return [int(pc.shape[1]) // c] * c if isinstance(c, int) and torch.is_tensor(pc) and pc.dim() == 2 else c
+    src, n1, shape = _packed_cloud(pc1, counts_of(c1, pc1), 'icp_register', 'pc1')
+    dst, n2, _ = _packed_cloud(pc2, counts_of(c2, pc2), 'icp_register', 'pc2')
+    if len(n1) != len(n2):
+        raise _lib.HplError('icp_register: pc1 holds %d clouds, pc2 %d' % (len(n1), len(n2)))
+    for what, c, n in (('pc1', c1, n1), ('pc2', c2, n2)):
+        if c is not None and not isinstance(c, int) and [int(x) for x in c] != n:
+            raise _lib.HplError('icp_register: the clouds of %s hold %s points, the lattice or counts say otherwise' % (what, n))
+    sp, dp = [0], [0]
+    for a, b in zip(n1, n2):
+        sp.append(sp[-1] + a)
+        dp.append(dp[-1] + b)
+    res = ops.icp(src, dst, init=init, src_prefix=sp, dst_prefix=dp, **kw)
+    fl = res[3]
+    if shape is None:
+        fl = fl.view(len(n1), n1[0], 3).transpose(1, 2)
+    elif shape is False:
+        fl = fl.t()
+    else:
+        fl = [fl[sp[b]:sp[b + 1]].t().unsqueeze(0) if shape[b] else fl[sp[b]:sp[b + 1]].t() for b in range(len(n1))]
+    return res[:3] + (fl,) + res[4:]
 
 
 # ----------------------------------------------------------------------------- moving objects

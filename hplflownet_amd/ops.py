@@ -532,6 +532,87 @@ def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_resid
     return res + (residual,) if return_residual else res
 
 
+# --------------------------------------------------------------------------- rigid registration of a cloud pair
+def _icp_scalar(name, v, zero_ok=False):
+    v = float(v)
+    if not ((v >= 0 if zero_ok else v > 0) and v < float('inf')):
+        raise _lib.HplError('icp: %s = %r (finite and %s 0)' % (name, v, '>=' if zero_ok else '>'))
+    return v
+
+
+def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_rot=0.0, tol_trans=0.0, src_prefix=None,
+        dst_prefix=None, return_matches=False, out=None):
+    """hpl_icp on the current stream: per pair the rigid motion q = R p + t that lays src (3, N) onto dst (3, M)
+    by robust point-to-point ICP -- each round matches every moved src point to its exact nearest dst point within max_dist
+    (a sorted grid over dst, built once a call), weighs the matches by Geman-McClure of scale tau and solves as ops.rigid_fit
+    does; the motion a round hands on is rounded to float32.  weight (N,) float32 or None: a weight that is not in (0, inf)
+    and a non-finite point count as 0.  init: a pair (R (B, 3, 3), t (B, 3)) of float32 device tensors -- an ops.rigid_fit
+    result passes straight in -- or None (identity).  iters 0 .. 64 rounds at most; a pair stops once a round changes no R
+    entry by more than tol_rot and no t entry by more than tol_trans (0: at a bitwise fixpoint).  src_prefix / dst_prefix (host
+    sequences of B + 1 ints from 0 to N / M): B <= 64 pairs, N_b != M_b allowed.
+    -> (R (B, 3, 3), t (B, 3), stats (B, 6) = (status, matched share, RMSE of the matches, rotation angle in degrees, |t|,
+    rounds run), flow [N, 3] = R p + t - p [, match (N,) int32 into the packed dst or -1, dist2 (N,) float32 or +inf]).
+    status 0 (fewer than 3 src points, no dst point, or a round without any match): the motion is the one the failed round
+    started from.  out: a contiguous [N, 3] float32 tensor that takes the flow.  No autograd, no host synchronisation."""
+    _int_in('icp', 'iters', iters, 0, 64)
+    max_dist, tau = _icp_scalar('max_dist', max_dist), _icp_scalar('tau', tau)
+    tol_rot, tol_trans = _icp_scalar('tol_rot', tol_rot, True), _icp_scalar('tol_trans', tol_trans, True)
+    src, src_ld = _soa3(src, 'src', 'icp')
+    dst, dst_ld = _soa3(dst, 'dst', 'icp')
+    N, M, dev = src.shape[1], dst.shape[1], src.device
+    if dst.device != dev:
+        raise _lib.HplError('icp: src is on %s, dst on %s' % (dev, dst.device))
+    if weight is not None:
+        if not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32 or weight.device != dev \
+                or weight.requires_grad:
+            raise _lib.HplError('icp: weight must be a (%d,) float32 tensor on %s without grad' % (N, dev))
+        weight = weight.contiguous()
+    sp = _prefix(src_prefix, N, 'icp', 'the prefix of src')
+    dp = _prefix(dst_prefix, M, 'icp', 'the prefix of dst')
+    if len(sp) != len(dp):
+        raise _lib.HplError('icp: the prefixes hold B + 1 entries each, got %d and %d' % (len(sp), len(dp)))
+    B = len(sp) - 1
+    if init is not None:
+        if not isinstance(init, (list, tuple)) or len(init) != 2:
+            raise _lib.HplError('icp: init is a pair (R (%d, 3, 3), t (%d, 3)) of float32 tensors on %s' % (B, B, dev))
+        for t_, shape in zip(init, ((B, 3, 3), (B, 3))):
+            if not torch.is_tensor(t_) or tuple(t_.shape) != shape or t_.dtype != torch.float32 or t_.device != dev or \
+                    t_.requires_grad:
+                raise _lib.HplError('icp: init is a pair (R (%d, 3, 3), t (%d, 3)) of float32 tensors on %s without grad' % (B, B, dev))
+        init = torch.cat([init[0].reshape(B, 9), init[1]], dim=1).contiguous()
+    if out is not None:
+        if not torch.is_tensor(out) or tuple(out.shape) != (N, 3) or out.dtype != torch.float32 or out.device != dev or \
+                not out.is_contiguous() or out.requires_grad:
+            raise _lib.HplError('icp: out must be a contiguous (%d, 3) float32 tensor on %s' % (N, dev))
+    else:
+        out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    match = torch.empty(N, dtype=torch.int32, device=dev) if return_matches else None
+    dist2 = torch.empty(N, dtype=torch.float32, device=dev) if return_matches else None
+    lib = _lib.load()
+    if N == 0:                                   # nothing to launch: every src cloud is empty
+        if init is None:
+            Rt = torch.zeros((B, 12), dtype=torch.float32, device=dev)
+            Rt[:, 0:9:4] = 1.0
+        else:
+            Rt = init
+        stats = torch.zeros((B, 6), dtype=torch.float32, device=dev)
+    else:
+        Rt = torch.empty((B, 12), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, 6), dtype=torch.float32, device=dev)
+        nbytes = lib.hpl_icp_workspace_bytes(B, N, M)
+        if nbytes < 0:
+            raise _lib.HplError('icp: %d pairs of %d and %d points together are outside the limits (64 pairs, N, M < 2^31 / 3)'
+                                % (B, N, M))
+        st = stream()
+        ws = _workspace('icp', dev, st, nbytes)
+        check(lib.hpl_icp(src.data_ptr(), src_ld, dst.data_ptr(), dst_ld, ptr(weight), ptr(init), B,
+                          (ctypes.c_int64 * (B + 1))(*sp), (ctypes.c_int64 * (B + 1))(*dp), iters, max_dist, tau, tol_rot,
+                          tol_trans, Rt.data_ptr(), stats.data_ptr(), ptr(match), ptr(dist2), out.data_ptr(), ws.data_ptr(),
+                          ws.numel(), st), 'hpl_icp')
+    res = (Rt[:, :9].view(B, 3, 3), Rt[:, 9:], stats, out)
+    return res + (match, dist2) if return_matches else res
+
+
 # --------------------------------------------------------------------------- moving objects from flow
 def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_points=5, max_objects=256, prefix=None, out=None):
     """hpl_motion_segment on the current stream: the points whose residual against a rigid fit exceeds tau

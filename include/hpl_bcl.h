@@ -1220,6 +1220,58 @@ int hpl_frames_from_ft3d(const float *disp, const float *dchange, const float *f
  * it are already unfiltered). */
 int hpl_png_unfilter(uint8_t *rows, int64_t height, int64_t stride, int bpp);
 
+/* ------------------------------------------------------------------------ *
+ * Rigid registration of a cloud pair (csrc/icp.hip): the motion (R, t) that lays src onto dst, from the clouds alone, by
+ * robust point-to-point ICP with an exact nearest-neighbour search within a radius on a sorted grid.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_icp for `batch` pairs of n_src / n_dst points together, in bytes (monotone in all three); -1 for a batch
+ * outside 1 .. 64 or a count outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_icp_workspace_bytes(int batch, int64_t n_src, int64_t n_dst);
+/* src (3, N) and dst (3, M) float32 SoA (row strides src_ld >= N, dst_ld >= M).  batch (1 .. 64) pairs: src_prefix /
+ * dst_prefix (HOST, batch + 1 ints each from 0 to N / M, non-decreasing, empty pairs allowed, N_b != M_b allowed) travel in
+ * the kernel arguments.  weight (N) float32 or NULL (all 1): the effective base weight w_i is the given weight, 0 when that is
+ * not in (0, inf) (NaN included) or a coordinate of the src point is not finite.  init [batch][12] float32 (DEVICE) or NULL
+ * (identity): R row-major, then t.  iters 0 .. 64; max_dist, tau finite and > 0; tol_rot, tol_trans >= 0.
+ * GRID (an accelerator only: the match below is defined over all pairs; tests/icp_oracle.py restates it in numpy without a
+ * grid): cell_k = floor(x_k * (1 / (1.001 * max_dist))) in float64 (the product 1.001 * max_dist, the quotient and the product
+ * with x_k each rounded once).  A dst point takes part when its three coordinates are finite and |cell_k| <= 2^18 - 2 for
+ * k = x, y, z; a query whose cell fails the same test has no match.
+ * MATCH of src point p under a float32 motion (R, t), every entry widened to float64: y_k = ((R[k][0] px + R[k][1] py) +
+ * R[k][2] pz) + t_k in float64, the query yq = float32(y); d2 = (dx * dx + dy * dy) + dz * dz in float32 with dx = yq.x - q.x,
+ * every operation rounded, no contraction (the arithmetic of hpl_knn_interp).  The match is the dst point of the same pair
+ * that takes part with the smallest d2, ties to the smaller dst index; it is accepted when d2 <= float32(max_dist * max_dist)
+ * (the product in float32); otherwise the point has no match (match -1, dist2 +inf).
+ * ROUND from the motion (R, t): r2_i = sum_k (y_k - q_k)^2 in float64 (k ascending, from 0) against the matched q;
+ * u_i = w_i / (s * s), s = 1 + r2_i * (1 / (tau * tau)) (Geman-McClure; tau widened first); u_i = 0 without a match.  The 16
+ * sums W = sum u, sum u dp, sum u dq, sum u dp dq^T about the pair's first src point (0 for a non-finite coordinate of it) are
+ * hpl_rigid_fit's, in its order (workgroups of 1024 consecutive points, lane l taking points l, l + 256, l + 512, l + 768, one
+ * LDS tree, then the fold of the workgroups' partials), and so is the solve (Horn's quaternion, csrc/rigid_solve.h).  The
+ * motion a round hands on is that solve's (R, t) ROUNDED TO FLOAT32 -- exactly what Rt holds: a call with iters = T equals T
+ * chained calls with iters = 1, each given the previous Rt as init, bit for bit (but for stats[5]) at tol = 0.
+ * STOP: a pair is finished when |new - old| <= tol_rot for every R entry and <= tol_trans for every t entry of the float32
+ * motions (the differences in float64); its later rounds are skipped.  At tol = 0 that skips bitwise fixpoints only.
+ * FAILURE: a pair with N_b < 3 or M_b = 0 has status 0 and runs no round.  A round fails when W is not > 0 or a sum or the
+ * new float32 motion is not finite: the pair ends with status 0 and keeps the motion that round started from (init at the
+ * first).  The failed round counts in stats[5].
+ * FINISH: one more match under the final motion writes match (N) int32 (the packed dst index, -1 for none), dist2 (N) float32
+ * (the match's d2, +inf for none) and flow [N][3] float32 = float32(y_k - p_k), the difference in float64 (each may be NULL).
+ * Rt [batch][12] float32: the final motion.  stats [batch][6] float32: status; matched share = accepted matches of points
+ * with w_i > 0 / N_b (0 for N_b = 0); RMSE = sqrt(sum r2 / count) over those points, a float64 sum in a fixed order (per
+ * workgroup as above, then one fold per pair), rounded once, 0 for none; the angle of the final float32 R in degrees,
+ * atan2(|v|, tr R - 1) with v = (R21 - R12, R02 - R20, R10 - R01), in float64; |t| = sqrt((t0^2 + t1^2) + t2^2) in float64;
+ * rounds run.  No floating-point atomic; a pair's outputs are the same bits alone, anywhere in a batch and beside other work.
+ * Stream-ordered: keys, one stable radix sort of dst, 2 iters launches, finish, fold; no copy back, no host synchronisation;
+ * no lane or workgroup waits for another.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_icp_workspace_bytes(batch, N, M); the outputs must not overlap the inputs.
+ * HPL_EINVAL before any launch (and without a device): batch or iters out of range; max_dist or tau <= 0 or not finite; a
+ * negative or NaN tolerance; a prefix that does not start at 0 or decreases; a row stride below its count; null src / Rt /
+ * stats / prefixes / workspace, null dst with M > 0; misaligned arrays; a workspace that is too small or misaligned; N or M >= 2^31 / 3.
+ * N == 0 is a no-op (the caller pre-fills Rt and stats). */
+int hpl_icp(const float *src, int64_t src_ld, const float *dst, int64_t dst_ld, const float *weight, const float *init,
+            int batch, const int64_t *src_prefix /* HOST */, const int64_t *dst_prefix /* HOST */, int iters, float max_dist,
+            float tau, float tol_rot, float tol_trans, float *Rt, float *stats, int32_t *match, float *dist2, float *flow,
+            void *workspace, int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
