@@ -48,6 +48,21 @@ class GConvDesc(ctypes.Structure):
                 ('a_guard', c_vp), ('y_guard', c_vp), ('guard_trips', c_vp)]
 
 
+class GConvInfo(ctypes.Structure):
+    """Mirror of `hpl_gconv_info`: the kernel instance a gather-GEMM launch takes (hpl_gconv_launch_info)."""
+    _fields_ = [('family', c_i32), ('bm', c_i32), ('bn', c_i32), ('threads', c_i32), ('avec', c_i32), ('f_lds', c_i32),
+                ('compact', c_i32), ('splits', c_i32), ('guard_sets', c_i32), ('col_share', c_i32), ('col_rows', c_i32),
+                ('tile_tables', c_i32), ('epi_fast', c_i32), ('finish', c_i32), ('tiles_m', c_i32), ('tiles_n', c_i32),
+                ('grid', c_i64)]
+
+
+class WGradInfo(ctypes.Structure):
+    """Mirror of `hpl_wgrad_info`: the kernel instance a weight-gradient launch takes (hpl_wgrad_launch_info)."""
+    _fields_ = [('family', c_i32), ('bn', c_i32), ('vec', c_i32), ('tap', c_i32), ('threads', c_i32), ('deep', c_i32),
+                ('tiles_k', c_i32), ('tiles_n', c_i32), ('bias', c_i32), ('pad_', c_i32), ('tiles', c_i64), ('splits', c_i64),
+                ('m_per_split', c_i64)]
+
+
 class QueryInfo(ctypes.Structure):
     """Mirror of `hpl_query_info`."""
     _fields_ = [('slots', c_vp), ('keys', c_vp), ('ids', c_vp), ('mask', ctypes.c_uint64), ('mm', c_vp), ('pmm', c_vp),
@@ -162,6 +177,10 @@ _SIGNATURES = {
     'hpl_gconv_forward_naive': (ctypes.c_int, [ctypes.POINTER(GConvDesc), c_vp]),
     'hpl_gconv_wgrad': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
                                        c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    'hpl_gconv_launch_info': (ctypes.c_int, [ctypes.POINTER(GConvDesc), ctypes.POINTER(GConvInfo)]),
+    'hpl_wgrad_launch_info': (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, ctypes.c_int, ctypes.c_int,
+                                             c_vp, c_i64, ctypes.c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp,
+                                             ctypes.POINTER(WGradInfo)]),
     'hpl_tap_lists': (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     'hpl_colsum': (ctypes.c_int, [c_vp, c_i64, c_i64, ctypes.c_int, c_vp, c_vp]),
     'hpl_leaky_bwd': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_f32, c_vp, c_i64, c_i64, ctypes.c_int, c_vp]),

@@ -19,6 +19,7 @@
 #include "gconv_common.h"
 #include <cstdlib>
 #include <cmath>
+#include <cstring>
 #include <string>
 
 #include <stdlib.h>
@@ -637,8 +638,12 @@ int hpl_gc::fill_params(const hpl_gconv_desc *d, GParams &p, const char *who) {
 }
 
 namespace {
-template <int BM, int BN, int WGM, int WGN>
-void launch_cfg(GParams &p, bool avec, hipStream_t s) {
+// The instance of one tile configuration (BM x BN output tile, WGM x WGN waves) for the launch p: split-K, the epilogue's
+// addressing, the XCD order, the LDS form.  Pure host code: it finishes p's launch fields and describes the instance in o.
+void plan_cfg(GParams &p, hpl_gconv_info &o, int BM, int BN, int WGM, int WGN) {
+    const bool avec = o.avec != 0;
+    o.family = HPL_FAMILY_FP32;
+    o.bm = BM; o.bn = BN; o.threads = 64 * WGM * WGN;
     p.tiles_m = (int)cdiv(p.M, BM);
     p.tiles_n = (int)cdiv(p.N, BN);
     if (p.tile_bm != BM || p.F == 1) p.tile_idx = nullptr;      // the table was cut for another tile height
@@ -658,7 +663,7 @@ void launch_cfg(GParams &p, bool avec, hipStream_t s) {
         // on dense data = 2.1 per CU: the CUs holding three set the time, 71 %).  Splitting K multiplies the work items;
         // pick the split count with the best (load balance) x (1 - cost of writing and re-reading the partial tiles).
         constexpr int mid = 1;
-        constexpr int WG_PER_CU = 16 / (WGM * WGN);                    // four waves per SIMD fill a CU
+        const int WG_PER_CU = 16 / (WGM * WGN);                        // four waves per SIMD fill a CU
         const double slots = 256.0 * WG_PER_CU;
         if (mid && tiles < 6 * slots) {
             double best = 0.0;
@@ -695,34 +700,57 @@ void launch_cfg(GParams &p, bool avec, hipStream_t s) {
         p.col_rows = p.col_share == 1 ? p.tiles_m : (int)cdiv(p.tiles_m, COL_CHUNK * p.col_share) * COL_CHUNK;
         grid = p.tiles_n * p.col_share * p.col_rows;
     }
-    if constexpr (BM == 64 && BN == 128 && WGM == 2 && WGN == 4) {
+    // F_LDS = taps whose indices are staged in LDS: 1 for dense GEMMs, 15 for the radius-1 stencil
+    o.f_lds = p.F == 1 ? 1 : 15;
+    o.compact = 0;
+    if (BM == 64 && BN == 128 && WGM == 2 && WGN == 4) {
         // three workgroups per CU (COMPACT LDS budget, 52.8 KB) for the tap-group passes of the big stencil launches: a
         // third workgroup covers the dispatch gaps and prologues of the other two -- slots occupied 0.91 -> 0.93 of 768,
         // dominant launch 816 -> 789 us alone (profiles/r02y_wg3.txt); in the three-stream pipeline the throughput is
         // unchanged (the GPU is matrix-pipe bound there).
         if (avec && p.F > 1 && p.F <= 8 && nk <= 512 && p.splits == 1) {      // (a tap group: <= 8 taps staged)
+            o.f_lds = 8;
+            o.compact = 1;
+        }
+    }
+    o.splits = p.splits;
+    o.guard_sets = 1;
+    o.col_share = p.col_share; o.col_rows = p.col_rows;
+    o.tile_tables = p.tile_idx ? 1 : 0;
+    o.epi_fast = p.epi_fast;
+    o.tiles_m = p.tiles_m; o.tiles_n = p.tiles_n;
+    o.grid = grid;
+}
+
+template <int BM, int BN, int WGM, int WGN>
+void launch_cfg(const GParams &p, const hpl_gconv_info &o, hipStream_t s) {
+    const int grid = (int)o.grid;
+    if constexpr (BM == 64 && BN == 128 && WGM == 2 && WGN == 4) {
+        if (o.compact) {
             k_gconv<BM, BN, WGM, WGN, true, 8, true><<<grid, 64 * WGM * WGN, 0, s>>>(p);
             return;
         }
     }
-    // F_LDS = taps whose indices are staged in LDS: 1 for dense GEMMs, 15 for the radius-1 stencil
-    if (p.F == 1) {
-        if (avec) k_gconv<BM, BN, WGM, WGN, true, 1><<<grid, 64 * WGM * WGN, 0, s>>>(p);
+    if (o.f_lds == 1) {
+        if (o.avec) k_gconv<BM, BN, WGM, WGN, true, 1><<<grid, 64 * WGM * WGN, 0, s>>>(p);
         else k_gconv<BM, BN, WGM, WGN, false, 1><<<grid, 64 * WGM * WGN, 0, s>>>(p);
     } else {
-        if (avec) k_gconv<BM, BN, WGM, WGN, true, 15><<<grid, 64 * WGM * WGN, 0, s>>>(p);
+        if (o.avec) k_gconv<BM, BN, WGM, WGN, true, 15><<<grid, 64 * WGM * WGN, 0, s>>>(p);
         else k_gconv<BM, BN, WGM, WGN, false, 15><<<grid, 64 * WGM * WGN, 0, s>>>(p);
     }
 }
 
-}  // namespace
-
-namespace {
-void launch_finish(const GParams &p, hipStream_t s) {
+// which finish kernel sums the partial tiles of a split-K launch
+int plan_finish(const GParams &p) {
+    if (p.splits <= 1) return HPL_FINISH_NONE;
     const bool vec = p.N % 4 == 0 && p.ldy % 4 == 0 && aligned16(p.Y) && aligned16(p.partial) && (!p.bias || aligned16(p.bias)) &&
                      (!p.res || (p.ldres % 4 == 0 && aligned16(p.res))) && (!p.Y2 || (p.ldy2 % 4 == 0 && aligned16(p.Y2))) &&
                      p.M * p.N < (int64_t)0x7fffffff && p.res_mod < (int64_t)0x7fffffff;
-    if (vec) {
+    return vec ? HPL_FINISH_VEC4 : HPL_FINISH_SCALAR;
+}
+
+void launch_finish(const GParams &p, const hpl_gconv_info &o, hipStream_t s) {
+    if (o.finish == HPL_FINISH_VEC4) {
         const int g = (int)imin(cdiv(p.M * (p.N / 4), 256), 2048);
         k_gconv_finish4<<<g, 256, 0, s>>>(p);
     } else {
@@ -730,20 +758,14 @@ void launch_finish(const GParams &p, hipStream_t s) {
         k_gconv_finish<<<g, 256, 0, s>>>(p);
     }
 }
-}  // namespace
 
-extern "C" int hpl_gconv_forward(const hpl_gconv_desc *d, hplStream stream) {
-    GParams p;
-    int rc = fill_params(d, p, "hpl_gconv_forward");
-    if (rc != HPL_OK) return rc;
-    if (p.M == 0) return HPL_OK;
-    hipStream_t s = to_stream(stream);
-    const bool avec = (p.C % 4 == 0) && (p.lda % 4 == 0) && aligned16(p.A);
-    if (avec && p.Wt3 && launch_split3(p, s)) {
-        if (p.splits > 1) launch_finish(p, s);       // (mid-size stencils: partial tiles over slice ranges, summed in fixed order)
-        HPL_CHECK_LAUNCH("hpl_gconv_forward");
-        if (p.y_amax && !p.y_amax_done) return amax_launch(p.Y, p.ldy, p.M, p.N, p.y_amax, s, p.y_guard);
-        return HPL_OK;
+// The whole selection of hpl_gconv_forward for a validated launch (M > 0).
+void plan_forward(GParams &p, hpl_gconv_info &o) {
+    memset(&o, 0, sizeof(o));
+    o.avec = ((p.C % 4 == 0) && (p.lda % 4 == 0) && aligned16(p.A)) ? 1 : 0;
+    if (o.avec && p.Wt3 && plan_split3(p, o)) {
+        o.finish = plan_finish(p);       // (mid-size stencils: partial tiles over slice ranges, summed in fixed order)
+        return;
     }
     // Tile selection.
     const int64_t t128 = cdiv(p.M, 128), t64 = cdiv(p.M, 64);
@@ -754,15 +776,49 @@ extern "C" int hpl_gconv_forward(const hpl_gconv_desc *d, hplStream stream) {
         // tiles, else 64x64 with 4 waves (4 workgroups per CU); 64-row tiles also skip more absent
         // taps than 128-row tiles (58.6 % vs 62.5 % of the slices executed on bcn1_).
         const int64_t tn = cdiv(p.N, 128);
-        if (t64 * tn >= 512) launch_cfg<64, 128, 2, 4>(p, avec, s);
-        else launch_cfg<64, 64, 2, 2>(p, avec, s);
+        if (t64 * tn >= 512) plan_cfg(p, o, 64, 128, 2, 4);
+        else plan_cfg(p, o, 64, 64, 2, 2);
     } else if (nsel > 32) {
-        launch_cfg<64, 64, 2, 2>(p, avec, s);       // 4 workgroups per CU; 128x64 measured 50 % slower at M = 70 k
+        plan_cfg(p, o, 64, 64, 2, 2);       // 4 workgroups per CU; 128x64 measured 50 % slower at M = 70 k
     } else {
-        if (t128 >= 512) launch_cfg<128, 32, 4, 1>(p, avec, s);
-        else launch_cfg<64, 32, 2, 1>(p, avec, s);
+        if (t128 >= 512) plan_cfg(p, o, 128, 32, 4, 1);
+        else plan_cfg(p, o, 64, 32, 2, 1);
     }
-    if (p.splits > 1) launch_finish(p, s);
+    o.finish = plan_finish(p);
+}
+}  // namespace
+
+extern "C" int hpl_gconv_launch_info(const hpl_gconv_desc *d, hpl_gconv_info *info) {
+    HPL_REQUIRE(info, "hpl_gconv_launch_info: null info");
+    memset(info, 0, sizeof(*info));
+    GParams p;
+    int rc = fill_params(d, p, "hpl_gconv_forward");
+    if (rc != HPL_OK) return rc;
+    if (p.M == 0) return HPL_OK;
+    plan_forward(p, *info);
+    return HPL_OK;
+}
+
+extern "C" int hpl_gconv_forward(const hpl_gconv_desc *d, hplStream stream) {
+    GParams p;
+    int rc = fill_params(d, p, "hpl_gconv_forward");
+    if (rc != HPL_OK) return rc;
+    if (p.M == 0) return HPL_OK;
+    hipStream_t s = to_stream(stream);
+    hpl_gconv_info o;
+    plan_forward(p, o);
+    if (o.family != HPL_FAMILY_FP32) {
+        launch_split3(p, o, s);
+        if (o.finish != HPL_FINISH_NONE) launch_finish(p, o, s);
+        HPL_CHECK_LAUNCH("hpl_gconv_forward");
+        if (p.y_amax && !p.y_amax_done) return amax_launch(p.Y, p.ldy, p.M, p.N, p.y_amax, s, p.y_guard);
+        return HPL_OK;
+    }
+    if (o.bm == 128) launch_cfg<128, 32, 4, 1>(p, o, s);
+    else if (o.bn == 128) launch_cfg<64, 128, 2, 4>(p, o, s);
+    else if (o.bn == 64) launch_cfg<64, 64, 2, 2>(p, o, s);
+    else launch_cfg<64, 32, 2, 1>(p, o, s);
+    if (o.finish != HPL_FINISH_NONE) launch_finish(p, o, s);
     HPL_CHECK_LAUNCH("hpl_gconv_forward");
     if (p.y_amax) return amax_launch(p.Y, p.ldy, p.M, p.N, p.y_amax, s, p.y_guard);
     return HPL_OK;
@@ -1489,19 +1545,22 @@ extern "C" int hpl_gconv_wgrad(const float *A, int64_t lda, int64_t rows_a, cons
                                   tap_ptr, tap_max, dbias, nullptr, nullptr, stream);
 }
 
-extern "C" int hpl_gconv_wgrad_scaled(const float *A, int64_t lda, int64_t rows_a, const int32_t *nbr,
-                                      int64_t nbr_stride, int64_t reg_stride, int64_t M, int C, int F,
-                                      const float *dY, int64_t lddy, int N, float *dWt, int64_t ldw,
-                                      const int32_t *tap_m, const int32_t *tap_row, const int32_t *tap_ptr,
-                                      int64_t tap_max, float *dbias, const float *a_amax, const float *dy_amax,
-                                      hplStream stream) {
+namespace {
+// The selection of hpl_gconv_wgrad_scaled as a pure host function: validates, fills the launch parameters and describes the
+// instance (no HIP call; pointers count as null / aligned or not).  *launch = 0: nothing to run (M == 0).
+int plan_wgrad(const float *A, int64_t lda, int64_t rows_a, const int32_t *nbr, int64_t nbr_stride, int64_t reg_stride, int64_t M,
+               int C, int F, const float *dY, int64_t lddy, int N, float *dWt, int64_t ldw, const int32_t *tap_m,
+               const int32_t *tap_row, const int32_t *tap_ptr, int64_t tap_max, float *dbias, const float *a_amax,
+               const float *dy_amax, WParams &p, hpl_wgrad_info &o, int *launch) {
+    memset(&o, 0, sizeof(o));
+    *launch = 0;
     HPL_REQUIRE(A && dY && dWt, "hpl_gconv_wgrad: null pointer");
     HPL_REQUIRE(M >= 0 && C > 0 && F > 0 && N > 0 && lda >= C && lddy >= N && ldw >= N,
                 "hpl_gconv_wgrad: bad sizes");
     HPL_REQUIRE(nbr || F == 1 || reg_stride > 0, "hpl_gconv_wgrad: F > 1 needs a table or reg_stride");
     HPL_REQUIRE(nbr || (int64_t)F * reg_stride + M < (int64_t)INT32_MAX, "hpl_gconv_wgrad: regular table too large");
     if (M == 0) return HPL_OK;
-    WParams p;
+    *launch = 1;
     p.A = A; p.lda = lda; p.nbr = nbr; p.nbr_stride = nbr_stride; p.reg_stride = reg_stride;
     p.M = M; p.C = C; p.F = F; p.K = F * C; p.dY = dY; p.lddy = lddy; p.N = N; p.dWt = dWt; p.ldw = ldw;
     p.rows_a = rows_a;
@@ -1519,15 +1578,14 @@ extern "C" int hpl_gconv_wgrad_scaled(const float *A, int64_t lda, int64_t rows_
     p.tap_ptr = tap ? tap_ptr : nullptr;
     p.c_tiles = c_tiles;
     p.dbias = tap ? nullptr : dbias;
-    if (tap && dbias) colsum_accumulate(dY, lddy, M, N, dbias, to_stream(stream));
     const int tiles_k = tap ? F * c_tiles : (int)cdiv(p.K, 128);
     const int64_t m_len = tap ? tap_max : M;                 // longest vertex loop of a tile
     if (vec) {
         // wide layers: split operands on the bf16 MFMA (wgrad3.hip)
         WParams q = p;
-        if (launch_wgrad3(q, tap, m_len, to_stream(stream))) {
-            if (!tap && dbias) colsum_accumulate(dY, lddy, M, N, dbias, to_stream(stream));
-            HPL_CHECK_LAUNCH("hpl_gconv_wgrad");
+        if (plan_wgrad3(q, tap, m_len, o)) {
+            p = q;
+            o.bias = dbias ? HPL_WBIAS_COLSUM : HPL_WBIAS_NONE;
             return HPL_OK;
         }
     }
@@ -1552,22 +1610,65 @@ extern "C" int hpl_gconv_wgrad_scaled(const float *A, int64_t lda, int64_t rows_
     }
     p.m_per_split = cdiv(cdiv(m_len, splits), 32) * 32;
     if (!tap) splits = cdiv(m_len, p.m_per_split);
-    dim3 grid(tiles, (unsigned)splits);
+    o.family = HPL_FAMILY_FP32;
+    o.bn = bn; o.vec = vec ? 1 : 0; o.tap = tap ? 1 : 0;
+    // BN = 128 with vector loads: 8 waves (2x4), 4 waves per SIMD, 2-5 % over 4 waves; always with the two register sets
+    o.threads = (bn == 128 && vec) ? 512 : 256;
+    o.deep = (bn == 128 && vec) ? 1 : 0;
+    o.tiles_k = tiles_k; o.tiles_n = p.tiles_n;
+    o.bias = !dbias ? HPL_WBIAS_NONE : (tap ? HPL_WBIAS_COLSUM : HPL_WBIAS_KERNEL);
+    o.tiles = tiles; o.splits = splits; o.m_per_split = p.m_per_split;
+    return HPL_OK;
+}
+}  // namespace
+
+extern "C" int hpl_wgrad_launch_info(const float *A, int64_t lda, int64_t rows_a, const int32_t *nbr,
+                                     int64_t nbr_stride, int64_t reg_stride, int64_t M, int C, int F,
+                                     const float *dY, int64_t lddy, int N, float *dWt, int64_t ldw,
+                                     const int32_t *tap_m, const int32_t *tap_row, const int32_t *tap_ptr,
+                                     int64_t tap_max, float *dbias, const float *a_amax, const float *dy_amax,
+                                     hpl_wgrad_info *info) {
+    HPL_REQUIRE(info, "hpl_wgrad_launch_info: null info");
+    WParams p;
+    int launch = 0;
+    return plan_wgrad(A, lda, rows_a, nbr, nbr_stride, reg_stride, M, C, F, dY, lddy, N, dWt, ldw, tap_m, tap_row, tap_ptr, tap_max,
+                      dbias, a_amax, dy_amax, p, *info, &launch);
+}
+
+extern "C" int hpl_gconv_wgrad_scaled(const float *A, int64_t lda, int64_t rows_a, const int32_t *nbr,
+                                      int64_t nbr_stride, int64_t reg_stride, int64_t M, int C, int F,
+                                      const float *dY, int64_t lddy, int N, float *dWt, int64_t ldw,
+                                      const int32_t *tap_m, const int32_t *tap_row, const int32_t *tap_ptr,
+                                      int64_t tap_max, float *dbias, const float *a_amax, const float *dy_amax,
+                                      hplStream stream) {
+    WParams p;
+    hpl_wgrad_info o;
+    int launch = 0;
+    const int rc = plan_wgrad(A, lda, rows_a, nbr, nbr_stride, reg_stride, M, C, F, dY, lddy, N, dWt, ldw, tap_m, tap_row, tap_ptr,
+                              tap_max, dbias, a_amax, dy_amax, p, o, &launch);
+    if (rc != HPL_OK || !launch) return rc;
     hipStream_t s = to_stream(stream);
+    if (o.bias == HPL_WBIAS_COLSUM && o.tap) colsum_accumulate(dY, lddy, M, N, dbias, s);
+    if (o.family != HPL_FAMILY_FP32) {
+        launch_wgrad3(p, o, s);
+        if (o.bias == HPL_WBIAS_COLSUM && !o.tap) colsum_accumulate(dY, lddy, M, N, dbias, s);
+        HPL_CHECK_LAUNCH("hpl_gconv_wgrad");
+        return HPL_OK;
+    }
+    const dim3 grid((unsigned)o.tiles, (unsigned)o.splits);
 #define LAUNCH(BN_)                                                          \
     do {                                                                     \
-        if (tap) k_wgrad<BN_, true, true><<<grid, 256, 0, s>>>(p);           \
-        else if (vec) k_wgrad<BN_, true, false><<<grid, 256, 0, s>>>(p);     \
+        if (o.tap) k_wgrad<BN_, true, true><<<grid, 256, 0, s>>>(p);         \
+        else if (o.vec) k_wgrad<BN_, true, false><<<grid, 256, 0, s>>>(p);   \
         else k_wgrad<BN_, false, false><<<grid, 256, 0, s>>>(p);             \
     } while (0)
-    if (bn == 128 && vec) {     // 8 waves (2x4): 4 waves per SIMD, 2-5 % over 4 waves
-        constexpr bool deep = true;
-        if (tap && deep) k_wgrad<128, true, true, 512, true><<<grid, 512, 0, s>>>(p);
-        else if (tap) k_wgrad<128, true, true, 512><<<grid, 512, 0, s>>>(p);
-        else if (deep) k_wgrad<128, true, false, 512, true><<<grid, 512, 0, s>>>(p);
+    if (o.threads == 512) {
+        if (o.tap && o.deep) k_wgrad<128, true, true, 512, true><<<grid, 512, 0, s>>>(p);
+        else if (o.tap) k_wgrad<128, true, true, 512><<<grid, 512, 0, s>>>(p);
+        else if (o.deep) k_wgrad<128, true, false, 512, true><<<grid, 512, 0, s>>>(p);
         else k_wgrad<128, true, false, 512><<<grid, 512, 0, s>>>(p);
     } else
-    if (bn == 128) LAUNCH(128); else if (bn == 64) LAUNCH(64); else LAUNCH(32);
+    if (o.bn == 128) LAUNCH(128); else if (o.bn == 64) LAUNCH(64); else LAUNCH(32);
 #undef LAUNCH
     HPL_CHECK_LAUNCH("hpl_gconv_wgrad");
     return HPL_OK;

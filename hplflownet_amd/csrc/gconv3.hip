@@ -1122,7 +1122,7 @@ int hpl_gc::split_planes() {
     return planes;
 }
 
-bool hpl_gc::launch_split3(GParams &p, hipStream_t s) {
+bool hpl_gc::plan_split3(GParams &p, hpl_gconv_info &o) {
     // qualifying launches: row-ordered stencil passes (or dense GEMMs) of wide layers, no scatter / split-K
     if (!split3_enabled() || p.scat || p.C < 32 || p.K > 32768) return false;
     if (p.F > 15 || (p.w_bytes / (p.ldw * 4)) % 8 != 0) return false;
@@ -1207,43 +1207,62 @@ bool hpl_gc::launch_split3(GParams &p, hipStream_t s) {
         if (!epi) p.epi_fast = 0;
     }
     p.y_amax_done = (p.y_amax && p.epi_fast && p.splits <= 1) ? 1 : 0;      // (else hpl_gconv_forward reduces Y afterwards)
+    o.family = p.planes == 2 ? HPL_FAMILY_PAIRS : HPL_FAMILY_TRIPLES;
+    o.bm = BM3; o.bn = BN; o.threads = bn256 ? 512 : 256;
     // instances by the taps whose indices a tile stages in LDS: 1 (dense GEMMs), <= 8 (tap-group passes), <= 15
+    o.f_lds = p.F == 1 ? 1 : (p.F <= 8 ? 8 : 15);
+    o.compact = 0;
+    o.splits = p.splits;
+    o.guard_sets = (p.planes == 2 && p.a_guard) ? 2 : 1;
+    p.guard_partials = (o.guard_sets == 2 && p.splits > 1) ? 1 : 0;      // (read by the finish kernels only)
+    o.col_share = p.col_share; o.col_rows = p.col_rows;
+    o.tile_tables = p.tile_idx ? 1 : 0;
+    o.epi_fast = p.epi_fast;
+    o.tiles_m = p.tiles_m; o.tiles_n = p.tiles_n;
+    o.grid = grid;
+    return true;
+}
+
+void hpl_gc::launch_split3(const GParams &p, const hpl_gconv_info &o, hipStream_t s) {
+    // every choice below is read from the planned struct: family (operand planes), bn, f_lds (taps staged), guard_sets, splits
+    const int grid = (int)o.grid;
+    const bool bn256 = o.bn == 256;
+    const int fl = o.f_lds;
     // (a three-stage weight ring for the 256-wide tile was A/B'd in round 3 and lost: four stages stay)
-    if (p.planes == 2) {
+    if (o.family == HPL_FAMILY_PAIRS) {
         if (bn256) {
-            if (p.F == 1) k_gconv3w<1, 4, 2><<<grid, 512, 0, s>>>(p);
-            else if (p.F <= 8) k_gconv3w<8, 4, 2><<<grid, 512, 0, s>>>(p);
+            if (fl == 1) k_gconv3w<1, 4, 2><<<grid, 512, 0, s>>>(p);
+            else if (fl == 8) k_gconv3w<8, 4, 2><<<grid, 512, 0, s>>>(p);
             else k_gconv3w<15, 4, 2><<<grid, 512, 0, s>>>(p);
         } else {
-            if (p.F == 1) k_gconv3<2, 1, 2><<<grid, 256, 0, s>>>(p);
-            else if (p.F <= 8) k_gconv3<2, 8, 2><<<grid, 256, 0, s>>>(p);
+            if (fl == 1) k_gconv3<2, 1, 2><<<grid, 256, 0, s>>>(p);
+            else if (fl == 8) k_gconv3<2, 8, 2><<<grid, 256, 0, s>>>(p);
             else k_gconv3<2, 15, 2><<<grid, 256, 0, s>>>(p);
         }
-        if (p.a_guard) {
+        if (o.guard_sets == 2) {
             // the guard's second launch: the same tiles on the residuals; it adds what the first launch stored and finishes.
             // (It leaves at once when the operand has no quiet row: an empty launch of this grid, 2-3 us.)
             GParams q = p;
             const int ggrid = grid;
-            if (p.splits > 1) { q.partial = p.partial + (int64_t)p.splits * p.M * p.N; p.guard_partials = 1; }      // a second set of partial tiles (k_gconv_finish adds both)
+            if (o.splits > 1) q.partial = p.partial + (int64_t)o.splits * p.M * p.N;      // a second set of partial tiles (k_gconv_finish adds both: plan_split3 set guard_partials)
             else { q.res = p.Y; q.ldres = p.ldy; q.res_mod = p.M; q.bias = nullptr; }
             if (bn256) {
-                if (p.F == 1) k_gconv3w<1, 4, 2, true><<<ggrid, 512, 0, s>>>(q);
-                else if (p.F <= 8) k_gconv3w<8, 4, 2, true><<<ggrid, 512, 0, s>>>(q);
+                if (fl == 1) k_gconv3w<1, 4, 2, true><<<ggrid, 512, 0, s>>>(q);
+                else if (fl == 8) k_gconv3w<8, 4, 2, true><<<ggrid, 512, 0, s>>>(q);
                 else k_gconv3w<15, 4, 2, true><<<ggrid, 512, 0, s>>>(q);
             } else {
-                if (p.F == 1) k_gconv3<2, 1, 2, 3, true><<<ggrid, 256, 0, s>>>(q);
-                else if (p.F <= 8) k_gconv3<2, 8, 2, 3, true><<<ggrid, 256, 0, s>>>(q);
+                if (fl == 1) k_gconv3<2, 1, 2, 3, true><<<ggrid, 256, 0, s>>>(q);
+                else if (fl == 8) k_gconv3<2, 8, 2, 3, true><<<ggrid, 256, 0, s>>>(q);
                 else k_gconv3<2, 15, 2, 3, true><<<ggrid, 256, 0, s>>>(q);
             }
         }
     } else if (bn256) {
-        if (p.F == 1) k_gconv3w<1, 4, 3><<<grid, 512, 0, s>>>(p);
-        else if (p.F <= 8) k_gconv3w<8, 4, 3><<<grid, 512, 0, s>>>(p);
+        if (fl == 1) k_gconv3w<1, 4, 3><<<grid, 512, 0, s>>>(p);
+        else if (fl == 8) k_gconv3w<8, 4, 3><<<grid, 512, 0, s>>>(p);
         else k_gconv3w<15, 4, 3><<<grid, 512, 0, s>>>(p);
     } else {
-        if (p.F == 1) k_gconv3<2, 1, 3><<<grid, 256, 0, s>>>(p);
-        else if (p.F <= 8) k_gconv3<2, 8, 3><<<grid, 256, 0, s>>>(p);
+        if (fl == 1) k_gconv3<2, 1, 3><<<grid, 256, 0, s>>>(p);
+        else if (fl == 8) k_gconv3<2, 8, 3><<<grid, 256, 0, s>>>(p);
         else k_gconv3<2, 15, 3><<<grid, 256, 0, s>>>(p);
     }
-    return true;
 }

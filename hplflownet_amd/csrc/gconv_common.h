@@ -102,7 +102,7 @@ __device__ __forceinline__ void tile_coords(const GParams &p, int &tm, int &tn, 
     const int xcd = bid % 8, pos = bid / 8;
     const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;   // bijective
     if (p.row_perm && p.col_share < 0) {
-        // Row-major order (round 6; the split-operand launches, gconv3.hip launch_split3): XCD x owns the scheduled tile-rows x, x + 8, ... (heaviest first) and
+        // Row-major order (round 6; the split-operand launches, gconv3.hip plan_split3): XCD x owns the scheduled tile-rows x, x + 8, ... (heaviest first) and
         // walks the column tiles of a tile-row back to back, so the tiles_n column tiles of one tile-row are resident on ONE XCD
         // at the same time: its gathered A rows are fetched into that L2 once, not once per column tile; the weight panels of all
         // column tiles then stream through every L2 (from the Infinity Cache).  Grid = 8 * col_rows * tiles_n.
@@ -179,8 +179,12 @@ __device__ __forceinline__ void tile_coords(const GParams &p, int &tm, int &tn) 
 
 // host side (gconv.hip / gconv3.hip)
 int fill_params(const hpl_gconv_desc *d, GParams &p, const char *who);
-// the split-operand kernel (gconv3.hip): true if it took the launch
-bool launch_split3(GParams &p, hipStream_t s);
+// Selection and launch are two steps: plan_* are pure host functions (no HIP call, no device memory read) that finish the
+// launch fields of p and describe the instance in an hpl_gconv_info; launch_* start exactly what that struct says.
+// hpl_gconv_launch_info reports the same struct, so what a test reads there is what runs.
+// the split-operand kernels (gconv3.hip): true if they take the launch
+bool plan_split3(GParams &p, hpl_gconv_info &o);
+void launch_split3(const GParams &p, const hpl_gconv_info &o, hipStream_t s);
 // HPL_MATH=f32 keeps every launch on the fp32 MFMA (A/B runs, parity baselines)
 bool split3_enabled();
 // operand planes of the split kernels: 2 = fp16 pairs (default), 3 = bf16 triples (HPL_MATH=bf16x3), 0 = HPL_MATH=f32
@@ -201,10 +205,10 @@ __device__ __forceinline__ bool guard_tripped(const float *a_amax, const unsigne
     return (am >> 23) >= (rmin >> 23) + (unsigned)GUARD_GAP && (am >> 23) < 255u;
 }
 constexpr int RESID_SHIFT = 24;          // residual scale 2^24: (a s - hi - lo) 2^24 < 2^15.01 for every a s < 2^15
-// the cheap part of launch_split3's test (the callers decide with it whether to compute the largest magnitude of A)
+// the cheap part of plan_split3's test (the callers decide with it whether to compute the largest magnitude of A)
 inline bool split3_maybe(int64_t M, int C, int F, int N) {
     if (!(C >= 32 && N >= 256 && M >= 1024 && F <= 15)) return false;
-    // ... and the shape tests of launch_split3 (round 6: the 1x1 convs of level 3 -- 1 787 rows -- had their operand reduced, 7 us
+    // ... and the shape tests of plan_split3 (round 6: the 1x1 convs of level 3 -- 1 787 rows -- had their operand reduced, 7 us
     // each, and then ran on the fp32 kernel): dense launches below 8 192 rows that do not fill half the CUs with 128 x 256 tiles, and
     // mid-size stencils that cannot be split over K into one round of workgroups, stay on the fp32 MFMA
     const int64_t tiles256 = ((M + 127) / 128) * ((N + 255) / 256);
@@ -231,8 +235,9 @@ struct WParams {
     int64_t rows_a;      // rows of A (0 = unknown)
     const float *a_amax; const float *dy_amax;     // optional DEVICE scalars (hpl_amax of A / dY): both given = fp16-pair operands
 };
-// the split-operand weight gradient (wgrad3.hip): true if it took the launch.  tap: p.tap_* are set (k tiles = (tap, channel
+// the split-operand weight gradient (wgrad3.hip): plan_wgrad3 is true if it takes the launch (pure, as plan_split3).  tap: p.tap_* are set (k tiles = (tap, channel
 // block)); m_len = longest vertex loop of a tile
-bool launch_wgrad3(WParams &p, bool tap, int64_t m_len, hipStream_t s);
+bool plan_wgrad3(WParams &p, bool tap, int64_t m_len, hpl_wgrad_info &o);
+void launch_wgrad3(const WParams &p, const hpl_wgrad_info &o, hipStream_t s);
 
 }  // namespace hpl_gc

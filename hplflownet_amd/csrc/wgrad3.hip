@@ -284,7 +284,7 @@ __global__ void __launch_bounds__(W3_NT) k_wgrad3(const WParams p) {
     wait_vm(N0{});
 
     // ---- epilogue: C/D layout of the 32x32 MFMA: col = lane & 31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).  Buffer atomics with
-    // 32-bit byte offsets (the image is far below 2 GB: checked by launch_wgrad3), out of range for rows past C / columns past N
+    // 32-bit byte offsets (the image is far below 2 GB: checked by plan_wgrad3), out of range for rows past C / columns past N
     const float u_a = split_unscale(s_a), u_d = split_unscale(s_d);      // (1 for PL = 3)
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void *)p.dWt, (short)0, 0x7fffffff, 0x00020000);
     const unsigned ldw_b = (unsigned)p.ldw * 4u;
@@ -305,7 +305,7 @@ __global__ void __launch_bounds__(W3_NT) k_wgrad3(const WParams p) {
 
 }  // namespace
 
-bool hpl_gc::launch_wgrad3(WParams &p, bool tap, int64_t m_len, hipStream_t s) {
+bool hpl_gc::plan_wgrad3(WParams &p, bool tap, int64_t m_len, hpl_wgrad_info &o) {
     // qualifying launches: the wide layers (tap mode stencils, dense 1x1 convs) with enough vertices to fill the chip
     static const int on = getenv("HPL_WGRAD3") ? atoi(getenv("HPL_WGRAD3")) : 1;
     constexpr int min_rows = 8192;
@@ -329,15 +329,22 @@ bool hpl_gc::launch_wgrad3(WParams &p, bool tap, int64_t m_len, hipStream_t s) {
     if (force > 0) splits = force;
     p.m_per_split = cdiv(cdiv(m_len, splits), W3_BMS) * W3_BMS;
     if (!tap) splits = cdiv(m_len, p.m_per_split);
-    const dim3 grid((unsigned)tiles, (unsigned)splits);
     // fp16 pairs when both largest magnitudes were given (and the mode allows), else the exact bf16 triples
     const bool pairs = split_planes() == 2 && p.a_amax && p.dy_amax;
-    if (pairs) {
-        if (tap) k_wgrad3<true, 2><<<grid, W3_NT, 0, s>>>(p);
+    o.family = pairs ? HPL_FAMILY_PAIRS : HPL_FAMILY_TRIPLES;
+    o.bn = W3_BN; o.vec = 1; o.tap = tap ? 1 : 0; o.threads = W3_NT; o.deep = 0;
+    o.tiles_k = (tap ? p.F : 1) * p.c_tiles; o.tiles_n = p.tiles_n;
+    o.tiles = tiles; o.splits = splits; o.m_per_split = p.m_per_split;
+    return true;
+}
+
+void hpl_gc::launch_wgrad3(const WParams &p, const hpl_wgrad_info &o, hipStream_t s) {
+    const dim3 grid((unsigned)o.tiles, (unsigned)o.splits);
+    if (o.family == HPL_FAMILY_PAIRS) {
+        if (o.tap) k_wgrad3<true, 2><<<grid, W3_NT, 0, s>>>(p);
         else k_wgrad3<false, 2><<<grid, W3_NT, 0, s>>>(p);
     } else {
-        if (tap) k_wgrad3<true, 3><<<grid, W3_NT, 0, s>>>(p);
+        if (o.tap) k_wgrad3<true, 3><<<grid, W3_NT, 0, s>>>(p);
         else k_wgrad3<false, 3><<<grid, W3_NT, 0, s>>>(p);
     }
-    return true;
 }

@@ -1328,30 +1328,26 @@ def amax_rows(X, rows=None, cols=None):
     return out, guard
 
 
-def _mat(x, what):
+def _mat(x, what, dev=True):
     """(data_ptr, leading dimension, rows, cols) of a channel-last 2-D float32 device matrix, validated with one
-    stride() / shape read (this sits on the host's critical path: ~100 calls per forward)."""
+    stride() / shape read (this sits on the host's critical path: ~100 calls per forward).  dev=False (launch queries): any device."""
     st, sh = x.stride(), x.shape
-    if len(st) != 2 or x.dtype is not torch.float32 or not x.is_cuda or (st[1] != 1 and sh[1] > 1):
+    if len(st) != 2 or x.dtype is not torch.float32 or (dev and not x.is_cuda) or (st[1] != 1 and sh[1] > 1):
         raise _lib.HplError('%s must be a channel-last 2-D float32 device tensor with unit channel stride, '
                             'got shape %s strides %s dtype %s device %s' % (what, tuple(sh), st, x.dtype, x.device))
     return x.data_ptr(), (st[0] if sh[0] > 1 else max(sh[1], st[0])), sh[0], sh[1]
 
 
-def gconv_raw(A, nbr, M, C, F, Wt, N, bias=None, act=ACT_NONE, res=None, res_mod=0, out=None,
-              scat=None, scat_c=0, naive=False, slope=LEAKY_RATE, row_perm=None, split_k=True, reg_stride=0, tiles=None,
-              out2=None, rows2=0, Wt3=None, y_amax=None, guard=True, y_guard=None, guard_trips=None):
-    """Y[m, n] = act(bias[n] + res[m % res_mod, n] + sum_{f,c} A[nbr[f, m], c] * Wt[f*C + c, n]).
-    row_perm (int32 [M], from tap_order): processing order of the output rows; results are unchanged.
-    nbr None and reg_stride > 0: tap f of row m reads row f*reg_stride + m (no table: the displacement
-    filter of the correlation layer, whose taps are the F blocks of H1 virtual vertices).
-    out2 / rows2: rows m < rows2 of the result are also stored to the matrix (view) `out2`.
-    y_amax (float32 [1], device, cleared by the caller): max(y_amax, largest |Y|) is left there; y_guard (int32 [1], cleared by the
-    caller): the range-guard word of Y beside it.  guard: fp16-pair launches take the range guard of A with its largest magnitude
-    (one pass: hpl_amax_rows) -- a second pass over the residuals when A has a row 2^18 below its largest entry; guard_trips
-    (int32 [1], device): += 1 when this launch took it."""
+def _gconv_desc(A, nbr, M, C, F, Wt, N, bias, act, res, res_mod, out, scat, scat_c, slope, row_perm, split_k, reg_stride, tiles,
+                out2, rows2, Wt3, y_amax, guard, y_guard, guard_trips, query=False):
+    """-> (hpl_gconv_desc, out, stream, tensors the descriptor points to) of a gconv_raw call: the one place the descriptor is
+    built, for the launch (gconv_raw) and for the query of the instance it takes (gconv_launch_info).  query: the tensors may live on any device -- the selection
+    looks at a pointer's null-ness and alignment only --, nothing is launched and no device memory is allocated."""
+    dev = not query
+    ptr = _addr if query else _lib.ptr
+    keep = None           # device scalars made here: they must outlive the launch
     d = GConvDesc()
-    d.A, d.lda, d.rows_a, a_cols = _mat(A, 'activation')
+    d.A, d.lda, d.rows_a, a_cols = _mat(A, 'activation', dev)
     if nbr is not None:
         nst, nsh = nbr.stride(), nbr.shape
         if nbr.dtype is not torch.int32 or len(nsh) != 2 or nsh[0] != F or nsh[1] != M or nst[1] != 1:
@@ -1378,29 +1374,37 @@ def gconv_raw(A, nbr, M, C, F, Wt, N, bias=None, act=ACT_NONE, res=None, res_mod
         elif scat is None and split3_maybe(M, C, F, N):
             # fp16 pairs: the launch scales A by its largest magnitude (csrc/gconv_common.h split3_maybe: launches that cannot
             # qualify skip the reduction and run on the fp32 MFMA)
-            if guard:
-                a_amax, a_guard = amax_rows(A, cols=C)
-                d.a_guard = ptr(a_guard)
+            if query:             # (the reductions are launches: a query stands a non-null scalar in for their results)
+                d.a_amax = _QUERY_PTR
+                if guard:
+                    d.a_guard = _QUERY_PTR
+            elif guard:
+                keep = amax_rows(A, cols=C)
+                d.a_amax, d.a_guard = ptr(keep[0]), ptr(keep[1])
                 if guard_trips is not None:
                     d.guard_trips = ptr(guard_trips)
             else:
-                a_amax = amax(A, cols=C)
+                keep = amax(A, cols=C)
+                d.a_amax = ptr(keep)
             d.Wt3, d.wt3_plane_stride, d.wt3_planes = ptr(Wt3.planes), Wt3.planes.stride(0), 2
-            d.a_amax, d.w_amax = ptr(a_amax), ptr(Wt3.amax)
+            d.w_amax = ptr(Wt3.amax)
     if bias is not None:
         d.bias = ptr(bias)
     if res is not None:
-        d.res, d.ldres, rrows, _ = _mat(res, 'res')
+        d.res, d.ldres, rrows, _ = _mat(res, 'res', dev)
         d.res_mod = res_mod or rrows
     if scat is not None:
         if out is None:
             raise _lib.HplError('scatter epilogue needs a zero-initialised `out`')
         d.scat, d.scat_stride, d.scat_c = ptr(scat), scat.stride(0), scat_c
-    elif out is None:
+    elif out is None and not query:
         out = torch.empty((M, N), dtype=torch.float32, device=A.device)
-    d.Y, d.ldy, _, _ = _mat(out, 'out')
+    if out is None:               # (a query: the result gconv_raw would allocate -- contiguous and aligned)
+        d.Y, d.ldy = _QUERY_PTR, N
+    else:
+        d.Y, d.ldy, _, _ = _mat(out, 'out', dev)
     if out2 is not None:
-        d.Y2, d.ldy2, r2, c2 = _mat(out2, 'out2')
+        d.Y2, d.ldy2, r2, c2 = _mat(out2, 'out2', dev)
         if scat is not None or rows2 > r2 or c2 < N:
             raise _lib.HplError('second destination: %d rows x %d columns for rows2=%d N=%d' % (r2, c2, rows2, N))
         d.rows2 = rows2
@@ -1416,16 +1420,59 @@ def gconv_raw(A, nbr, M, C, F, Wt, N, bias=None, act=ACT_NONE, res=None, res_mod
             d.tile_idx, d.tile_mask, d.tile_bm = ptr(tiles[0]), ptr(tiles[1]), tiles[0].shape[2]
         if CLOCK_PROBE is not None and N > 64 and M >= 16384:
             d.clock_probe = CLOCK_PROBE.data_ptr()
-    st = stream()
+    st = None if query else stream()
     if split_k and scat is None and M * N <= _SPLITK_MAX_ELEMS:
-        ws = _splitk_workspace(A.device, st)
-        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
+        if query:
+            d.ws, d.ws_bytes = _QUERY_PTR, _SPLITK_WS_FLOATS * 4
+        else:
+            ws = _splitk_workspace(A.device, st)
+            d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
+    return d, out, st, keep
+
+
+def gconv_raw(A, nbr, M, C, F, Wt, N, bias=None, act=ACT_NONE, res=None, res_mod=0, out=None,
+              scat=None, scat_c=0, naive=False, slope=LEAKY_RATE, row_perm=None, split_k=True, reg_stride=0, tiles=None,
+              out2=None, rows2=0, Wt3=None, y_amax=None, guard=True, y_guard=None, guard_trips=None):
+    """Y[m, n] = act(bias[n] + res[m % res_mod, n] + sum_{f,c} A[nbr[f, m], c] * Wt[f*C + c, n]).
+    row_perm (int32 [M], from tap_order): processing order of the output rows; results are unchanged.
+    nbr None and reg_stride > 0: tap f of row m reads row f*reg_stride + m (no table: the displacement
+    filter of the correlation layer, whose taps are the F blocks of H1 virtual vertices).
+    out2 / rows2: rows m < rows2 of the result are also stored to the matrix (view) `out2`.
+    y_amax (float32 [1], device, cleared by the caller): max(y_amax, largest |Y|) is left there; y_guard (int32 [1], cleared by the
+    caller): the range-guard word of Y beside it.  guard: fp16-pair launches take the range guard of A with its largest magnitude
+    (one pass: hpl_amax_rows) -- a second pass over the residuals when A has a row 2^18 below its largest entry; guard_trips
+    (int32 [1], device): += 1 when this launch took it."""
+    d, out, st, _keep = _gconv_desc(A, nbr, M, C, F, Wt, N, bias, act, res, res_mod, out, scat, scat_c, slope, row_perm, split_k,
+                                    reg_stride, tiles, out2, rows2, Wt3, y_amax, guard, y_guard, guard_trips)
     lib = _lib.load()
     rc = (lib.hpl_gconv_forward_naive if naive else lib.hpl_gconv_forward)(ctypes.byref(d), st)
     if rc != 0:
         check(rc, 'hpl_gconv_forward')
     return out
 
+
+def _info_dict(info):
+    return {name: getattr(info, name) for name, _ in info._fields_ if name != 'pad_'}
+
+
+def gconv_launch_info(A, nbr, M, C, F, Wt, N, bias=None, act=ACT_NONE, res=None, res_mod=0, out=None,
+                      scat=None, scat_c=0, slope=LEAKY_RATE, row_perm=None, split_k=True, reg_stride=0, tiles=None,
+                      out2=None, rows2=0, Wt3=None, y_amax=None, guard=True, y_guard=None, guard_trips=None):
+    """The kernel instance gconv_raw takes for the same arguments, as a dict of hpl_gconv_info's fields (include/hpl_bcl.h).
+    Host code only: it launches nothing and the tensors may be host tensors of the same shapes, strides and alignment."""
+    d = _gconv_desc(A, nbr, M, C, F, Wt, N, bias, act, res, res_mod, out, scat, scat_c, slope, row_perm, split_k,
+                    reg_stride, tiles, out2, rows2, Wt3, y_amax, guard, y_guard, guard_trips, query=True)[0]
+    info = _lib.GConvInfo()
+    check(_lib.load().hpl_gconv_launch_info(ctypes.byref(d), ctypes.byref(info)), 'hpl_gconv_launch_info')
+    return _info_dict(info)
+
+
+def _addr(t):
+    """Address of a tensor on any device (or None): for the launch queries."""
+    return None if t is None else t.data_ptr()
+
+
+_QUERY_PTR = 256      # a non-null, aligned stand-in for device memory a query would otherwise have to allocate
 
 #: diagnostic (bench.py): a zeroed int64 device tensor (>= 2 entries); sampled workgroups of the wide row-ordered
 #: launches add their residence in shader cycles to [0] and in 100 MHz wall ticks to [1] -- the clock the chip
@@ -1434,6 +1481,7 @@ CLOCK_PROBE = None
 
 _SPLITK_MAX_ELEMS = 8 << 20          # split-K is offered for outputs of <= 8 M elements (the launch picks the count)
 _SPLITK_WS = {}
+_SPLITK_WS_FLOATS = 16 << 20
 
 
 def _splitk_workspace(device, st):
@@ -1442,30 +1490,56 @@ def _splitk_workspace(device, st):
     key = (device, st)
     ws = _SPLITK_WS.get(key)
     if ws is None:
-        ws = _SPLITK_WS[key] = torch.empty(16 << 20, dtype=torch.float32, device=device)
+        ws = _SPLITK_WS[key] = torch.empty(_SPLITK_WS_FLOATS, dtype=torch.float32, device=device)
     return ws
+
+
+def _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=False):
+    """-> (arguments of hpl_gconv_wgrad_scaled up to the stream, dWt, bias gradient or None, device scalars the arguments point
+    to): built in one place for the launch
+    (wgrad_raw) and for the query of its instance (wgrad_launch_info; query: as _gconv_desc)."""
+    ptr = _addr if query else _lib.ptr
+    if not query:
+        A, dY = _cl(A), _cl(dY, 'dY')
+    kp, ldw = round_up(F * C, 32), round_up(N, 4)
+    if query:                     # (nothing is allocated: aligned stand-ins for the gradient and the bias gradient behind it)
+        dWt, gb = None, None
+        p_dWt, p_gb = _QUERY_PTR, (_QUERY_PTR + kp * ldw * 4 if want_bias else None)
+    else:
+        buf = torch.zeros(kp * ldw + (ldw if want_bias else 0), dtype=torch.float32, device=A.device)
+        dWt = buf[:kp * ldw].view(kp, ldw)
+        gb = buf[kp * ldw:kp * ldw + N] if want_bias else None
+        p_dWt, p_gb = ptr(dWt), ptr(gb)
+    tl, tr, tp = taps if (taps is not None and nbr is not None) else (None, None, None)
+    # wide layers (csrc/wgrad3.hip's test): fp16-pair operands need the largest magnitudes of both
+    sa = sd = keep = None
+    if SPLIT_PLANES == 2 and SPLIT3 and N >= 256 and C >= 128 and M >= 8192 and (tl is not None or (F == 1 and nbr is None)):
+        if query:
+            sa = sd = _QUERY_PTR
+        else:
+            keep = (amax(A, cols=C), amax(dY, rows=M, cols=N))       # (both alive until the launch is enqueued)
+            sa, sd = ptr(keep[0]), ptr(keep[1])
+    return (ptr(A), _ld(A), A.shape[0], ptr(nbr), nbr.stride(0) if nbr is not None else 0,
+            reg_stride if nbr is None else 0, M, C, F, ptr(dY), _ld(dY), N, p_dWt, ldw,
+            ptr(tl), ptr(tr), ptr(tp), M if tl is not None else 0, p_gb, sa, sd), dWt, gb, keep
 
 
 def wgrad_raw(A, nbr, M, C, F, dY, N, taps=None, want_bias=False, reg_stride=0):
     """-> dWt [roundup(F*C,32), roundup(N,4)] = sum_m A[nbr[f,m], c] * dY[m, n]  (and, with want_bias,
     the bias gradient sum_m dY[m, :] from the same launch).
     taps = tap_lists(nbr): sum over the present vertices of each tap only (wide layers)."""
-    A, dY = _cl(A), _cl(dY, 'dY')
-    kp, ldw = round_up(F * C, 32), round_up(N, 4)
-    buf = torch.zeros(kp * ldw + (ldw if want_bias else 0), dtype=torch.float32, device=A.device)
-    dWt = buf[:kp * ldw].view(kp, ldw)
-    gb = buf[kp * ldw:kp * ldw + N] if want_bias else None
-    tl, tr, tp = taps if (taps is not None and nbr is not None) else (None, None, None)
-    # wide layers (csrc/wgrad3.hip's test): fp16-pair operands need the largest magnitudes of both
-    sa = sd = None
-    if SPLIT_PLANES == 2 and SPLIT3 and N >= 256 and C >= 128 and M >= 8192 and (tl is not None or (F == 1 and nbr is None)):
-        sa, sd = amax(A, cols=C), amax(dY, rows=M, cols=N)
-    check(_lib.load().hpl_gconv_wgrad_scaled(ptr(A), _ld(A), A.shape[0], ptr(nbr), nbr.stride(0) if nbr is not None else 0,
-                                             reg_stride if nbr is None else 0, M, C, F, ptr(dY), _ld(dY), N, ptr(dWt), ldw,
-                                             ptr(tl), ptr(tr), ptr(tp),
-                                             M if tl is not None else 0, ptr(gb), ptr(sa), ptr(sd), stream()),
-          'hpl_gconv_wgrad')
+    args, dWt, gb, _keep = _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride)
+    check(_lib.load().hpl_gconv_wgrad_scaled(*(args + (stream(),))), 'hpl_gconv_wgrad')
     return (dWt, gb) if want_bias else dWt
+
+
+def wgrad_launch_info(A, nbr, M, C, F, dY, N, taps=None, want_bias=False, reg_stride=0):
+    """The kernel instance wgrad_raw takes for the same arguments, as a dict of hpl_wgrad_info's fields (include/hpl_bcl.h).
+    Host code only, as gconv_launch_info."""
+    args = _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=True)[0]
+    info = _lib.WGradInfo()
+    check(_lib.load().hpl_wgrad_launch_info(*(args + (ctypes.byref(info),))), 'hpl_wgrad_launch_info')
+    return _info_dict(info)
 
 
 def colsum(X):

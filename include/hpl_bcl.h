@@ -362,6 +362,60 @@ int hpl_gconv_wgrad_scaled(const float *A, int64_t lda, int64_t rows_a, const in
                            const int32_t *tap_m, const int32_t *tap_row, const int32_t *tap_ptr,
                            int64_t tap_max, float *dbias, const float *a_amax, const float *dy_amax, hplStream stream);
 
+/* Which kernel instance a launch takes.  hpl_gconv_forward / hpl_gconv_wgrad_scaled pick one of many instances from the
+ * shape, the strides and the alignment of the operands; the two queries below run the SAME selection (the launch path launches
+ * from the struct they fill) and report it.  They call no HIP function and read no device memory: a pointer counts only as NULL
+ * or not and by its 16-byte alignment, so they run on a machine without a GPU.  They return what the launch would return for
+ * the same arguments (HPL_EINVAL with hpl_last_error() set for a refused launch); M == 0 leaves the struct zeroed. */
+#define HPL_FAMILY_FP32 0      /* fp32 operands on the fp32 MFMA (csrc/gconv.hip) */
+#define HPL_FAMILY_PAIRS 2     /* fp16 pairs (csrc/gconv3.hip, csrc/wgrad3.hip) */
+#define HPL_FAMILY_TRIPLES 3   /* bf16 triples */
+#define HPL_FINISH_NONE 0      /* no split-K: the tiles store the result */
+#define HPL_FINISH_SCALAR 1    /* partial tiles summed by the scalar finish kernel */
+#define HPL_FINISH_VEC4 2      /* ... by the float4 finish kernel */
+typedef struct hpl_gconv_info {
+    int32_t family;            /* HPL_FAMILY_* */
+    int32_t bm, bn;            /* tile: rows x columns of the output */
+    int32_t threads;           /* workgroup size */
+    int32_t avec;              /* 16-byte loads of the gathered rows (C % 4 == 0, lda % 4 == 0, A aligned) */
+    int32_t f_lds;             /* taps whose indices a tile stages in LDS: 1, 8 or 15 */
+    int32_t compact;           /* the three-workgroups-per-CU instance of the 64 x 128 tile (tap groups) */
+    int32_t splits;            /* split-K: workgroups per tile (1 = none) */
+    int32_t guard_sets;        /* passes over the tiles: 2 = a pair launch with a range guard (split-K: a second set of partial tiles) */
+    int32_t col_share;         /* XCD order of a row-permuted launch: XCDs per column tile (0: not column-major, -1: row-major) */
+    int32_t col_rows;          /* tile-rows per virtual column in that order */
+    int32_t tile_tables;       /* the caller's tile index tables are used (cut for this tile height) */
+    int32_t epi_fast;          /* 32-bit buffer addressing in the epilogue */
+    int32_t finish;            /* HPL_FINISH_* */
+    int32_t tiles_m, tiles_n;
+    int64_t grid;              /* workgroups of the (first) tile launch */
+} hpl_gconv_info;
+int hpl_gconv_launch_info(const hpl_gconv_desc *desc /* HOST */, hpl_gconv_info *info /* HOST */);
+
+#define HPL_WBIAS_NONE 0       /* no bias gradient asked for */
+#define HPL_WBIAS_KERNEL 1     /* by the k-tile-0 workgroups of the weight-gradient kernel */
+#define HPL_WBIAS_COLSUM 2     /* by a column-sum launch of its own (tap mode, wgrad3) */
+typedef struct hpl_wgrad_info {
+    int32_t family;            /* HPL_FAMILY_FP32, or the wgrad3 kernel's HPL_FAMILY_PAIRS / HPL_FAMILY_TRIPLES */
+    int32_t bn;                /* columns of dWt per tile (rows: 128) */
+    int32_t vec;               /* 16-byte loads of A and dY */
+    int32_t tap;               /* tap mode: k tiles = (tap, 128-channel block), vertex loops over the tap lists */
+    int32_t threads;           /* 256 or 512 */
+    int32_t deep;              /* two register sets in flight (the 512-thread form) */
+    int32_t tiles_k, tiles_n;
+    int32_t bias;              /* HPL_WBIAS_* */
+    int32_t pad_;
+    int64_t tiles;             /* grid.x = tiles_k * tiles_n */
+    int64_t splits;            /* grid.y: slabs of the vertex loop */
+    int64_t m_per_split;       /* vertices per slab (tap mode: of the longest list) */
+} hpl_wgrad_info;
+int hpl_wgrad_launch_info(const float *A, int64_t lda, int64_t rows_a, const int32_t *nbr,
+                          int64_t nbr_stride, int64_t reg_stride, int64_t M, int C, int F,
+                          const float *dY, int64_t lddy, int N, float *dWt, int64_t ldw,
+                          const int32_t *tap_m, const int32_t *tap_row, const int32_t *tap_ptr,
+                          int64_t tap_max, float *dbias, const float *a_amax, const float *dy_amax,
+                          hpl_wgrad_info *info /* HOST */);
+
 /* out[n] = sum_m X[m*ld + n]   (bias gradients) */
 int hpl_colsum(const float *X, int64_t ld, int64_t M, int N, float *out, hplStream stream);
 /* dX = dY * (Y > 0 ? 1 : slope)   element-wise on [M][N] views (LeakyReLU backward) */

@@ -56,6 +56,19 @@ def test_relayout_job_layout_matches_header():
     assert ctypes.sizeof(_lib.RelayoutJob) == 8 + 4 * 8 + 4 * 4 + 8
 
 
+def test_launch_info_layouts_match_header():
+    hdr = header_text()
+    for cname, cls in (('hpl_gconv_info', _lib.GConvInfo), ('hpl_wgrad_info', _lib.WGradInfo)):
+        struct = hdr[hdr.index('typedef struct %s {' % cname):hdr.index('} %s;' % cname)]
+        struct = re.sub(r'/\*.*?\*/', '', struct, flags=re.S)
+        names = []
+        for decl in re.findall(r'(?:int32_t|int64_t)\s+([\w\s,]+);', struct):
+            names += [n.strip() for n in decl.split(',')]
+        assert names == [f[0] for f in cls._fields_], cname
+    assert ctypes.sizeof(_lib.GConvInfo) == 16 * 4 + 8
+    assert ctypes.sizeof(_lib.WGradInfo) == 10 * 4 + 3 * 8
+
+
 def test_no_cpu_fallback():
     import hplflownet_amd as H
     m = H.BilateralConvFlex(3, 1, 8, [8], 'cpu', True, True, True, False, False, False)
@@ -91,7 +104,8 @@ def test_executor_struct_layouts_match_header(tmp_path):
         pytest.skip('no C compiler')
     mirrors = {'hpl_ref': _lib.Ref, 'hpl_buf': _lib.Buf, 'hpl_weight': _lib.Weight, 'hpl_op': _lib.Op,
                'hpl_level_tables': _lib.LevelTables, 'hpl_gconv_desc': _lib.GConvDesc, 'hpl_relayout_job': _lib.RelayoutJob,
-               'hpl_lattice_spec': _lib.LatticeSpec, 'hpl_split3_job': _lib.Split3Job}
+               'hpl_lattice_spec': _lib.LatticeSpec, 'hpl_split3_job': _lib.Split3Job, 'hpl_gconv_info': _lib.GConvInfo,
+               'hpl_wgrad_info': _lib.WGradInfo}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "hpl_bcl.h"', 'int main(void) {']
     for cname, cls in mirrors.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))

@@ -120,7 +120,7 @@ def test_design_md_quotes_the_committed_profile_set():
 
 def test_split3_maybe_covers_every_launch_the_split_kernel_takes():
     """ops.split3_maybe / gconv_common.h split3_maybe decide whether a launch's operand magnitude is reduced at all: it must say
-    yes wherever launch_split3 (mirrored by bench.split3_takes) takes the launch, and no for the shapes round 6 found reduced in
+    yes wherever plan_split3 (mirrored by bench.split3_takes) takes the launch, and no for the shapes round 6 found reduced in
     vain (the 1x1 convs of level 3: 1 787 rows)."""
     from hplflownet_amd import ops
     if not ops.SPLIT3:

@@ -125,19 +125,21 @@ def _gconv_ref(A, nbr, M, C, F, W, bias, res, res_mod, act, slope=0.1):
     return y
 
 
+# (the instance named beside a case is what ops.gconv_launch_info reports for it; tests/gconv_forms.py holds the table that
+# reaches every instance, <64,128> and COMPACT among them, and tests/test_gconv_forms_cpu.py pins it)
 GCONV_CASES = [
     # M, rowsA, C, F, O, table, bias, res, act
-    (300, 300, 68, 15, 64, True, True, False, True),       # Down blur conv, 64x64 tile
-    (1000, 1000, 64, 1, 64, False, True, False, False),    # 1x1 conv, dense
-    (700, 650, 36, 15, 128, True, True, False, True),      # 128x128 tile, table into a different row set
-    (513, 513, 580, 15, 200, True, False, False, False),   # wide C, K tail (8700 % 32 != 0), N tail
-    (2000, 2000, 3, 1, 32, False, True, False, True),      # conv1 first layer: C=3 scalar path
-    (900, 900, 32, 1, 3, False, True, False, False),       # conv4: N=3
-    (15 * 97, 120, 64, 15, 32, True, True, True, True),    # corr B-term: virtual vertices + broadcast residual
-    (97, 15 * 97, 32, 15, 64, True, True, False, True),    # displacement filter through a regular table
-    (70000, 70000, 68, 15, 64, True, True, False, True),   # enough tiles for the 128-row configs
-    (70000, 500, 64, 15, 32, True, False, False, False),   # 128x32 config
-    (33, 40, 8, 15, 16, True, True, False, True),          # tiny
+    (300, 300, 68, 15, 64, True, True, False, True),       # Down blur conv: <64,64> tile, 8-way small split-K, vec4 finish
+    (1000, 1000, 64, 1, 64, False, True, False, False),    # 1x1 conv, dense: <64,64>, F_LDS 1, no split
+    (700, 650, 36, 15, 128, True, True, False, True),      # <64,64> tile (11 x 2 tiles), 4-way split; table into a different row set
+    (513, 513, 580, 15, 200, True, False, False, False),   # wide C, K tail (8700 % 32 != 0), N tail: <64,64>, 14-way split
+    (2000, 2000, 3, 1, 32, False, True, False, True),      # conv1 first layer: C=3 scalar path, <64,32>
+    (900, 900, 32, 1, 3, False, True, False, False),       # conv4: N=3, <64,32>
+    (15 * 97, 120, 64, 15, 32, True, True, True, True),    # corr B-term: virtual vertices + broadcast residual; <64,32>, 7-way split
+    (97, 15 * 97, 32, 15, 64, True, True, False, True),    # displacement filter through a (random) table; <64,64>, 3-way split
+    (70000, 70000, 68, 15, 64, True, True, False, True),   # N = 64: <64,64> (1094 tiles), 2-way mid split-K, vec4 finish
+    (70000, 500, 64, 15, 32, True, False, False, False),   # <128,32> (547 tiles), no split
+    (33, 40, 8, 15, 16, True, True, False, True),          # tiny: one <64,32> tile
 ]
 
 
@@ -281,7 +283,9 @@ def test_wgrad_colsum_leaky(ops, M, rows, C, F, O):
                                                   (2500, 2500, 580, 15, 96, 0.1)])
 def test_tap_lists_and_wgrad_tap_mode(ops, M, rows, C, F, O, density):
     """Per-tap lists of present vertices (hpl_tap_lists) and the weight gradient summed over them
-    (tap-aligned k tiles): same result as the full vertex loop and as float64."""
+    (tap-aligned k tiles): same result as the full vertex loop and as float64.
+    What ops.wgrad_launch_info reports: C=260 is NOT tap mode (three 128-blocks = 384 channels > 1.25 * 260: the full loop on the
+    512-thread deep form, bias in the kernel); C=128 runs tap mode at BN=64; C=580 runs tap mode on the 512-thread deep form."""
     rng = np.random.RandomState(C + M)
     A = rng.randn(rows, C).astype(np.float32)
     nbr = np.where(rng.rand(F, M) < density, rng.randint(0, rows, size=(F, M)), -1).astype(np.int32)
