@@ -1494,10 +1494,12 @@ def _splitk_workspace(device, st):
     return ws
 
 
-def _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=False):
+def _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=False, scales=True):
     """-> (arguments of hpl_gconv_wgrad_scaled up to the stream, dWt, bias gradient or None, device scalars the arguments point
     to): built in one place for the launch
-    (wgrad_raw) and for the query of its instance (wgrad_launch_info; query: as _gconv_desc)."""
+    (wgrad_raw) and for the query of its instance (wgrad_launch_info; query: as _gconv_desc).
+    scales: True: the largest magnitudes of A and dY are measured where the launch can use them; False: none are passed; a pair
+    of float32 [1] device tensors: the caller's own (upper bounds of the magnitudes of A and dY)."""
     ptr = _addr if query else _lib.ptr
     if not query:
         A, dY = _cl(A), _cl(dY, 'dY')
@@ -1513,7 +1515,13 @@ def _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=False
     tl, tr, tp = taps if (taps is not None and nbr is not None) else (None, None, None)
     # wide layers (csrc/wgrad3.hip's test): fp16-pair operands need the largest magnitudes of both
     sa = sd = keep = None
-    if SPLIT_PLANES == 2 and SPLIT3 and N >= 256 and C >= 128 and M >= 8192 and (tl is not None or (F == 1 and nbr is None)):
+    if scales is not True and scales is not False:
+        keep = tuple(scales)
+        if len(keep) != 2 or any(s.dtype != torch.float32 or s.numel() != 1 for s in keep):
+            raise _lib.HplError('wgrad: scales must be True, False or a pair of float32 [1] tensors')
+        sa, sd = ptr(keep[0]), ptr(keep[1])
+    elif scales and SPLIT_PLANES == 2 and SPLIT3 and N >= 256 and C >= 128 and M >= 8192 and \
+            (tl is not None or (F == 1 and nbr is None)):
         if query:
             sa = sd = _QUERY_PTR
         else:
@@ -1524,19 +1532,21 @@ def _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=False
             ptr(tl), ptr(tr), ptr(tp), M if tl is not None else 0, p_gb, sa, sd), dWt, gb, keep
 
 
-def wgrad_raw(A, nbr, M, C, F, dY, N, taps=None, want_bias=False, reg_stride=0):
+def wgrad_raw(A, nbr, M, C, F, dY, N, taps=None, want_bias=False, reg_stride=0, scales=True):
     """-> dWt [roundup(F*C,32), roundup(N,4)] = sum_m A[nbr[f,m], c] * dY[m, n]  (and, with want_bias,
     the bias gradient sum_m dY[m, :] from the same launch).
-    taps = tap_lists(nbr): sum over the present vertices of each tap only (wide layers)."""
-    args, dWt, gb, _keep = _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride)
+    taps = tap_lists(nbr): sum over the present vertices of each tap only (wide layers).
+    scales: the operand magnitudes of the wide layers' fp16-pair form (csrc/wgrad3.hip).  True: measured here; False: none, so
+    the split-operand kernel takes bf16 triples; (a, d): float32 [1] device tensors >= the largest |A| and |dY|."""
+    args, dWt, gb, _keep = _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, scales=scales)
     check(_lib.load().hpl_gconv_wgrad_scaled(*(args + (stream(),))), 'hpl_gconv_wgrad')
     return (dWt, gb) if want_bias else dWt
 
 
-def wgrad_launch_info(A, nbr, M, C, F, dY, N, taps=None, want_bias=False, reg_stride=0):
+def wgrad_launch_info(A, nbr, M, C, F, dY, N, taps=None, want_bias=False, reg_stride=0, scales=True):
     """The kernel instance wgrad_raw takes for the same arguments, as a dict of hpl_wgrad_info's fields (include/hpl_bcl.h).
     Host code only, as gconv_launch_info."""
-    args = _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=True)[0]
+    args = _wgrad_args(A, nbr, M, C, F, dY, N, taps, want_bias, reg_stride, query=True, scales=scales)[0]
     info = _lib.WGradInfo()
     check(_lib.load().hpl_wgrad_launch_info(*(args + (ctypes.byref(info),))), 'hpl_wgrad_launch_info')
     return _info_dict(info)

@@ -2,6 +2,9 @@
 of cases shared by tests/test_gconv_forms_cpu.py (which instance does a case take: ops.gconv_launch_info / wgrad_launch_info
 against the EXPECT_* entries below) and tests/test_gpu_gconv_forms.py (is that instance right: float64 on the device).
 
+WGRAD3 is the table of the split-operand weight gradient (csrc/wgrad3.hip), with operands whose arithmetic is exact
+(exact_wgrad_operands; tests/test_gpu_wgrad3_exact.py compares them bit for bit).
+
 A case is a dict of shape parameters; its operands are built by forward_operands / wgrad_operands, with the same shapes,
 strides and alignment on either device (the selection reads nothing else).  Shapes are the smallest that reach a form; the
 thresholds they sit on are those of csrc/gconv.hip (plan_forward, plan_cfg, plan_wgrad) and csrc/wgrad3.hip (plan_wgrad3):
@@ -153,6 +156,33 @@ WGRAD = [
 ]
 
 
+# WGRAD3: the forms of the split-operand weight gradient (csrc/wgrad3.hip), each at the smallest shape that reaches it.  Their
+# operands come from exact_wgrad_operands below: integers whose products and sums are exact, so a result has ONE right value.
+# Dense slabs are m_per_split vertices (256 with one tile); a tap's list of L vertices is cut into slabs of
+# ceil16(ceil(L / splits)).  table = 'eng': the engineered lists of _w3_table.
+WGRAD3 = [
+    # ---- dense 1x1 layers (F = 1, no table)
+    _w('w3x_dense_floor', 8192, 8192, 128, 1, 256, 'dense'),                          # one tile, 32 full slabs
+    _w('w3x_dense_m8193', 8193, 8193, 128, 1, 256, 'dense'),                          # a 33rd slab of one vertex
+    _w('w3x_dense_m8208', 8208, 8208, 128, 1, 256, 'dense'),                          # last slab 16: one full step
+    _w('w3x_dense_m8209', 8209, 8209, 128, 1, 256, 'dense'),                          # 17: two steps, the second of one row
+    _w('w3x_dense_m8225', 8225, 8225, 128, 1, 256, 'dense'),                          # 33: three steps
+    _w('w3x_dense_c132_n260', 8192, 8192, 132, 1, 260, 'dense'),                      # 4 channels / 4 columns in the second blocks
+    _w('w3x_dense_c260_n516', 8192, 8192, 260, 1, 516, 'dense'),                      # 3 x 3 tiles
+    _w('w3x_dense_views', 8192, 8192 + 53, 128, 1, 256, 'dense', a_off=4, a_ld=140, dy_off=8, dy_ld=268),
+    _w('w3x_dense_view_odd', 8192, 8192, 128, 1, 256, 'dense', a_off=1, a_ld=140),    # not 16-byte aligned: the fp32 kernel
+    # ---- tap mode (a table and its lists)
+    _w('w3x_tap_floor', 8192, 8192, 128, 15, 256, taps=True),
+    _w('w3x_tap_f2', 8192, 8192, 128, 2, 256, taps=True),
+    _w('w3x_tap_c208', 8192, 8192, 208, 15, 256, taps=True),                          # an 80-wide last channel block
+    _w('w3x_tap_c324', 8192, 8192, 324, 15, 256, taps=True),                          # 68-wide (the model's bcn2_)
+    _w('w3x_tap_c132', 8192, 8192, 132, 15, 256, taps=True),                          # fails the tap rule: the fp32 kernel
+    _w('w3x_tap_n260', 8192, 8192, 128, 15, 260, taps=True),
+    _w('w3x_tap_views', 8192, 8192 + 53, 128, 15, 256, taps=True, a_off=4, a_ld=140, dy_off=8, dy_ld=268),
+    _w('w3x_tap_lists', 8192, 8192, 128, 8, 256, 'eng', taps=True),
+]
+
+
 def _gi(family, bm, bn, threads, avec, f_lds, compact, splits, guard_sets, col_share, col_rows, tile_tables, epi_fast, finish,
         tiles_m, tiles_n, grid):
     return dict(family=family, bm=bm, bn=bn, threads=threads, avec=avec, f_lds=f_lds, compact=compact, splits=splits,
@@ -266,6 +296,42 @@ EXPECT_WGRAD = {
     'w_view_odd': _wi(0, 64, 0, 0, 256, 0, 5, 1, 1, 5, 16, 64),
 }
 
+# EXPECT_WGRAD3: as EXPECT_WGRAD, for the default mode with operand magnitudes (scales=True).  wgrad3_expect gives the entry of
+# another selection.
+EXPECT_WGRAD3 = {
+    'w3x_dense_floor': _wi(2, 256, 1, 0, 512, 0, 1, 1, 2, 1, 32, 256),
+    'w3x_dense_m8193': _wi(2, 256, 1, 0, 512, 0, 1, 1, 2, 1, 33, 256),
+    'w3x_dense_m8208': _wi(2, 256, 1, 0, 512, 0, 1, 1, 2, 1, 33, 256),
+    'w3x_dense_m8209': _wi(2, 256, 1, 0, 512, 0, 1, 1, 2, 1, 33, 256),
+    'w3x_dense_m8225': _wi(2, 256, 1, 0, 512, 0, 1, 1, 2, 1, 33, 256),
+    'w3x_dense_c132_n260': _wi(2, 256, 1, 0, 512, 0, 2, 2, 2, 4, 32, 256),
+    'w3x_dense_c260_n516': _wi(2, 256, 1, 0, 512, 0, 3, 3, 2, 9, 27, 304),
+    'w3x_dense_views': _wi(2, 256, 1, 0, 512, 0, 1, 1, 2, 1, 32, 256),
+    'w3x_dense_view_odd': _wi(0, 128, 0, 0, 256, 0, 1, 2, 1, 2, 128, 64),
+    'w3x_tap_floor': _wi(2, 256, 1, 1, 512, 0, 15, 1, 2, 15, 8, 1024),
+    'w3x_tap_f2': _wi(2, 256, 1, 1, 512, 0, 2, 1, 2, 2, 8, 1024),
+    'w3x_tap_c208': _wi(2, 256, 1, 1, 512, 0, 30, 1, 2, 30, 8, 1024),
+    'w3x_tap_c324': _wi(2, 256, 1, 1, 512, 0, 45, 1, 2, 45, 8, 1024),
+    'w3x_tap_c132': _wi(0, 128, 1, 0, 512, 1, 16, 2, 1, 32, 16, 512),
+    'w3x_tap_n260': _wi(2, 256, 1, 1, 512, 0, 15, 2, 2, 30, 8, 1024),
+    'w3x_tap_views': _wi(2, 256, 1, 1, 512, 0, 15, 1, 2, 15, 8, 1024),
+    'w3x_tap_lists': _wi(2, 256, 1, 1, 512, 0, 8, 1, 2, 8, 8, 1024),
+}
+
+
+def wgrad3_expect(name, math='', scales=True):
+    """The hpl_wgrad_info a WGRAD3 case must report under HPL_MATH = math, with (scales=True) or without operand magnitudes:
+    the pinned entry with the family the selection leaves -- bf16 triples without magnitudes or under bf16x3.  None: under
+    HPL_MATH=f32 a split-operand case stays on the fp32 kernel (family FP32, BN 128; its cut is that kernel's own)."""
+    want = EXPECT_WGRAD3[name]
+    if want['family'] == FP32:
+        return want
+    if math == 'f32':
+        return None
+    if math == 'bf16x3' or scales is False:
+        return dict(want, family=TRIPLES)
+    return want
+
 
 # ------------------------------------------------------------------------------------------ operands
 def _rand(shape, gen, device, fill):
@@ -285,8 +351,9 @@ def _view(rows, cols, off, ld, gen, device, fill, pad_value=None):
 
 def _table(case, gen, device, fill, density=0.7):
     F, M, rows = case['F'], case['M'], case['rows']
-    if case['table'] != 'rand':
+    if case['table'] in ('dense', 'reg'):
         return None
+    assert case['table'] == 'rand' or not fill           # ('eng': filled by exact_wgrad_operands alone)
     if not fill:
         return torch.empty((F, M), dtype=torch.int32, device=device)
     nbr = torch.randint(0, rows, (F, M), generator=gen, dtype=torch.int32)
@@ -375,3 +442,160 @@ def wgrad_operands(case, device, fill=True):
             kw['taps'] = (torch.empty(F * M, dtype=torch.int32, device=device), torch.empty(F * M, dtype=torch.int32, device=device),
                           torch.empty(F + 1, dtype=torch.int32, device=device))
     return (A, nbr, M, C, F, dY, N), kw
+
+
+# ------------------------------------------------------------------------------------------ exact operands (WGRAD3)
+# Integer-valued operands whose weight gradient has one right value in every form and family:
+#   * a power-of-two scale is exact, and an integer below 2^22 is exactly an fp16 pair once the largest magnitude of its matrix
+#     sits in the top binade (14 + 7 bits below the scaled unit 2^-7 ... fp16's 11 + 11), and exactly a bf16 triple (3 x 8 bits);
+#   * the kernel keeps hi*hi, hi*lo, lo*hi of pairs and the products with i + j <= 2 of triples: with one operand full width and
+#     the other in its first plane alone, nothing that is dropped is non-zero;
+#   * every partial sum is an integer of the common unit below 2^24, so fp32 accumulation is exact in any order.
+# The last point is the precondition abs_product_max checks: (|X|^T |dY|).max() < EXACT_LIMIT.  The classes stay below
+# 0.75 * 2^24 where a column has more than one term, so that the partial sums of a single plane (|hi| <= |x| (1 + 2^-8)) stay
+# below 2^24 too; a lone term 4 * (2^22 - 1) is one exact product per plane.
+EXACT_LIMIT = 1 << 24
+CLASSES = ('small', 'planes_a', 'planes_dy', 'ramp')
+_POW2_PATTERNS = ((4,), (2, 1), (1, 1, 1), (1, 1, 1))     # magnitudes of the non-zero entries of one column: sum <= 3, or 4 alone
+PAD = 1234567.5                                           # what lies beside a view: reading it ruins a result
+
+
+def _w3_table(case, gen):
+    """The [F, M] table of a WGRAD3 case (None: dense).  Every tap reads distinct rows, so that a channel's magnitudes sum over
+    a tap at most once each.  'rand': tap 0 is every vertex (reading row 0 .. M - 1), tap 3 is empty, the others a random half.
+    'eng' (F = 8): every vertex / none / one / exactly 16 / 17 / 40 (fewer than 8 slabs x 16: trailing slabs are empty) / a
+    random half / vertex M - 1 alone, reading the last row of A."""
+    F, M, rows = case['F'], case['M'], case['rows']
+    if case['table'] == 'dense':
+        return None
+    nbr = torch.full((F, M), -1, dtype=torch.int32)
+    nbr[0] = torch.arange(M, dtype=torch.int32)
+    for f in range(1, F):
+        src = torch.randperm(rows, generator=gen)[:M].to(torch.int32)
+        if case['table'] == 'eng':
+            count = {1: 0, 2: 1, 3: 16, 4: 17, 5: 40, 6: None, 7: 0}[f]
+        else:
+            count = 0 if f == 3 else None
+        if count is None:
+            keep = torch.rand(M, generator=gen) < 0.5
+        else:
+            keep = torch.zeros(M, dtype=torch.bool)
+            keep[torch.randperm(M, generator=gen)[:count]] = True
+        nbr[f] = torch.where(keep, src, torch.full_like(src, -1))
+    if case['table'] == 'eng':
+        nbr[7, M - 1] = rows - 1
+    return nbr
+
+
+def _w3_marks(case, nbr):
+    """[(tap, vertex)] the sparse classes place their non-zeros at: the first and last vertex of every slab of every tap's list
+    (without tap mode: of the vertex range, which tap 0 reads whole), every position 0 .. 15 of a 16-vertex stage (tap 0), vertex 0 and
+    vertex M - 1."""
+    M, want = case['M'], EXPECT_WGRAD3[case['name']]
+    marks = []
+    for f in range(case['F'] if want['tap'] else 1):
+        present = torch.nonzero(nbr[f] >= 0)[:, 0] if want['tap'] else torch.arange(M)
+        L = present.numel()
+        if L == 0:
+            continue
+        per = (-(-L // want['splits']) + 15) // 16 * 16 if want['tap'] else want['m_per_split']
+        slabs = -(-L // per)
+        pos = [0, L - 1]
+        for s in range(slabs):
+            pos += [s * per, min(L, (s + 1) * per) - 1]
+        if f == 0:
+            pos += [(i % slabs) * per + 16 * (i % 3) + i for i in range(16)]
+        marks += [(f, int(present[j])) for j in dict.fromkeys(pos) if j < L]
+    return marks
+
+
+def _sparse_pow2(shape, lines_axis, targets, gen):
+    """A zero matrix with, on every line (column of dY, channel of A: lines_axis = 1), the entries of one of _POW2_PATTERNS with
+    random signs at consecutive rows of `targets` (cyclic: every target is used when the lines offer enough slots)."""
+    X = torch.zeros(shape, dtype=torch.float32)
+    n_lines, t = shape[lines_axis], 0
+    assert len(targets) >= 3
+    sign = torch.randint(0, 2, (n_lines, 3), generator=gen) * 2 - 1
+    for n in range(n_lines):
+        for k, mag in enumerate(_POW2_PATTERNS[n % len(_POW2_PATTERNS)]):
+            X[targets[t % len(targets)], n] = float(mag * sign[n, k])
+            t += 1
+    assert t >= len(targets), 'more marked vertices (%d) than slots (%d)' % (len(targets), t)
+    return X
+
+
+def _full_width(shape, bits, gen):
+    """Integers uniform in (-2^bits, 2^bits), with entry [0, 0] = -(2^bits - 1): the largest magnitude, and an odd one."""
+    X = torch.randint(-(1 << bits) + 1, 1 << bits, shape, generator=gen).float()
+    X[0, 0] = -float((1 << bits) - 1)
+    return X
+
+
+def _as_view(X, off, ld, device):
+    """X on the device as the column view [off, off + cols) of a buffer with row stride ld (None: contiguous) filled with PAD."""
+    rows, cols = X.shape
+    if ld is None or (ld == cols and off == 0):
+        return X.to(device)
+    buf = torch.full((rows, ld), PAD, dtype=torch.float32)
+    buf[:, off:off + cols] = X
+    return buf.to(device)[:, off:off + cols]
+
+
+def exact_wgrad_operands(case, cls, device, bits=22):
+    """Operands of ops.wgrad_raw / ops.wgrad_launch_info for a WGRAD3 case in class cls -> (args, kwargs); the tap lists are built
+    on a GPU only (the query and the precondition need none).  bits: the width of the full-width operand of the planes_ classes.
+      small      A, dY dense integers in [-15, 15]: every vertex, tail and slab contributes
+      planes_a   A integers in (-2^bits, 2^bits); dY zero but for +-2^p (p in 0..2) at the marked vertices (_w3_marks)
+      planes_dy  the mirror image: dY full width, A zero but for +-2^p in the rows the marked vertices read
+      ramp       A integers of 12-13 significant bits, dY in {-1, 0, 1} at 1/8 density"""
+    gen = torch.Generator().manual_seed(sum(map(ord, case['name'])) + 1000 * CLASSES.index(cls))
+    M, rows, C, F, N = case['M'], case['rows'], case['C'], case['F'], case['N']
+    nbr = _w3_table(case, gen)
+    if cls == 'small':
+        A = torch.randint(-15, 16, (rows, C), generator=gen).float()
+        dY = torch.randint(-15, 16, (M, N), generator=gen).float()
+    elif cls == 'ramp':
+        A = torch.randint(1 << 11, 1 << 13, (rows, C), generator=gen).float() * (torch.randint(0, 2, (rows, C), generator=gen) * 2 - 1)
+        dY = torch.randint(-1, 2, (M, N), generator=gen).float() * (torch.rand((M, N), generator=gen) < 0.1875)     # (2/3 non-zero)
+    elif cls == 'planes_a':
+        A = _full_width((rows, C), bits, gen)
+        dY = _sparse_pow2((M, N), 1, list(dict.fromkeys(m for _, m in _w3_marks(case, nbr))), gen)
+    elif cls == 'planes_dy':
+        marks = _w3_marks(case, nbr)
+        A = _sparse_pow2((rows, C), 1, list(dict.fromkeys(m if nbr is None else int(nbr[f, m]) for f, m in marks)), gen)
+        dY = _full_width((M, N), bits, gen)
+    else:
+        raise ValueError(cls)
+    A, dY = _as_view(A, case['a_off'], case['a_ld'], device), _as_view(dY, case['dy_off'], case['dy_ld'], device)
+    nbr = None if nbr is None else nbr.to(device)
+    kw = dict(want_bias=case['bias'])
+    if case['taps'] and A.is_cuda:
+        from hplflownet_amd import ops
+        kw['taps'] = ops.tap_lists(nbr)
+    return (A, nbr, M, C, F, dY, N), kw
+
+
+def wgrad_ref64(A, nbr, M, C, F, dY, N):
+    """-> (dW, S) [F*C, N] in dtype float64 on a GPU: the weight gradient restated with index_select + matmul, and the sum of the
+    magnitudes of its terms, (|X|^T |dY|).  On the CPU float32 serves: sums of non-negative integers are exact there until they
+    reach 2^24 and never fall below it afterwards, which is all the precondition asks."""
+    dt = torch.float64 if A.is_cuda else torch.float32
+    Az = torch.cat([A.to(dt), torch.zeros((1, C), dtype=dt, device=A.device)])
+    d = dY.to(dt)
+    dW = torch.empty((F * C, N), dtype=dt, device=A.device)
+    S = torch.empty_like(dW)
+    for f in range(F):
+        idx = torch.arange(M, device=A.device) if nbr is None else nbr[f].long()
+        # (only vertices with something on both sides: the sparse classes leave a few hundred)
+        live = torch.nonzero((idx >= 0) & d.ne(0).any(1))[:, 0]
+        X = Az.index_select(0, idx[live])
+        use = X.ne(0).any(1)
+        X, D = X[use], d[live[use]]
+        dW[f * C:(f + 1) * C] = X.t() @ D
+        S[f * C:(f + 1) * C] = X.abs().t() @ D.abs()
+    return dW, S
+
+
+def abs_product_max(args):
+    """(|X|^T |dY|).max() of a weight-gradient operand set: below EXACT_LIMIT, every fp32 partial sum is exact."""
+    return float(wgrad_ref64(*args)[1].max())

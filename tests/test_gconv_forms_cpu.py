@@ -24,7 +24,7 @@ def _wgrad_info(case):
 
 
 def test_tables_are_consistent():
-    for cases, expect in ((G.FORWARD, G.EXPECT_FORWARD), (G.WGRAD, G.EXPECT_WGRAD)):
+    for cases, expect in ((G.FORWARD, G.EXPECT_FORWARD), (G.WGRAD, G.EXPECT_WGRAD), (G.WGRAD3, G.EXPECT_WGRAD3)):
         names = [c['name'] for c in cases]
         assert len(set(names)) == len(names)
         assert set(names) == set(expect)
@@ -129,6 +129,107 @@ def test_every_required_wgrad_form_is_reached():
         feats.append(f)
     for form in REQUIRED_WGRAD:
         assert any(all(k in f and f[k] == v for k, v in form.items()) for f in feats), 'no WGRAD case reaches %r' % (form,)
+
+
+def _wgrad3_info(case, scales):
+    args, kw = G.wgrad_operands(case, 'cpu', fill=False)
+    return ops.wgrad_launch_info(*args, scales=scales, **kw)
+
+
+@pytest.mark.parametrize('scales', [True, False], ids=['scales', 'noscales'])
+@pytest.mark.parametrize('case', G.WGRAD3, ids=[c['name'] for c in G.WGRAD3])
+def test_wgrad3_case_takes_its_form(case, scales):
+    """The pinned entry with magnitudes in the default mode; bf16 triples without them or under HPL_MATH=bf16x3; the fp32
+    kernel under HPL_MATH=f32, and in every mode for the two cases that must stay on it."""
+    want = G.wgrad3_expect(case['name'], MATH, scales)
+    got = _wgrad3_info(case, scales)
+    if want is None:
+        assert MATH == 'f32' and got['family'] == G.FP32 and got['bn'] == 128
+        return
+    assert got == want
+    if MATH == '' and scales:
+        assert got == G.EXPECT_WGRAD3[case['name']]
+    if MATH == '' and G.EXPECT_WGRAD3[case['name']]['family'] != G.FP32:
+        assert got['family'] == (G.PAIRS if scales else G.TRIPLES)
+
+
+def test_wgrad3_query_with_the_callers_magnitudes():
+    """A pair of float32 [1] tensors selects as measured magnitudes do; anything else is refused."""
+    import torch
+    case = G.WGRAD3[0]
+    args, kw = G.wgrad_operands(case, 'cpu', fill=False)
+    one = torch.ones(1)
+    assert ops.wgrad_launch_info(*args, scales=(one, one), **kw) == ops.wgrad_launch_info(*args, **kw)
+    with pytest.raises(_lib.HplError, match='scales'):
+        ops.wgrad_launch_info(*args, scales=(one, torch.ones(1, dtype=torch.float64)), **kw)
+
+
+# The forms of the split-operand weight gradient the table must reach, written out.  Features (_w3_features): tap, F, the
+# vertices of the last dense slab (M - (splits - 1) * m_per_split), the widths of the last channel and column blocks
+# (c_tail = C % 128, n_tail = N % 256; 0: full), tiles_k / tiles_n, view (operands as column views), more_rows (rows of A past
+# M), lists ('eng': the engineered lists), wgrad3 (the default mode hands off).
+REQUIRED_WGRAD3 = (
+    # dense: the floor, and a last slab of 1 / 16 / 17 / 33 vertices = 1 / 1 / 2 / 3 steps
+    [dict(wgrad3=True, tap=0, M=8192, C=128, N=256, tiles=1, splits=32, m_per_split=256, last_slab=256, view=False)] +
+    [dict(wgrad3=True, tap=0, tiles=1, m_per_split=256, splits=33, last_slab=n) for n in (1, 16, 17, 33)] +
+    # dense: 4 channels / 4 columns in the second blocks; 3 x 3 tiles; column views with rows of A past M
+    [dict(wgrad3=True, tap=0, c_tail=4, n_tail=4, tiles_k=2, tiles_n=2), dict(wgrad3=True, tap=0, tiles_k=3, tiles_n=3),
+     dict(wgrad3=True, tap=0, view=True, more_rows=True)] +
+    # a view at an odd offset stays on the fp32 kernel
+    [dict(wgrad3=False, tap=0, table='dense', view=True, vec=0, M=8192, C=128, N=256)] +
+    # tap mode: the floor, F = 2, an 80- and a 68-wide last channel block, 4 columns in a second block, views
+    [dict(wgrad3=True, tap=1, M=8192, C=128, F=15, N=256, view=False), dict(wgrad3=True, tap=1, F=2),
+     dict(wgrad3=True, tap=1, c_tail=80), dict(wgrad3=True, tap=1, C=324, c_tail=68), dict(wgrad3=True, tap=1, n_tail=4, tiles_n=2),
+     dict(wgrad3=True, tap=1, view=True, more_rows=True)] +
+    # C = 132 with lists fails the tap rule and stays on the fp32 kernel
+    [dict(wgrad3=False, taps=True, tap=0, C=132, M=8192, N=256)] +
+    # the engineered lists
+    [dict(wgrad3=True, tap=1, F=8, table='eng')]
+)
+
+
+def _w3_features(c):
+    want = G.EXPECT_WGRAD3[c['name']]
+    f = dict(want)
+    f.update(M=c['M'], C=c['C'], F=c['F'], N=c['N'], table=c['table'], taps=c['taps'], wgrad3=want['family'] != G.FP32,
+             c_tail=c['C'] % 128, n_tail=c['N'] % 256, view=bool(c['a_off'] or c['dy_off'] or c['a_ld'] or c['dy_ld']),
+             more_rows=c['rows'] > c['M'])
+    if not want['tap']:
+        f['last_slab'] = c['M'] - (want['splits'] - 1) * want['m_per_split']
+    return f
+
+
+def test_every_required_wgrad3_form_is_reached_in_each_family():
+    """Every form above is some case's pinned entry (pinned against the query by test_wgrad3_case_takes_its_form), and that case
+    takes PAIRS with magnitudes and TRIPLES without in the default mode (there the query itself is asked again)."""
+    for form in REQUIRED_WGRAD3:
+        hits = [c for c in G.WGRAD3 if all(k in f and f[k] == v for f in [_w3_features(c)] for k, v in form.items())]
+        assert hits, 'no WGRAD3 case reaches %r' % (form,)
+        if form['wgrad3'] and MATH == '':
+            assert any(_wgrad3_info(c, True)['family'] == G.PAIRS and _wgrad3_info(c, False)['family'] == G.TRIPLES for c in hits)
+        if not form['wgrad3']:
+            assert all(_wgrad3_info(c, s)['family'] == G.FP32 for c in hits for s in (True, False))
+
+
+@pytest.mark.parametrize('cls', G.CLASSES)
+@pytest.mark.parametrize('case', G.WGRAD3, ids=[c['name'] for c in G.WGRAD3])
+def test_exact_operands_keep_every_partial_sum_exact(case, cls):
+    """The property of the inputs that makes a bit-for-bit comparison legitimate: (|X|^T |dY|).max() < 2^24 in the common unit.
+    Also: integer values, the classes' shapes (a full-width operand has its largest magnitude in the top binade)."""
+    import torch
+    args, _ = G.exact_wgrad_operands(case, cls, 'cpu')
+    A, nbr, M, C, F, dY, N = args
+    assert G.abs_product_max(args) < G.EXACT_LIMIT
+    assert torch.equal(A, A.round()) and torch.equal(dY, dY.round())
+    if cls == 'planes_a':
+        assert (1 << 21) <= float(A.abs().max()) < (1 << 22) and int((dY != 0).sum(0).max()) <= 4 and float(dY.abs().max()) == 4
+    if cls == 'planes_dy':
+        assert (1 << 21) <= float(dY.abs().max()) < (1 << 22) and int((A != 0).sum(0).max()) <= 4 and float(A.abs().max()) == 4
+    if nbr is not None:                                     # the table reads row 0 and the last row of A somewhere
+        assert int(nbr.min()) == -1 and bool((nbr == 0).any()) and int(nbr.max()) < A.shape[0]
+        if case['table'] == 'eng':
+            assert [int((nbr[f] >= 0).sum()) for f in (0, 1, 2, 3, 4, 5, 7)] == [M, 0, 1, 16, 17, 40, 1]
+            assert int(nbr[7, M - 1]) == A.shape[0] - 1
 
 
 def test_queries_refuse_what_the_launch_refuses():

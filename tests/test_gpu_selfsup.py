@@ -342,12 +342,26 @@ def test_trainer_step_is_the_hand_written_step():
         flow.backward(dflow.t()[None])
         h.opt.step()
         return _params(h)
-    h1, h2 = by_hand(), by_hand()
-    spread = max(float((a - b).abs().max()) for a, b in zip(h1, h2))
-    diff = max(float((a - b).abs().max()) for a, b in zip(after, h1))
-    print('hand-written step twice: %.3g apart; the trainer against it: %.3g' % (spread, diff))
-    # (the backward's scatter kernels add with atomics: two runs of ONE program need not agree in the last bits.  Measured on an
-    # MI355X: the hand-written step twice 3.38e-07 apart, the trainer's step 1.49e-08 from it)
+
+    def by_trainer():
+        t = engine.Trainer('HPLFlowNetShallow', DEV, init='hash', loss='selfsup')
+        t.train_step(pc1, pc2, nan_sf, t._single_lattice(pc1, pc2))
+        return _params(t)
+
+    def apart(x, y):
+        return max(float((a - b).abs().max()) for a, b in zip(x, y))
+    # The backward's scatter kernels add with atomics: two runs of ONE program need not agree in the last bits, and Adam's first
+    # step (lr * g / (|g| + eps)) turns a last-bit change of a gradient near eps into a visible change of its parameter, so a run
+    # falls into one of a few modes.  Measured on an MI355X over 8 hand-written and 4 trainer steps: hand-written pairs 1.7e-08
+    # to 4.2e-07 apart, trainer against hand-written 1.5e-08 to 7.6e-07, both in clusters (2e-08 .. 7e-08 and 3.4e-07 .. 7.6e-07).
+    # One sample of the spread against one sample of the distance is therefore a coin: 4 runs of each give 6 samples of the
+    # spread, and the trainer's step is the hand-written one when SOME run of it is within that spread of SOME hand-written run (a
+    # step that computes something else is lr-sized, 1e-4, away from every one of them).
+    hands = [by_hand() for _ in range(4)]
+    trained = [after] + [by_trainer() for _ in range(3)]
+    spread = max(apart(hands[i], hands[j]) for i in range(4) for j in range(i))
+    diff = min(apart(t, h) for t in trained for h in hands)
+    print('hand-written steps: up to %.3g apart; the trainer\'s nearest to one of them: %.3g' % (spread, diff))
     if spread == 0.0:
         assert diff == 0.0
     else:

@@ -1,8 +1,11 @@
-"""The split-operand weight gradient (csrc/wgrad3.hip: both fp32 operands carried as three bf16 terms on the bf16 matrix
-pipe, MFMA fragments fetched with the LDS transpose read) against float64 and against the fp32-MFMA kernel
-(HPL_WGRAD3=0 in a second interpreter).  Pinned here: its error against the exact result is of the fp32 rounding class on
-tap-list stencils and dense 1x1 layers, including the tails (channels past the last 128-block, columns past the last
-256-block, slabs that end inside a 16-vertex stage, taps with empty lists) and the bias gradient of the same call."""
+"""The split-operand weight gradient (csrc/wgrad3.hip: both fp32 operands split while they are staged, MFMA fragments fetched
+with the LDS transpose read) against float64 and against the fp32-MFMA kernel (HPL_WGRAD3=0 in a second interpreter).  Every
+case here is handed its operands' magnitudes by ops.wgrad_raw, so what runs is what ops.wgrad_launch_info reports: scaled fp16
+pairs on the fp16 matrix pipe in the default mode, three bf16 terms under HPL_MATH=bf16x3 (test_cases_take_the_mode_s_family).
+Pinned here: its error against the exact result is of the fp32 rounding class on tap-list stencils and dense 1x1 layers,
+including the tails (channels past the last 128-block, columns past the last 256-block, slabs that end inside a 16-vertex
+stage, taps with empty lists) and the bias gradient of the same call.  tests/test_gpu_wgrad3_exact.py holds the same kernel
+bit for bit on operands whose arithmetic is exact."""
 import os
 import subprocess
 import sys
@@ -45,6 +48,20 @@ CASES = [
     (9001, 512, 1, 512, 1.0, None),           # dense, odd vertex count
     (8192, 132, 1, 256, 1.0, None),           # dense, 4 channels in the second block
 ]
+
+
+def test_cases_take_the_mode_s_family():
+    """What the query reports for the cases of this file: fp16 pairs by default, bf16 triples under HPL_MATH=bf16x3 (and the
+    fp32 kernel when HPL_MATH=f32 or HPL_WGRAD3=0 keep the hand-off away)."""
+    from hplflownet_amd import ops
+    math = os.environ.get('HPL_MATH', '')
+    want = 0 if (math == 'f32' or os.environ.get('HPL_WGRAD3', '1') == '0') else (3 if math == 'bf16x3' else 2)
+    for M, C, F, N, _density, _empty in CASES:
+        rows_a = M if F == 1 else M + 53
+        A, dY = torch.empty(rows_a, C, device=DEV), torch.empty(M, N, device=DEV)
+        nbr = torch.empty((F, M), dtype=torch.int32, device=DEV) if F > 1 else None
+        taps = tuple(torch.empty(n, dtype=torch.int32, device=DEV) for n in (F * M, F * M, F + 1)) if F > 1 else None
+        assert ops.wgrad_launch_info(A, nbr, M, C, F, dY, N, taps=taps, want_bias=True)['family'] == want, (M, C, F, N)
 
 
 def _run_case(M, C, F, N, density, empty_tap):
