@@ -6,6 +6,7 @@ Public surface (mirrors the reference's operator interface for the path):
     HPLFlowNet, HPLFlowNetShallow, DeviceLattice, DenseFlow      (callers; flownet.py)
     rigid_refine                                                 (rigid motion from flow; flownet.py, ops.rigid_fit)
     icp_register                                                 (rigid registration of a cloud pair; flownet.py, ops.icp)
+    estimate_normals                                             (surface normals of clouds; flownet.py, ops.normals)
     segment_motion                                               (moving objects from flow; flownet.py, ops.motion_segment)
     selfsup_loss                                                 (Chamfer + smoothness loss; flownet.py, ops.selfsup_loss)
     remove_ground                                                (fitted-plane ground removal; flownet.py, ops.ground_fit)
@@ -15,8 +16,8 @@ The arithmetic lives in libhplbcl.so (csrc/*.hip, C ABI in include/hpl_bcl.h).
 """
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, Conv2dReLU, Conv3dReLU,  # noqa: F401
                   sparse_sum)
-from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, frames_from_ft3d, frames_from_kitti,  # noqa: F401
-                      icp_register, remove_ground, rigid_refine, segment_motion, selfsup_loss, voxel_downsample)
+from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, estimate_normals, frames_from_ft3d,  # noqa: F401
+                      frames_from_kitti, icp_register, remove_ground, rigid_refine, segment_motion, selfsup_loss, voxel_downsample)
 from .lattice import GenerateDataUnsymmetric, to_reference_format  # noqa: F401
 
 __version__ = '0.1.0'

@@ -245,6 +245,13 @@ _SIGNATURES = {
     'hpl_icp_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, c_i64]),
     'hpl_icp': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
                                ctypes.c_int, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'hpl_normals_workspace_bytes': (c_i64, [ctypes.c_int, c_i64]),
+    'hpl_normals': (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.POINTER(c_i64), ctypes.c_int, c_f32, ctypes.POINTER(c_f32), c_vp,
+                                   c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'hpl_icp_plane_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, c_i64]),
+    'hpl_icp_plane': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, ctypes.c_int, ctypes.POINTER(c_i64),
+                                     ctypes.POINTER(c_i64), ctypes.c_int, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_i64, c_vp]),
     'hpl_plan_create': (c_vp, [ctypes.POINTER(Op), ctypes.c_int, ctypes.POINTER(Buf), ctypes.c_int,
                                ctypes.POINTER(Weight), ctypes.c_int, ctypes.POINTER(c_vp), ctypes.c_int]),
     'hpl_plan_destroy': (None, [c_vp]),

@@ -354,14 +354,18 @@ class Trainer(object):
                 raise HplError('validate: segment applies to rigid')
             segment = segment_options(segment)
         if icp is not None:
-            if not isinstance(icp, dict) or set(icp) - {'iters', 'max_dist', 'tau', 'init'} or \
-                    icp.get('init', 'identity') not in ('identity', 'rigid'):
+            if not isinstance(icp, dict) or set(icp) - {'iters', 'max_dist', 'tau', 'init', 'metric', 'normals_k', 'normals_radius'} or \
+                    icp.get('init', 'identity') not in ('identity', 'rigid') or icp.get('metric', 'point') not in ('point', 'plane') or \
+                    (icp.get('metric', 'point') != 'plane' and ('normals_k' in icp or 'normals_radius' in icp)):
                 raise HplError('validate: icp takes {\'iters\': T, \'max_dist\': d, \'tau\': tau, \'init\': \'identity\' | '
-                               '\'rigid\'}, got %r' % (icp,))
+                               '\'rigid\', \'metric\': \'point\' | \'plane\'[, \'normals_k\': K, \'normals_radius\': R with '
+                               '\'plane\']}, got %r' % (icp,))
+            icp_plane = {k: icp[k] for k in ('metric', 'normals_k', 'normals_radius') if k in icp and icp.get('metric') == 'plane'}
             icp_init = icp.get('init', 'identity')
             if icp_init == 'rigid' and rigid is None:
                 raise HplError('validate: icp init \'rigid\' starts from the rigid fit: it takes rigid')
             icp = {'iters': int(icp.get('iters', 30)), 'max_dist': float(icp.get('max_dist', 1.0)), 'tau': float(icp.get('tau', 0.3))}
+            icp.update(icp_plane)                # (point-to-plane, DESIGN.md §29: icp_register runs ops.normals on pc2)
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
@@ -777,6 +781,13 @@ def parse_args(argv=None):
     ap.add_argument('--icp-init', default=None, choices=['identity', 'rigid'],
                     help='--baseline icp: start from identity (the papers\' baseline, independent of the model; default) or from '
                          'the fit of --rigid-refine (network + ICP)')
+    ap.add_argument('--icp-metric', default=None, choices=['point', 'plane'],
+                    help='--baseline icp: the residual of a round: point-to-point (default) or point-to-plane on the normals of '
+                         'pc2, estimated on the device behind each forward (DESIGN.md §29)')
+    ap.add_argument('--icp-normals-k', type=int, default=None, metavar='K',
+                    help='--icp-metric plane: neighbours of a normal (3 .. 32, default 16)')
+    ap.add_argument('--icp-normals-radius', type=float, default=None, metavar='R',
+                    help='--icp-metric plane: radius of a normal\'s neighbourhood in metres (finite and > 0, default --icp-max-dist)')
     ap.add_argument('--loss', default='epe3d', choices=['epe3d', 'selfsup'],
                     help='training loss: epe3d against the ground-truth flow (default), or selfsup: Chamfer distance between the '
                          'warped cloud and pc2 plus the smoothness of the flow over the k nearest neighbours -- no flow label is '
@@ -865,10 +876,22 @@ def parse_args(argv=None):
         ap.error('--icp-init applies to --baseline icp')
     if a.icp_init == 'rigid' and not a.rigid_refine:
         ap.error('--icp-init rigid starts from the fit of --rigid-refine')
+    if a.icp_metric is not None and not on:
+        ap.error('--icp-metric applies to --baseline icp')
+    if a.icp_normals_k is not None and (a.icp_metric != 'plane' or not 3 <= a.icp_normals_k <= 32):
+        ap.error('--icp-normals-k takes 3 .. 32 and applies to --icp-metric plane')
+    if a.icp_normals_radius is not None and (a.icp_metric != 'plane' or not 0 < a.icp_normals_radius < float('inf')):
+        ap.error('--icp-normals-radius takes a finite value > 0 and applies to --icp-metric plane')
     a.icp = {'iters': 30 if a.icp_iters is None else a.icp_iters,
              'max_dist': 1.0 if a.icp_max_dist is None else a.icp_max_dist,
              'tau': 0.3 if a.icp_tau is None else a.icp_tau,
              'init': a.icp_init or 'identity'} if on else None
+    if on and a.icp_metric is not None:          # (recorded in the configuration the run prints; the report keys do not change)
+        a.icp['metric'] = a.icp_metric
+        if a.icp_normals_k is not None:
+            a.icp['normals_k'] = a.icp_normals_k
+        if a.icp_normals_radius is not None:
+            a.icp['normals_radius'] = a.icp_normals_radius
     on = a.loss == 'selfsup'
     if on and a.evaluate:
         ap.error('--loss applies to training (--evaluate reports the supervised metrics)')

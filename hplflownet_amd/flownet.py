@@ -22,7 +22,7 @@ from . import _lib, ops
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, NbrTable, _ConvReLU, _conv_of, pointwise_conv,
                   to_channel_first, to_channel_last)
 
-__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine', 'icp_register', 'segment_motion']
+__all__ = ['HPLFlowNet', 'HPLFlowNetShallow', 'DeviceLattice', 'PairBlur', 'DenseFlow', 'rigid_refine', 'icp_register', 'estimate_normals', 'segment_motion']
 
 
 # ----------------------------------------------------------------------------- lattice container
@@ -582,7 +582,7 @@ def load_reference_checkpoint(model, checkpoint, strict=True):
 
 
 # ----------------------------------------------------------------------------- rigid refinement
-def _pair_counts(lat_or_counts, total):
+def _pair_counts(lat_or_counts, total, who='rigid_refine'):
     """Points per pair of a packed cloud of `total` points: from a lattice (a ragged one: its point_counts of cloud 1; an
     equal batch: total / batch) or a sequence of counts."""
     if lat_or_counts is None:
@@ -595,7 +595,7 @@ def _pair_counts(lat_or_counts, total):
     else:
         counts = [int(c) for c in lat_or_counts]
     if sum(counts) != total or any(c < 0 for c in counts):
-        raise _lib.HplError('rigid_refine: the point counts %s do not add up to %d points' % (counts, total))
+        raise _lib.HplError('%s: the point counts %s do not add up to %d points' % (who, counts, total))
     return counts
 
 
@@ -698,7 +698,10 @@ def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
     a packed (3, sum N_b) cloud takes its pairs' counts from lat_or_counts: a ragged forward's lattice (its point_counts),
     a sequence of counts for both clouds, or a pair (counts of pc1, counts of pc2).  B > 1 clouds are packed into one
     (3, sum N_b) tensor first (one copy each).  init: (R (B, 3, 3), t (B, 3)) -- the first entries of a rigid_refine result --
-    or None (identity).  kw: weight (packed, pair-major), iters, max_dist, tau, tol_rot, tol_trans, return_matches of ops.icp.
+    or None (identity).  kw: weight (packed, pair-major), iters, max_dist, tau, tol_rot, tol_trans, return_matches of ops.icp;
+    metric='plane'  with normals (the (3, sum M_b) normals of the packed pc2) or, with normals=None, ONE
+    ops.normals call on pc2 in the same stream: normals_k (16) neighbours within normals_radius (default: max_dist), seen from
+    the origin.
     -> (R (B, 3, 3), t (B, 3), stats (B, 6), flow[, match, dist2]), flow = R p + t - p in the form of pc1: views of one
     [sum N_b, 3] tensor; match and dist2 stay packed."""
     c1 = c2 = None
@@ -726,6 +729,17 @@ def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
     for a, b in zip(n1, n2):
         sp.append(sp[-1] + a)
         dp.append(dp[-1] + b)
+    metric, normals = kw.pop('metric', 'point'), kw.pop('normals', None)
+    normals_k, normals_radius = kw.pop('normals_k', 16), kw.pop('normals_radius', None)
+    if metric == 'plane':
+        # metric='plane' (DESIGN.md §29): normals = the (3, sum M_b) normals of the packed pc2, or None: ops.normals of pc2 on the
+        # same stream, k = normals_k, radius = normals_radius (default: max_dist), seen from the origin
+        if normals is None:
+            normals = ops.normals(dst, k=normals_k, radius=kw.get('max_dist', 1.0) if normals_radius is None else normals_radius,
+                                  prefix=dp)[0]
+        kw.update(metric='plane', dst_normal=normals)
+    elif metric != 'point' or normals is not None:
+        raise _lib.HplError('icp_register: metric = %r (\'point\', or \'plane\' with normals (3, M) or None)' % (metric,))
     res = ops.icp(src, dst, init=init, src_prefix=sp, dst_prefix=dp, **kw)
     fl = res[3]
     if shape is None:
@@ -735,6 +749,36 @@ def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
     else:
         fl = [fl[sp[b]:sp[b + 1]].t().unsqueeze(0) if shape[b] else fl[sp[b]:sp[b + 1]].t() for b in range(len(n1))]
     return res[:3] + (fl,) + res[4:]
+
+
+# ----------------------------------------------------------------------------- surface normals
+def estimate_normals(pc, lat_or_counts=None, k=16, radius=1.0, viewpoint=None):
+    """The surface normals of the cloud(s) pc in ONE ops.normals call.  pc in the forms rigid_refine takes: a
+    (B, 3, N) tensor (or (3, N): one cloud), or a list of B (3, N_b) / (1, 3, N_b) tensors (a ragged batch); a packed
+    (3, sum N_b) cloud takes its clouds' counts from lat_or_counts (a forward's lattice -- a ragged one: the counts of its
+    first clouds --, or a sequence of counts).  B > 1 clouds are packed into one (3, sum N_b) tensor first (one copy).
+    k, radius, viewpoint: of ops.normals (viewpoint: three numbers for every cloud, or B triples; None: the origin).
+    -> (normal, curvature, count): normal in the form of pc -- (B, 3, N), (3, N) or a list of views of one (3, sum N_b)
+    tensor --, curvature and count (B, N) for a (B, 3, N) tensor, else packed (sum N_b,)."""
+    counts = None
+    if torch.is_tensor(pc) and pc.dim() == 2 and lat_or_counts is not None:
+        counts = _pair_counts(lat_or_counts, int(pc.shape[1]), 'estimate_normals')
+    cloud, counts, shape = _packed_cloud(pc, counts, 'estimate_normals', 'pc')
+    if shape is not None and shape is not False and lat_or_counts is not None and \
+            _pair_counts(lat_or_counts, sum(counts), 'estimate_normals') != counts:
+        raise _lib.HplError('estimate_normals: the clouds hold %s points, the lattice or counts say otherwise' % (counts,))
+    prefix = [0]
+    for c in counts:
+        prefix.append(prefix[-1] + c)
+    normal, curvature, count = ops.normals(cloud, k=k, radius=radius, viewpoint=viewpoint, prefix=prefix)
+    B = len(counts)
+    if shape is None:
+        n = counts[0]
+        return normal.view(3, B, n).transpose(0, 1), curvature.view(B, n), count.view(B, n)
+    if shape is False:
+        return normal, curvature, count
+    return ([normal[:, prefix[b]:prefix[b + 1]].unsqueeze(0) if shape[b] else normal[:, prefix[b]:prefix[b + 1]]
+             for b in range(B)], curvature, count)
 
 
 # ----------------------------------------------------------------------------- moving objects

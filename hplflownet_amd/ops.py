@@ -541,7 +541,7 @@ def _icp_scalar(name, v, zero_ok=False):
 
 
 def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_rot=0.0, tol_trans=0.0, src_prefix=None,
-        dst_prefix=None, return_matches=False, out=None):
+        dst_prefix=None, return_matches=False, out=None, metric='point', dst_normal=None):
     """hpl_icp on the current stream: per pair the rigid motion q = R p + t that lays src (3, N) onto dst (3, M)
     by robust point-to-point ICP -- each round matches every moved src point to its exact nearest dst point within max_dist
     (a sorted grid over dst, built once a call), weighs the matches by Geman-McClure of scale tau and solves as ops.rigid_fit
@@ -553,7 +553,14 @@ def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_r
     -> (R (B, 3, 3), t (B, 3), stats (B, 6) = (status, matched share, RMSE of the matches, rotation angle in degrees, |t|,
     rounds run), flow [N, 3] = R p + t - p [, match (N,) int32 into the packed dst or -1, dist2 (N,) float32 or +inf]).
     status 0 (fewer than 3 src points, no dst point, or a round without any match): the motion is the one the failed round
-    started from.  out: a contiguous [N, 3] float32 tensor that takes the flow.  No autograd, no host synchronisation."""
+    started from.  out: a contiguous [N, 3] float32 tensor that takes the flow.  No autograd, no host synchronisation.
+    metric='plane' (hpl_icp_plane) takes dst_normal (3, M) float32 -- ops.normals(dst)[0] --: the round minimises
+    the residuals along the matched points' normals (a match on a zero or non-finite normal takes no part) by a minimum-norm
+    Gauss-Newton step; match, stop, failure, finish and the outputs are the same."""
+    if metric not in ('point', 'plane'):
+        raise _lib.HplError('icp: metric = %r (\'point\' or \'plane\')' % (metric,))
+    if (metric == 'plane') != (dst_normal is not None):
+        raise _lib.HplError('icp: metric \'plane\' takes dst_normal (3, M), metric \'point\' takes none')
     _int_in('icp', 'iters', iters, 0, 64)
     max_dist, tau = _icp_scalar('max_dist', max_dist), _icp_scalar('tau', tau)
     tol_rot, tol_trans = _icp_scalar('tol_rot', tol_rot, True), _icp_scalar('tol_trans', tol_trans, True)
@@ -562,6 +569,10 @@ def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_r
     N, M, dev = src.shape[1], dst.shape[1], src.device
     if dst.device != dev:
         raise _lib.HplError('icp: src is on %s, dst on %s' % (dev, dst.device))
+    if dst_normal is not None:
+        dst_normal, dn_ld = _soa3(dst_normal, 'dst_normal', 'icp')
+        if dst_normal.shape[1] != M or dst_normal.device != dev:
+            raise _lib.HplError('icp: dst_normal must be a (3, %d) float32 tensor on %s' % (M, dev))
     if weight is not None:
         if not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32 or weight.device != dev \
                 or weight.requires_grad:
@@ -599,18 +610,77 @@ def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_r
     else:
         Rt = torch.empty((B, 12), dtype=torch.float32, device=dev)
         stats = torch.empty((B, 6), dtype=torch.float32, device=dev)
-        nbytes = lib.hpl_icp_workspace_bytes(B, N, M)
+        nbytes = (lib.hpl_icp_plane_workspace_bytes if metric == 'plane' else lib.hpl_icp_workspace_bytes)(B, N, M)
         if nbytes < 0:
             raise _lib.HplError('icp: %d pairs of %d and %d points together are outside the limits (64 pairs, N, M < 2^31 / 3)'
                                 % (B, N, M))
         st = stream()
         ws = _workspace('icp', dev, st, nbytes)
-        check(lib.hpl_icp(src.data_ptr(), src_ld, dst.data_ptr(), dst_ld, ptr(weight), ptr(init), B,
-                          (ctypes.c_int64 * (B + 1))(*sp), (ctypes.c_int64 * (B + 1))(*dp), iters, max_dist, tau, tol_rot,
-                          tol_trans, Rt.data_ptr(), stats.data_ptr(), ptr(match), ptr(dist2), out.data_ptr(), ws.data_ptr(),
-                          ws.numel(), st), 'hpl_icp')
+        tail = (ptr(weight), ptr(init), B, (ctypes.c_int64 * (B + 1))(*sp), (ctypes.c_int64 * (B + 1))(*dp), iters, max_dist, tau,
+                tol_rot, tol_trans, Rt.data_ptr(), stats.data_ptr(), ptr(match), ptr(dist2), out.data_ptr(), ws.data_ptr(),
+                ws.numel(), st)
+        if metric == 'plane':
+            check(lib.hpl_icp_plane(src.data_ptr(), src_ld, dst.data_ptr(), dst_ld, dst_normal.data_ptr(), dn_ld, *tail),
+                  'hpl_icp_plane')
+        else:
+            check(lib.hpl_icp(src.data_ptr(), src_ld, dst.data_ptr(), dst_ld, *tail), 'hpl_icp')
     res = (Rt[:, :9].view(B, 3, 3), Rt[:, 9:], stats, out)
     return res + (match, dist2) if return_matches else res
+
+
+# --------------------------------------------------------------------------- surface normals
+def normals(pc, k=16, radius=1.0, viewpoint=None, prefix=None, return_neighbors=False, out=None):
+    """hpl_normals on the current stream: per point of pc (3, N) its k (3 .. 32) nearest points of the same cloud
+    within radius, itself included, exact and ordered by (d2, index) -- a sorted grid over the cloud, built once a call --, and
+    the unit eigenvector of the smallest eigenvalue of their float64 scatter matrix, turned towards the cloud's viewpoint.
+    viewpoint: three numbers for every cloud, B triples, or None (the origin); host values.  prefix (host sequence of B + 1 ints
+    from 0 to N): B <= 64 clouds, every point searching its own cloud.
+    -> (normal (3, N) float32, curvature (N,) float32 = lambda_min / sum lambda, count (N,) int32 <= k [, nbr (N, k) int32 into
+    the packed cloud, then -1, nbr_d2 (N, k) float32, then +inf]).  A point with fewer than 3 neighbours, a degenerate
+    neighbourhood or a non-finite or out-of-range position has the normal (0, 0, 0) and the curvature 0.  out: a (3, N) float32
+    tensor with unit stride along its points (rows may be views of a wider buffer) that takes the normal.  No autograd, no host
+    synchronisation."""
+    _int_in('normals', 'k', k, 3, 32)
+    radius = float(radius)
+    if not (radius > 0 and radius < float('inf')):
+        raise _lib.HplError('normals: radius = %r (finite and > 0)' % (radius,))
+    pc, pc_ld = _soa3(pc, 'pc', 'normals')
+    N, dev = pc.shape[1], pc.device
+    pp = _prefix(prefix, N, 'normals')
+    B = len(pp) - 1
+    view = None
+    if viewpoint is not None:
+        try:
+            v = torch.as_tensor(viewpoint, dtype=torch.float32, device='cpu').reshape(-1).tolist()
+        except (TypeError, ValueError, RuntimeError):
+            v = []
+        if len(v) == 3:
+            v = v * B
+        if len(v) != 3 * B:
+            raise _lib.HplError('normals: viewpoint holds three numbers or %d triples, got %r' % (B, viewpoint))
+        view = (ctypes.c_float * (3 * B))(*v)
+    if out is not None:
+        if not torch.is_tensor(out) or tuple(out.shape) != (3, N) or out.dtype != torch.float32 or out.device != dev or \
+                out.requires_grad or (N > 1 and out.stride(1) != 1) or out.stride(0) < max(N, 1):
+            raise _lib.HplError('normals: out must be a (3, %d) float32 tensor on %s with unit stride along its points' % (N, dev))
+    else:
+        out = torch.empty((3, N), dtype=torch.float32, device=dev)
+    curvature = torch.empty(N, dtype=torch.float32, device=dev)
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    nbr = torch.empty((N, k), dtype=torch.int32, device=dev) if return_neighbors else None
+    nbr_d2 = torch.empty((N, k), dtype=torch.float32, device=dev) if return_neighbors else None
+    if N > 0:
+        lib = _lib.load()
+        nbytes = lib.hpl_normals_workspace_bytes(B, N)
+        if nbytes < 0:
+            raise _lib.HplError('normals: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (B, N))
+        st = stream()
+        ws = _workspace('normals', dev, st, nbytes)
+        check(lib.hpl_normals(pc.data_ptr(), pc_ld, B, (ctypes.c_int64 * (B + 1))(*pp), k, radius, view, out.data_ptr(),
+                              out.stride(0), ptr(curvature), ptr(count), ptr(nbr), ptr(nbr_d2), ws.data_ptr(), ws.numel(), st),
+              'hpl_normals')
+    res = (out, curvature, count)
+    return res + (nbr, nbr_d2) if return_neighbors else res
 
 
 # --------------------------------------------------------------------------- moving objects from flow

@@ -1326,6 +1326,81 @@ int hpl_icp(const float *src, int64_t src_ld, const float *dst, int64_t dst_ld, 
             float tau, float tol_rot, float tol_trans, float *Rt, float *stats, int32_t *match, float *dist2, float *flow,
             void *workspace, int64_t workspace_bytes, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Surface normals of packed ragged clouds (csrc/normals.hip): per point its k nearest neighbours within a radius, exact, on
+ * a sorted grid over the cloud itself, and the principal-component normal of that neighbourhood.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_normals for `batch` clouds of n_total points together, in bytes (monotone in n_total); -1 for a batch
+ * outside 1 .. 64 or a count outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_normals_workspace_bytes(int batch, int64_t n_total);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N).  batch (1 .. 64) clouds: prefix (HOST, batch + 1 ints from 0 to N,
+ * non-decreasing, empty clouds allowed) travels in the kernel arguments.  k 3 .. 32; radius finite and > 0; viewpoint (HOST,
+ * [batch][3] float32, finite) or NULL (the origin for every cloud).
+ * GRID (an accelerator only: the neighbourhood below is defined over all pairs of a cloud; tests/normals_oracle.py restates it
+ * in numpy without a grid): cell_k = floor(x_k * (1 / (1.001 * radius))) in float64 (the product 1.001 * radius, the quotient
+ * and the product with x_k each rounded once).  A point TAKES PART when its three coordinates are finite and
+ * |cell_k| <= 2^18 - 2 for k = x, y, z; a point that does not has count 0, no neighbour and no normal.
+ * DISTANCE d2(i, j) = (dx * dx + dy * dy) + dz * dz in float32 with dx = p_i.x - p_j.x, every operation rounded, no
+ * contraction (the arithmetic of hpl_knn_interp).
+ * NEIGHBOURHOOD N(i) of a point that takes part: the points j of the same cloud that take part with d2(i, j) <=
+ * float32(radius * radius) (the product in float32), i itself included (d2 = 0), ordered by (d2, j) ascending -- equal d2:
+ * the smaller index first --, the first k of them.  count (N) int32 = |N(i)| <= k.  nbr [N][k] int32: the packed indices in
+ * that order, then -1; nbr_d2 [N][k] float32: their d2, then +inf (each of curvature, count, nbr, nbr_d2 may be NULL).
+ * COVARIANCE in float64, in neighbourhood order, every sum from 0: m = (sum p_j) / count; the six sums
+ * C_ab = sum (p_ja - m_a) (p_jb - m_b), a <= b.
+ * EIGENPAIR: cyclic Jacobi (csrc/cloud_common.h, at most 12 sweeps, as hpl_ground_fit) on the symmetric C; lambda_0 ..
+ * lambda_2 are the diagonal afterwards.  The normal is the eigenvector column of the smallest lambda (equal lambdas: the
+ * smaller column), divided once by its length sqrt((n0 n0 + n1 n1) + n2 n2) in float64.
+ * ORIENTATION: s = (n0 (v0 - p0) + n1 (v1 - p1)) + n2 (v2 - p2) in float64, v the cloud's viewpoint and p the point, widened
+ * from float32.  The normal is negated when s < 0; when s == 0, when its first non-zero component is negative.
+ * VALID when count >= 3, the three lambdas are finite and the largest is > 0: normal (3, N) float32 SoA (row stride
+ * normal_ld >= N) = float32(n), a unit vector; curvature (N) float32 = float32(max(lambda_min, 0) / ((lambda_0 + lambda_1) +
+ * lambda_2)), the surface variation.  Otherwise the normal is (0, 0, 0) and the curvature 0.
+ * No floating-point atomic; a point's outputs are the same bits alone, anywhere in a batch and beside other work.
+ * Stream-ordered: keys, one stable radix sort of (key, 16-byte record), one search-and-PCA launch (a lane per sorted record;
+ * the list of the best k kept in registers, instances of 8, 16 and 32 entries); no copy back, no host synchronisation; no
+ * lane or workgroup waits for another; every loop is bounded by a cell's population or log2 N.  The search costs the
+ * population of 27 cells per point: all points in one cell is quadratic.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_normals_workspace_bytes(batch, N).
+ * HPL_EINVAL before any launch (and without a device): batch or k out of range; radius <= 0 or not finite; a non-finite
+ * viewpoint; a prefix that does not start at 0 or decreases; N >= 2^31 / 3; N k >= 2^31 with nbr or nbr_d2 given; a row stride
+ * below N; null pc / normal / prefix / workspace; misaligned arrays; a workspace that is too small or misaligned; an output
+ * that overlaps pc or the workspace.  N == 0 is a no-op. */
+int hpl_normals(const float *pc, int64_t pc_ld, int batch, const int64_t *prefix /* HOST */, int k, float radius,
+                const float *viewpoint /* HOST [batch][3] or NULL */, float *normal, int64_t normal_ld, float *curvature,
+                int32_t *count, int32_t *nbr, float *nbr_d2, void *workspace, int64_t workspace_bytes, hplStream stream);
+
+/* ------------------------------------------------------------------------ *
+ * Point-to-plane ICP (csrc/icp_plane.hip; what it shares with csrc/icp.hip lives in csrc/icp_common.h): hpl_icp with the
+ * residual taken along the matched dst point's normal.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_icp_plane, in bytes (monotone in all three); -1 as hpl_icp_workspace_bytes. */
+int64_t hpl_icp_plane_workspace_bytes(int batch, int64_t n_src, int64_t n_dst);
+/* hpl_icp's arguments, and dst_normal (3, M) float32 SoA (row stride dnormal_ld >= M), e.g. hpl_normals' output for dst.
+ * Everything hpl_icp states holds -- grid, match, weights, stop, failure, finish (which reports EVERY point-to-point match),
+ * Rt, stats, chaining, determinism --; the ROUND differs:
+ * A matched dst point's normal n (widened to float64) is VALID when its three components are finite and not all zero; a match
+ * on an invalid normal has u = 0 in the round.
+ * r = sum_k (y_k - q_k) n_k in float64 (k ascending, from 0); u = w / (s * s), s = 1 + (r * r) * (1 / (tau * tau)).
+ * a = (y - c) x n with c the pair's pivot (its first src point, 0 for a non-finite coordinate); J = (a0, a1, a2, n0, n1, n2).
+ * The 28 sums W = sum u, the 21 upper entries of H = sum (u J_p) J_q (row-major) and g_p = sum (u J_p) r go through
+ * hpl_icp's workgroup order (one LDS tree per 1024 src points, then a fold of the workgroups' partials in 8 strided runs).
+ * SOLVE (float64): cyclic Jacobi on the 6 x 6 H, at most 16 sweeps; lambda = the diagonal, V = the eigenvector columns;
+ * x = - sum over {i: lambda_i > 1e-10 lambda_max} V_i (V_i . g) / lambda_i, the minimum-norm step: a direction the geometry does
+ * not observe (sliding along a single plane) gets no update and does not fail the pair.  (omega, delta) = x;
+ * E = I + sin(theta) / theta K + (1 - cos(theta)) / theta^2 K^2 with K = [omega]x, theta = |omega| (theta < 1e-12: E = I + K);
+ * R' = E R, t' = E (t - c) + c + delta, then ROUNDED TO FLOAT32: iters = T equals T chained calls bit for bit at tol = 0.
+ * FAILURE as hpl_icp: W not > 0, lambda_max not > 0, or a sum or the new motion not finite.
+ * DRIFT: R is a product of one rotation per round, each product rounded to float32 and never re-projected: after T rounds
+ * R^T R differs from I by at most about 6 T 2^-24 per entry.
+ * workspace >= hpl_icp_plane_workspace_bytes(batch, N, M).  HPL_EINVAL as hpl_icp, and for a null dst_normal with M > 0, a
+ * misaligned dst_normal or dnormal_ld < M. */
+int hpl_icp_plane(const float *src, int64_t src_ld, const float *dst, int64_t dst_ld, const float *dst_normal, int64_t dnormal_ld,
+                  const float *weight, const float *init, int batch, const int64_t *src_prefix /* HOST */,
+                  const int64_t *dst_prefix /* HOST */, int iters, float max_dist, float tau, float tol_rot, float tol_trans,
+                  float *Rt, float *stats, int32_t *match, float *dist2, float *flow, void *workspace, int64_t workspace_bytes,
+                  hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--repeats', type=int, default=7)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--metric', default='point', choices=['point', 'plane'],
+                    help='plane: instead of the tables above, point-to-plane (DESIGN.md §29) against point-to-point on a pair whose '
+                         'clouds are sampled independently from the same surfaces: a round, a run to the fixpoint, rounds, error')
     ap.add_argument('--small', action='store_true', help='tiny shapes: a rehearsal of the script, not a measurement')
     a = ap.parse_args()
     from hplflownet_amd import ops
@@ -62,6 +65,30 @@ def main():
     def say(row):
         lines.append(row)
         print(row, flush=True)
+    if a.metric == 'plane':
+        import icp_plane_oracle as Q
+        say('src and dst sampled independently from the same surfaces (tests/icp_plane_oracle.pair), dst moved by the scene\'s motion;')
+        say('normals of dst by ops.normals(k = 16, radius = 1), timed apart; R / t: largest entry off the true motion')
+        for n, calls, warmup in ((one, 50, 10), (big, 3, 2)):
+            src, dst = (t(x) for x in Q.pair(n, 7))
+            out = torch.empty((n, 3), device=dev)
+            nrm = ops.normals(dst, k=16, radius=1.0)[0]
+            med, lo, hi = per_call_us(lambda: ops.normals(dst, k=16, radius=1.0), calls, a.repeats, warmup)
+            say('N = M = %d: ops.normals(dst) %.1f (%.1f .. %.1f)' % (n, med, lo, hi))
+            for metric, kw in (('point', {}), ('plane', dict(metric='plane', dst_normal=nrm))):
+                row = '   %-5s' % metric
+                for iters in (0, 1, 30):
+                    fn = lambda: ops.icp(src, dst, iters=iters, out=out, **kw)       # noqa: E731
+                    med, lo, hi = per_call_us(fn, calls, a.repeats, warmup)
+                    row += '   iters = %2d: %10.1f (%.1f .. %.1f)' % (iters, med, lo, hi)
+                R, tt, stats, _ = fn()
+                row += '   rounds run %2d, R off by %.3g, t by %.3g m' % (
+                    int(stats[0, 5]), float(np.abs(R[0].cpu().numpy() - O.TRUE_R).max()), float(np.abs(tt[0].cpu().numpy() - O.TRUE_T).max()))
+                say(row)
+        if a.out:
+            with open(a.out, 'w') as fd:
+                fd.write('\n'.join(lines) + '\n')
+        return
     for name, counts, calls, warmup in shapes:
         parts = [O.scene(n, 90 + i) for i, n in enumerate(counts)]
         src, dst = t(np.concatenate([x[0] for x in parts], 1)), t(np.concatenate([x[1] for x in parts], 1))
