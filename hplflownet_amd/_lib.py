@@ -234,6 +234,10 @@ _SIGNATURES = {
     'hpl_voxel_downsample': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i64), c_f32,
                                             ctypes.POINTER(c_f32), ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp,
                                             c_vp, c_vp, c_i64, c_vp]),
+    'hpl_fps_resident_capacity': (ctypes.c_int, []),
+    'hpl_fps_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, c_i64, ctypes.c_int]),
+    'hpl_fps': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i32),
+                               c_i64, ctypes.c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'hpl_frames_workspace_bytes': (c_i64, [ctypes.c_int, c_i64]),
     'hpl_frames_from_kitti': (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.POINTER(ctypes.c_int32),
                                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_i64), ctypes.POINTER(c_f32), c_f32,

@@ -447,15 +447,23 @@ class KITTI(_PairFolder):
     GROUND_KEYS = ('up', 'max_tilt_deg', 'hyps', 'tau', 'refine', 'cut')
 
     def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None, ground=None,
-                 voxel=None, voxel_mode='centroid'):
+                 voxel=None, voxel_mode='centroid', fps=None):
         """remove_ground: True -- the reference's rule, a correspondence is dropped when y < -1.4 in both clouds --, False, or
         'plane': the same pair rule on a plane fitted to each cloud on the device (flownet.remove_ground(corr=True, seed=0,
         call=<frame number>, **ground), DESIGN.md §21: a frame's result does not depend on the order of reading).
         voxel (None: off): after the ground removal and before the transform samples its points, the pair is put on a voxel
         grid of that edge on the device (flownet.voxel_downsample(corr=True, voxel=voxel, mode=voxel_mode)):
-        one correspondence per occupied cell of pc1."""
+        one correspondence per occupied cell of pc1.
+        fps (None: off): after the ground removal and the voxel grid and before the transform, the pair is sampled to `fps`
+        correspondences by farthest point sampling on the device (flownet.fps_sample(corr=True, num_points=fps), DESIGN.md §30);
+        a frame of fewer distinct positions keeps that many."""
         from . import _lib, ops
         super(KITTI, self).__init__(transform, device)
+        if fps is not None:
+            if torch.device(device).type != 'cuda':
+                raise _lib.HplError('KITTI: fps samples on the device, got device %s (there is no CPU fallback)' % (device,))
+            ops.fps_args('KITTI: fps', fps, 1)
+        self.fps = fps
         if voxel is not None:
             if torch.device(device).type != 'cuda':
                 raise _lib.HplError('KITTI: voxel downsamples on the device, got device %s (there is no CPU fallback)' % (device,))
@@ -520,6 +528,11 @@ class KITTI(_PairFolder):
             t1, t2 = (torch.from_numpy(np.ascontiguousarray(p[:, :3].T, dtype=np.float32)).to(self.device) for p in (pc1, pc2))
             v1, v2 = voxel_downsample(t1, t2, voxel=self.voxel, mode=self.voxel_mode, corr=True)[:2]
             pc1, pc2 = (np.ascontiguousarray(v[0].t().cpu().numpy()) for v in (v1, v2))
+        if self.fps is not None:
+            from .flownet import fps_sample
+            t1, t2 = (torch.from_numpy(np.ascontiguousarray(p[:, :3].T, dtype=np.float32)).to(self.device) for p in (pc1, pc2))
+            f1, f2 = fps_sample(t1, t2, num_points=self.fps, corr=True)[:2]
+            pc1, pc2 = (np.ascontiguousarray(f[0].t().cpu().numpy()) for f in (f1, f2))
         return pc1, pc2
 
 
@@ -608,12 +621,12 @@ class KITTIRaw(KITTI):
     for the tree process_kitti.py would have written; the keywords are KITTI's."""
 
     def __init__(self, transform, raw_root, calib_dir, remove_ground=True, mapping_file=None, device='cuda', ground=None,
-                 voxel=None, voxel_mode='centroid'):
+                 voxel=None, voxel_mode='centroid', fps=None):
         _need_device('KITTIRaw', device)
         if calib_dir is None or not os.path.isdir(calib_dir):
             raise FileNotFoundError('KITTIRaw: calib_dir %r is not a directory (the back-projection needs every frame\'s P_rect_02)' % (calib_dir,))
         super(KITTIRaw, self).__init__(transform, raw_root, remove_ground=remove_ground, mapping_file=mapping_file, device=device,
-                                       calib_dir=calib_dir, ground=ground, voxel=voxel, voxel_mode=voxel_mode)
+                                       calib_dir=calib_dir, ground=ground, voxel=voxel, voxel_mode=voxel_mode, fps=fps)
         self.P = {nm: read_kitti_P(os.path.join(calib_dir, nm + '.txt')) for nm in (os.path.basename(d) for d in self.samples)}
 
     def _sample_dirs(self, raw_root):

@@ -808,6 +808,10 @@ def parse_args(argv=None):
                          '(flownet.voxel_downsample, DESIGN.md §24); default off')
     ap.add_argument('--voxel-mode', default=None, choices=['centroid', 'nearest'],
                     help='--voxel: a cell becomes the mean of its points (centroid, the default) or the point nearest to it')
+    ap.add_argument('--fps', type=int, default=None, metavar='K',
+                    help='--dataset KITTI: sample every frame to K correspondences (an int >= 1) by farthest point sampling on the '
+                         'device, after the ground removal and --voxel and before the sampling of --points '
+                         '(flownet.fps_sample, DESIGN.md §30); default off')
     ap.add_argument('--ground-tau', type=float, default=None, metavar='TAU',
                     help='--ground plane: inlier distance of the fit in metres (finite and > 0, default 0.1)')
     ap.add_argument('--ground-cut', type=float, default=None, metavar='C',
@@ -929,6 +933,10 @@ def parse_args(argv=None):
         ap.error('--voxel takes a finite value > 0')
     if a.voxel_mode is not None and a.voxel is None:
         ap.error('--voxel-mode applies to --voxel')
+    if a.fps is not None and a.dataset != 'KITTI':
+        ap.error('--fps applies to --dataset KITTI')
+    if a.fps is not None and a.fps < 1:
+        ap.error('--fps takes an int >= 1')
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0
@@ -1051,7 +1059,7 @@ def _real_data(a, tr, dev, rank, world):
         kitti = data_mod.KITTIRaw if a.raw_root is not None else data_mod.KITTI
         val = kitti(process(True), a.raw_root if a.raw_root is not None else a.data_root, device=dev, calib_dir=a.kitti_calib,
                     remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit, voxel=a.voxel,
-                    voxel_mode=a.voxel_mode or 'centroid')
+                    voxel_mode=a.voxel_mode or 'centroid', fps=a.fps)
         train = None
         if a.kitti_calib is None:
             log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')

@@ -963,6 +963,71 @@ def voxel_downsample(pc1, pc2=None, sf=None, voxel=0.1, mode='centroid', corr=Tr
     return res
 
 
+# ----------------------------------------------------------------------------- farthest point sampling
+def fps_sample(pc1, pc2=None, sf=None, num_points=8192, corr=True, start=None, seed=None, return_index=False):
+    """The pair(s) sampled to num_points points a cloud by farthest point sampling, by ONE ops.fps call.  pc1 /
+    pc2 / sf in the forms voxel_downsample takes: (3, N) tensors (one pair), (B, 3, N) tensors, or lists of B (3, N_b) tensors;
+    pc2 and sf may be None.  A cloud of fewer distinct finite positions than num_points yields that many points.
+    corr=True (the clouds of a pair correspond point to point, so they hold as many points): pc1 decides; pc2 and sf ride as
+    attribute channels, so a pair stays a pair and pc2' - pc1' keeps sf' exactly.  At most 64 pairs a call.
+    corr=False: the 2 B clouds -- the pc1 clouds first, then the pc2 clouds -- are each sampled on their own; sf follows pc1.
+    At most 32 pairs a call.
+    start: one index per sampled cloud (its first sample); seed: every sampled cloud's start is drawn on the host from
+    numpy.random.RandomState(seed), in cloud order; neither: every cloud starts at its first finite point.
+    One read-back: the counts.
+    -> (pc1 list of (3, count_b), pc2 list or None, sf list or None, stats (B, 4) int32 -- corr=False with pc2: (2, B, 4) --
+    [, idx list]): return_index appends, per sampled cloud, idx (count_b,) int64 into the cloud, in selection order."""
+    who = 'fps_sample'
+    c1 = _clouds(pc1, who, 'pc1')
+    c2 = _clouds(pc2, who, 'pc2') if pc2 is not None else None
+    fl = _clouds(sf, who, 'sf') if sf is not None else None
+    B = len(c1)
+    if (c2 is not None and len(c2) != B) or (fl is not None and (len(fl) != B or any(f.shape[1] != c.shape[1] for f, c in zip(fl, c1)))):
+        raise _lib.HplError('%s: pc1, pc2 and sf hold as many clouds, and sf as many points as pc1' % who)
+    joint = corr or c2 is None
+    if corr and c2 is not None and any(a.shape[1] != b.shape[1] for a, b in zip(c1, c2)):
+        raise _lib.HplError('%s: corr=True takes clouds that correspond point to point (as many points in pc1 and pc2)' % who)
+    if not 1 <= (B if joint else 2 * B) <= 64:
+        raise _lib.HplError('%s: %d pairs (1 .. %d a call)' % (who, B, 64 if joint else 32))
+    clouds = c1 if joint else c1 + c2
+    ops.fps_args(who, num_points, len(clouds))
+    if start is not None and seed is not None:
+        raise _lib.HplError('%s: start and seed together (give one)' % who)
+    sizes = [int(c.shape[1]) for c in clouds]
+    if seed is not None:
+        import numpy as np
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 32:
+            raise _lib.HplError('%s: seed = %r (an int in 0 .. 2^32 - 1)' % (who, seed))
+        rs = np.random.RandomState(seed)
+        start = [int(rs.randint(0, n)) if n > 0 else 0 for n in sizes]
+    prefix = [0]
+    for n in sizes:
+        prefix.append(prefix[-1] + n)
+    pc = torch.cat(clouds, dim=1)
+    n1 = prefix[B]
+    riders = []
+    if joint and c2 is not None:
+        riders.append(torch.cat(c2, dim=1))
+    if fl is not None:
+        f = torch.cat(fl, dim=1)
+        riders.append(f if joint else torch.cat([f, f.new_zeros((3, prefix[-1] - n1))], dim=1))
+    attrs = torch.cat(riders, dim=0) if riders else None
+    out_pc, out_attrs, idx, _, _, stats = ops.fps(pc, num_points, attrs, start=start, prefix=prefix)
+    K = stats[:, 0].cpu().tolist()                                              # the one read-back
+    m = num_points
+    cols = [out_pc[:, b * m:b * m + K[b]] for b in range(len(clouds))]
+    o1 = cols[:B]
+    o2 = None if c2 is None else cols[B:] if not joint else [out_attrs[:3, b * m:b * m + K[b]] for b in range(B)]
+    of = None
+    if fl is not None:
+        r0 = out_attrs.shape[0] - 3
+        of = [out_attrs[r0:, b * m:b * m + K[b]] for b in range(B)]
+    res = (o1, o2, of, stats if joint else stats.view(2, B, 4))
+    if return_index:
+        res += ([idx[b, :K[b]].long() for b in range(len(clouds))],)
+    return res
+
+
 # ----------------------------------------------------------------------------- frames from raw maps
 def _pack_planes(who, frames, specs, device):
     """frames: a list of tuples of per-frame arrays (numpy or tensors), plane k of shape (H, W) + specs[k][1] and a dtype in

@@ -906,6 +906,98 @@ def voxel_downsample(pc, attrs=None, voxel=0.1, origin=(0, 0, 0), mode='centroid
     return out_pc, out_attrs, count, rep, voxel_of, stats
 
 
+# --------------------------------------------------------------------------- farthest point sampling
+FPS_PATHS = {'auto': 0, 'resident': 1, 'rounds': 2}
+
+
+def fps_resident_capacity():
+    """The most points a cloud may hold on fps's resident path."""
+    return int(_lib.load().hpl_fps_resident_capacity())
+
+
+def fps_args(who, m, batch, path='auto'):
+    """(m, the path's number) or an HplError: m a non-bool int >= 1 with batch * m inside the 32-bit limit."""
+    if isinstance(m, bool) or not isinstance(m, int) or m < 1 or batch * m >= (2 ** 31 + 2) // 3:
+        raise _lib.HplError('%s: %r samples for each of %d clouds (an int >= 1, together below 2^31 / 3)' % (who, m, batch))
+    if not isinstance(path, str) or path not in FPS_PATHS:
+        raise _lib.HplError('%s: path = %r (%s)' % (who, path, ', '.join(repr(p) for p in FPS_PATHS)))
+    return m, FPS_PATHS[path]
+
+
+def fps(pc, m, attrs=None, start=None, prefix=None, path='auto', return_cover=False, out=None):
+    """hpl_fps on the current stream: farthest point sampling, m points per cloud in selection order -- sample 0
+    is the cloud's start (start[b], a cloud-local index; None, or a start whose point is not finite: the smallest finite
+    index), every further sample the finite point farthest (float32 d2, ties to the smaller index) from all samples before it;
+    a cloud stops early when every remaining point coincides with a sample.  pc (3, N) float32 (rows may be views of a wider
+    buffer); attrs (C, N) float32, C <= 8, or None: channels gathered with their points; prefix (host sequence of B + 1 ints
+    from 0 to N): B <= 64 clouds, each sampled on its own; start: None or a host sequence of B ints; path: 'auto', 'resident'
+    (one launch, clouds of at most fps_resident_capacity() points) or 'rounds' (one launch a round, any size) -- the same bits.
+    -> (out_pc (3, B m) float32: column b m + j is sample j of cloud b, 0 past the cloud's count; out_attrs (C, B m) or None;
+    idx (B, m) int32, cloud-local, -1 past the count; dist (B, m) float32: each sample's distance to the samples before it
+    when it was chosen, +inf for sample 0, 0 past the count; cover (N,) float32 with return_cover, else None: every point's
+    squared distance to its nearest sample; stats (B, 4) int32 = (count, finite points, others, the path taken: 1 or 2)).
+    out: a (3, B m) float32 tensor with unit stride along the samples that takes out_pc; it must not overlap pc or attrs.  The
+    same bits for a cloud alone and in any batch.  No autograd, no host synchronisation, no read-back."""
+    who = 'fps'
+    pc, pc_ld = _soa3(pc, 'pc', who)
+    N, dev = pc.shape[1], pc.device
+    C, attr_ld = 0, 0
+    if attrs is not None:
+        if not torch.is_tensor(attrs) or attrs.dim() != 2 or attrs.shape[1] != N or attrs.dtype != torch.float32 or \
+                attrs.device != dev or not 1 <= attrs.shape[0] <= 8:
+            raise _lib.HplError('%s: attrs must be a (C, %d) float32 tensor on %s with 1 <= C <= 8, got %s' % (
+                who, N, dev, (tuple(attrs.shape), attrs.dtype, attrs.device) if torch.is_tensor(attrs) else type(attrs)))
+        if attrs.requires_grad:
+            raise _lib.HplError('%s has no autograd: attrs requires grad' % who)
+        C = attrs.shape[0]
+        if (C > 1 and attrs.stride(0) < max(N, 1)) or (N > 1 and attrs.stride(1) != 1):
+            attrs = attrs.contiguous()
+        attr_ld = max(N, 1) if C == 1 or attrs.is_contiguous() else attrs.stride(0)
+    pp = _prefix(prefix, N, who)
+    B = len(pp) - 1
+    m, pnum = fps_args(who, m, B, path)
+    M = B * m
+    st = None
+    if start is not None:
+        import operator
+        try:
+            st = [None if isinstance(x, bool) else operator.index(x) for x in start]
+        except TypeError:
+            st = None
+        if st is None or len(st) != B or None in st or any(pp[b + 1] > pp[b] and not 0 <= st[b] < pp[b + 1] - pp[b] for b in range(B)):
+            raise _lib.HplError('%s: start holds %d ints, each an index into its cloud, got %r' % (who, B, start))
+        st = (ctypes.c_int32 * B)(*[x if pp[b + 1] > pp[b] else 0 for b, x in enumerate(st)])
+    if out is not None:
+        if not torch.is_tensor(out) or tuple(out.shape) != (3, M) or out.dtype != torch.float32 or out.device != dev or \
+                out.requires_grad or out.stride(0) < M or (M > 1 and out.stride(1) != 1):
+            raise _lib.HplError('%s: out must be a (3, %d) float32 tensor on %s with unit stride along the samples' % (who, M, dev))
+        out_pc = out
+    else:
+        out_pc = torch.empty((3, M), dtype=torch.float32, device=dev)
+    out_ld = M if out_pc.is_contiguous() else out_pc.stride(0)
+    if N == 0:                                   # nothing to launch: every cloud is empty
+        out_pc.zero_()
+        return (out_pc, torch.zeros((C, M), dtype=torch.float32, device=dev) if C else None,
+                torch.full((B, m), -1, dtype=torch.int32, device=dev), torch.zeros((B, m), dtype=torch.float32, device=dev),
+                torch.zeros(0, dtype=torch.float32, device=dev) if return_cover else None,
+                torch.zeros((B, 4), dtype=torch.int32, device=dev))
+    out_attrs = torch.empty((C, M), dtype=torch.float32, device=dev) if C else None
+    idx = torch.empty((B, m), dtype=torch.int32, device=dev)
+    dist = torch.empty((B, m), dtype=torch.float32, device=dev)
+    cover = torch.empty(N, dtype=torch.float32, device=dev) if return_cover else None
+    stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    nbytes = lib.hpl_fps_workspace_bytes(B, N, m, C)
+    if nbytes < 0:
+        raise _lib.HplError('%s: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (who, B, N))
+    s = stream()
+    ws = _workspace(who, dev, s, nbytes)
+    check(lib.hpl_fps(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, (ctypes.c_int64 * (B + 1))(*pp), st, m, pnum,
+                      idx.data_ptr(), dist.data_ptr(), out_pc.data_ptr(), out_ld, ptr(out_attrs), M, ptr(cover),
+                      stats.data_ptr(), ws.data_ptr(), ws.numel(), s), 'hpl_fps')
+    return out_pc, out_attrs, idx, dist, cover, stats
+
+
 # --------------------------------------------------------------------------- frames from raw maps
 def _frames_plane(who, name, t, dtypes, shape, dev):
     """A packed per-pixel device tensor of the given shape and one of the dtypes, contiguous (a view that starts anywhere in a

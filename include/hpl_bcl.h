@@ -1212,6 +1212,59 @@ int hpl_voxel_downsample(const float *pc, int64_t pc_ld, const float *attr, int6
                          hplStream stream);
 
 /* ------------------------------------------------------------------------ *
+ * Farthest point sampling (csrc/fps.hip): exactly m points per cloud -- fewer only when a cloud runs out of distinct
+ * positions --, each the point farthest from all chosen before it, with attribute channels riding along.
+ * ------------------------------------------------------------------------ */
+#define HPL_FPS_AUTO 0
+#define HPL_FPS_RESIDENT 1
+#define HPL_FPS_ROUNDS 2
+/* The most points a cloud may hold on the resident path (one workgroup per cloud, the cloud in registers). */
+int hpl_fps_resident_capacity(void);
+/* Workspace of hpl_fps for `batch` clouds of n_total points together, m samples each and `channels` attribute channels, in
+ * bytes (monotone in batch and n_total); -1 for a batch outside 1 .. 64, channels outside 0 .. 8, n_total outside
+ * 0 .. 2^31 / 3 - 1, m < 1 or batch * m >= 2^31 / 3. */
+int64_t hpl_fps_workspace_bytes(int batch, int64_t n_total, int64_t m, int channels);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N); attr (channels, N) float32 SoA (row stride attr_ld >= N) riding along,
+ * channels 0 .. 8 (attr may be NULL with channels == 0).  batch (1 .. 64) clouds: prefix (HOST, batch + 1 ints from 0 to N,
+ * non-decreasing, empty clouds allowed) travels in the kernel arguments.  m >= 1 samples are asked of every cloud.  start:
+ * HOST, batch cloud-local indices, or NULL.  path: HPL_FPS_AUTO, HPL_FPS_RESIDENT or HPL_FPS_ROUNDS.
+ * Per cloud b of n_b points, on its own:
+ * VALID: a point is valid when its three coordinates are finite.  A point that is not is never selected and never counted.
+ * STATE: D_i = +inf for every valid point i.
+ * START: sample 0 is start[b]; with start == NULL, or when the point at start[b] is not finite, the smallest valid index.
+ * ROUND j >= 1: with s the previous sample, D_i = min(D_i, d2(i, s)), d2 = (dx * dx + dy * dy) + dz * dz in float32, one
+ * rounding per operation, no contraction (the arithmetic of hpl_knn_interp).  Sample j is the valid point of the largest D,
+ * ties to the SMALLER index: the largest key (bits(D) << 32) | (0xFFFFFFFF - i) as an unsigned integer, since D >= +0.
+ * STOP: the cloud stops when the largest D is exactly 0 -- every remaining point then coincides in float32 d2 with a sample,
+ * a true duplicate or a d2 that underflowed -- or when it has no valid point.  So count_b <= min(m, valid_b), and a cloud's
+ * samples are pairwise distinct indices.  A d2 that overflows to +inf is an ordinary value (min(inf, inf) = inf); the
+ * coordinates of valid points are finite, so no NaN can arise.
+ * OUTPUTS: idx [batch][m] int32: cloud-local indices in selection order, -1 past count_b.  dist [batch][m] float32: the D of
+ * each sample at the moment it was chosen, +inf for sample 0, 0 past count_b; from column 1 on it does not increase (min is
+ * exact).  out_pc (3, batch * m) (row stride out_ld >= batch * m): column b * m + j holds sample j of cloud b, 0 past the
+ * count.  out_attr (channels, batch * m) (row stride out_attr_ld): the channels gathered the same way; may be NULL.  cover (N)
+ * float32 or NULL: every point's final D, its squared distance to its nearest sample, 0 for a point that is not valid.  stats
+ * [batch][4] int32: count_b, valid points, points that are not finite, the path taken (HPL_FPS_RESIDENT or HPL_FPS_ROUNDS,
+ * one for the whole call).
+ * PATHS, the same bits on both: RESIDENT holds a cloud in the registers of one workgroup and runs all m rounds in one launch;
+ * it takes clouds of at most hpl_fps_resident_capacity() points.  ROUNDS keeps D in the workspace and takes one launch per
+ * round plus one; it takes any size.  AUTO is RESIDENT when every cloud of the call fits, else ROUNDS for the whole call.
+ * The only atomics are integer counts; no floating-point atomic: a cloud's outputs are the same bits alone, anywhere in a
+ * batch, on either path and beside other work.  Stream-ordered, launches whose number and sizes depend on the prefix and m
+ * alone, no copy back, no host synchronisation (count_b is known on the device only); no workgroup waits for another.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_fps_workspace_bytes(batch, N, m, channels).
+ * HPL_EINVAL before any launch (and without a device): batch, channels, path or m out of range; a prefix that does not start
+ * at 0 or decreases; a start outside its cloud (the start of an empty cloud is ignored); a row stride below N (inputs) or
+ * batch * m (outputs); null pc / prefix / idx / dist / out_pc / stats / workspace, null attr with channels > 0; misaligned
+ * arrays; a workspace that is too small or misaligned; N >= 2^31 / 3; an output overlapping an input; path RESIDENT with a
+ * cloud above the capacity.  N == 0 is a no-op (nothing is written). */
+int hpl_fps(const float *pc, int64_t pc_ld, const float *attr, int64_t attr_ld, int channels, int batch,
+            const int64_t *prefix /* HOST */, const int32_t *start /* HOST [batch] or NULL */, int64_t m, int path,
+            int32_t *idx /* [batch][m] */, float *dist /* [batch][m] */, float *out_pc, int64_t out_ld, float *out_attr,
+            int64_t out_attr_ld, float *cover /* (N) or NULL */, int32_t *stats /* [batch][4] */, void *workspace,
+            int64_t workspace_bytes, hplStream stream);
+
+/* ------------------------------------------------------------------------ *
  * Frames from raw maps (csrc/frames.hip): corresponding point clouds from disparity and optical-flow maps, the valid
  * correspondences of every frame compacted in pixel order.
  * ------------------------------------------------------------------------ */
