@@ -1,14 +1,14 @@
-// icp_common.h -- what icp.hip (point-to-point) and icp_plane.hip (point-to-plane) share, moved
-// here verbatim from icp.hip: the grid key and cell, the record and the per-pair state, the keys kernel, the exact match of a
-// moved src point within max_dist (match_point), the residual, the pivot, the finish, the fold and the room of the sort.  Only
-// IcpArgs gained the two fields of the normals (unused by icp.hip).  Header only; everything has internal linkage.
+// icp_common.h -- what icp.hip (point-to-point) and icp_plane.hip (point-to-plane) share: the
+// per-pair state, the keys kernel, the exact match of a moved src point within max_dist (match_point), the residual, the
+// pivot, the finish, the fold and the room of the sort.  The grid itself (key, cell, record) is grid_common.h's
+// (DESIGN.md §31).  IcpArgs carries the two fields of the normals (unused by icp.hip).  Header only; everything has internal
+// linkage.
 #pragma once
-#include "cloud_common.h"
+#include "grid_common.h"
 #include "rigid_solve.h"
 
 #include <limits.h>
 #include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace hpl;
 
@@ -20,17 +20,6 @@ constexpr int ICP_PER_LANE = 4;
 constexpr int ICP_SPAN = ICP_BLOCK * ICP_PER_LANE;   // src points per workgroup
 constexpr int ICP_RUNS = ICP_BLOCK / RIGID_SUMS;
 constexpr int ICP_AHEAD = 4;                         // records of a run loaded before they are compared
-constexpr int ICP_CELL_BITS = 19;
-constexpr int ICP_CELL_BIAS = 1 << (ICP_CELL_BITS - 1);
-constexpr double ICP_CELL_MAX = (double)(ICP_CELL_BIAS - 2);         // |cell| <= 2^18 - 2: the neighbours' fields stay in 19 bits
-constexpr double ICP_CELL_MARGIN = 1.001;
-
-typedef unsigned long long u64;
-
-struct __attribute__((aligned(16))) Rec {
-    float x, y, z;
-    int32_t i;                  // the packed dst index
-};
 
 struct State {                  // per pair, 64 bytes
     float m[12];                // the current motion: R row-major, then t
@@ -52,7 +41,7 @@ struct IcpArgs {
     State *state;
     double *partials;           // [src workgroups][16]; the finish reuses it as [src workgroups][2]
     u64 *key, *skey;
-    Rec *rec, *srec;
+    GridRec *rec, *srec;        // i: the packed dst index
     float *Rt, *stats, *dist2, *flow;
     int32_t *match;
     double inv_cell, itau2;
@@ -62,20 +51,6 @@ struct IcpArgs {
     int32_t dprefix[CLOUD_MAX_BATCH + 1];      // dst points of pairs 0 .. b-1
     int32_t bprefix[CLOUD_MAX_BATCH + 1];      // src workgroups of pairs 0 .. b-1
 };
-
-__device__ __forceinline__ u64 make_key(int b, int cx, int cy, int cz) {
-    return ((u64)b << (3 * ICP_CELL_BITS)) | ((u64)cx << (2 * ICP_CELL_BITS)) | ((u64)cy << ICP_CELL_BITS) | (u64)cz;
-}
-
-// the cell of (x, y, z), biased; false when the point is non-finite or its cell is outside the field range
-__device__ __forceinline__ bool cell_of(double inv_cell, float x, float y, float z, int *c) {
-    const double cx = floor((double)x * inv_cell), cy = floor((double)y * inv_cell), cz = floor((double)z * inv_cell);
-    if (!(fabs(cx) <= ICP_CELL_MAX && fabs(cy) <= ICP_CELL_MAX && fabs(cz) <= ICP_CELL_MAX)) return false;     // (NaN fails)
-    c[0] = (int)cx + ICP_CELL_BIAS;
-    c[1] = (int)cy + ICP_CELL_BIAS;
-    c[2] = (int)cz + ICP_CELL_BIAS;
-    return true;
-}
 
 __global__ void __launch_bounds__(ICP_BLOCK) k_icp_keys(const IcpArgs a) {
     const int64_t j64 = (int64_t)blockIdx.x * ICP_BLOCK + threadIdx.x;
@@ -92,14 +67,7 @@ __global__ void __launch_bounds__(ICP_BLOCK) k_icp_keys(const IcpArgs a) {
     }
     if (j64 >= a.m) return;
     const int j = (int)j64;
-    const float x = a.dst[j], y = a.dst[a.dst_ld + j], z = a.dst[2 * a.dst_ld + j];
-    int c[3];
-    u64 key = ~0ull;
-    if (cell_of(a.inv_cell, x, y, z, c)) key = make_key(group_of(a.dprefix, a.batch, j), c[0], c[1], c[2]);
-    a.key[j] = key;
-    Rec r;
-    r.x = x; r.y = y; r.z = z; r.i = j;
-    a.rec[j] = r;
+    grid_store(a, a.dprefix, j, a.dst[j], a.dst[a.dst_ld + j], a.dst[2 * a.dst_ld + j]);
 }
 
 struct SrcPoint {
@@ -125,16 +93,18 @@ __device__ __forceinline__ SrcPoint match_point(const IcpArgs &a, int b, int64_t
     int bi = INT_MAX;
     float bx = 0.f, by = 0.f, bz = 0.f;          // the best candidate so far
     int c[3];
-    if (a.m > 0 && cell_of(a.inv_cell, qx, qy, qz, c)) {
+    if (a.m > 0 && grid_cell_of(a.inv_cell, qx, qy, qz, c)) {
         // The 9 runs [lo, hi): lower_bound of the run's first key and of the key behind its last, all 18 searches in lockstep.
         // The step sizes depend on m alone, so the 18 loads of a step are independent: a point waits for log2(m) loads in a
-        // row, not for 18 times as many, and the scans below know their ends without reading a key.
+        // row, not for 18 times as many, and the scans below know their ends without reading a key.  (k_normals has the same
+        // text: one function for both changed the code of both, k_normals<32> was slower through it and the ICP kernels were
+        // not timed, DESIGN.md §31, rule R.)
         u64 klo[9], khi[9];
         int lo[9], hi[9];
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
-            klo[k] = make_key(b, c[0] + k / 3 - 1, c[1] + k % 3 - 1, c[2] - 1);
-            khi[k] = make_key(b, c[0] + k / 3 - 1, c[1] + k % 3 - 1, c[2] + 1) + 1;
+            klo[k] = grid_key(b, c[0] + k / 3 - 1, c[1] + k % 3 - 1, c[2] - 1);
+            khi[k] = grid_key(b, c[0] + k / 3 - 1, c[1] + k % 3 - 1, c[2] + 1) + 1;
             lo[k] = hi[k] = 0;
         }
         int n = a.m;                             // the answer lies in [lo, lo + n]
@@ -155,7 +125,7 @@ __device__ __forceinline__ SrcPoint match_point(const IcpArgs &a, int b, int64_t
 #pragma unroll
         for (int k = 0; k < 9; ++k) {
             for (int t = lo[k]; t < hi[k]; t += ICP_AHEAD) {
-                Rec r[ICP_AHEAD];                // independent loads, in flight together; those past the run repeat its last
+                GridRec r[ICP_AHEAD];            // independent loads, in flight together; those past the run repeat its last
 #pragma unroll
                 for (int v = 0; v < ICP_AHEAD; ++v) r[v] = a.srec[min(t + v, hi[k] - 1)];
 #pragma unroll
@@ -254,18 +224,9 @@ __global__ void __launch_bounds__(ICP_BLOCK) k_icp_fold(const IcpArgs a) {
     o[5] = (float)st.rounds;
 }
 
-size_t temp_bytes(int64_t n) {
-    size_t s = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, s, (const u64 *)nullptr, (u64 *)nullptr, (const Rec *)nullptr, (Rec *)nullptr,
-                                    (size_t)n, 0u, 64u, (hipStream_t) nullptr);
-    return s;
-}
-
-// rocPRIM does not promise that its temporary storage grows with n: the room kept for it covers n and the next power of two
+// the room of the one sort of (key, record)
 inline int64_t temp_room(int64_t n) {
-    int64_t cap = 1024;
-    while (cap < n) cap <<= 1;
-    return align256((int64_t)imax((int64_t)temp_bytes(n), (int64_t)temp_bytes(cap)));
+    return room_next_pow2(n, [](int64_t c) { return radix_temp_bytes<u64, GridRec>(c, 64u); });
 }
 
 }  // namespace

@@ -162,8 +162,8 @@ struct Layout {                  // byte offsets
         partials = c.take((cdiv(n, ICP_SPAN) + batch) * ICPP_SUMS * (int64_t)sizeof(double));
         key = c.take(m * 8);
         skey = c.take(m * 8);
-        rec = c.take(m * (int64_t)sizeof(Rec));
-        srec = c.take(m * (int64_t)sizeof(Rec));
+        rec = c.take(m * (int64_t)sizeof(GridRec));
+        srec = c.take(m * (int64_t)sizeof(GridRec));
         bytes = c.bytes;
     }
 };
@@ -211,9 +211,9 @@ extern "C" int hpl_icp_plane(const float *src, int64_t src_ld, const float *dst,
     a.state = carved<State>(workspace, L.state);
     a.partials = carved<double>(workspace, L.partials);
     a.key = carved<u64>(workspace, L.key); a.skey = carved<u64>(workspace, L.skey);
-    a.rec = carved<Rec>(workspace, L.rec); a.srec = carved<Rec>(workspace, L.srec);
+    a.rec = carved<GridRec>(workspace, L.rec); a.srec = carved<GridRec>(workspace, L.srec);
     a.Rt = Rt; a.stats = stats; a.match = match; a.dist2 = dist2; a.flow = flow;
-    a.inv_cell = 1.0 / (ICP_CELL_MARGIN * (double)max_dist);
+    a.inv_cell = 1.0 / (GRID_CELL_MARGIN * (double)max_dist);
     a.itau2 = 1.0 / ((double)tau * (double)tau);
     a.md2 = max_dist * max_dist;                 // rounded once to float32, as the acceptance states
     a.tol_rot = tol_rot; a.tol_trans = tol_trans;
@@ -226,7 +226,7 @@ extern "C" int hpl_icp_plane(const float *src, int64_t src_ld, const float *dst,
     HPL_CHECK_LAUNCH("hpl_icp_plane (keys)");
     if (M > 0) {
         size_t tb = (size_t)temp_room(M);
-        const hipError_t e = rocprim::radix_sort_pairs(temp, tb, (const u64 *)a.key, a.skey, (const Rec *)a.rec, a.srec, (size_t)M,
+        const hipError_t e = rocprim::radix_sort_pairs(temp, tb, (const u64 *)a.key, a.skey, (const GridRec *)a.rec, a.srec, (size_t)M,
                                                        0u, 64u, s);      // (the largest key, of the points left out, has every bit set)
         if (e != hipSuccess) { set_error("hpl_icp_plane: radix sort failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
     }

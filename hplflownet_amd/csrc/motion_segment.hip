@@ -24,11 +24,11 @@
 //                  ..., then an LDS tree), rounded once
 //
 // Integer counts do not depend on their order, the float sums have one order, the root is the smallest index: every output of
-// a pair is the same bits alone, anywhere in a batch and beside other work.
-#include "cloud_common.h"
+// a pair is the same bits alone, anywhere in a batch and beside other work.  The key, its limits, the counter and the room of
+// the sorts are grid_common.h's.
+#include "grid_common.h"
 
 #include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 using namespace hpl;
@@ -37,12 +37,6 @@ namespace {
 
 constexpr int MS_MAX_OBJECTS = 4096;
 constexpr int MS_BLOCK = 256;
-constexpr int MS_CELL_BITS = 19;
-constexpr int MS_CELL_BIAS = 1 << (MS_CELL_BITS - 1);
-constexpr double MS_CELL_MAX = (double)(MS_CELL_BIAS - 2);           // |cell| <= 2^18 - 2: the neighbours' fields stay in 19 bits
-constexpr double MS_CELL_MARGIN = 1.001;
-
-typedef unsigned long long u64;
 
 struct SegArgs {
     const float *pc;
@@ -67,20 +61,6 @@ struct SegArgs {
 // the pair of point i: the last one that starts at or before i
 __device__ __forceinline__ int pair_of(const SegArgs &a, int i) { return group_of(a.pprefix, a.batch, i); }
 
-__device__ __forceinline__ u64 make_key(int b, int cx, int cy, int cz) {
-    return ((u64)b << (3 * MS_CELL_BITS)) | ((u64)cx << (2 * MS_CELL_BITS)) | ((u64)cy << MS_CELL_BITS) | (u64)cz;
-}
-
-// adds v to stats[pair][slot] for every lane with v != 0; a workgroup inside one pair sends one atomic
-__device__ __forceinline__ void count_into(const SegArgs &a, bool uniform, int b, int slot, int v) {
-    if (uniform) {
-        const int total = __syncthreads_count(v);
-        if (threadIdx.x == 0 && total) atomicAdd(&a.stats[b * 4 + slot], total);
-    } else if (v) {
-        atomicAdd(&a.stats[b * 4 + slot], 1);
-    }
-}
-
 __global__ void __launch_bounds__(MS_BLOCK) k_seg_keys(const SegArgs a) {
     const int64_t i0 = (int64_t)blockIdx.x * MS_BLOCK;
     const int64_t i64 = i0 + threadIdx.x;
@@ -98,9 +78,9 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_keys(const SegArgs a) {
         const bool ok = isfinite(x) && isfinite(y) && isfinite(z) && isfinite(fx) && isfinite(fy) && isfinite(fz);
         if (ok && r > a.tau) {                   // (a NaN residual fails the comparison)
             const double cx = floor((double)x * a.inv_cell), cy = floor((double)y * a.inv_cell), cz = floor((double)z * a.inv_cell);
-            mover = fabs(cx) <= MS_CELL_MAX && fabs(cy) <= MS_CELL_MAX && fabs(cz) <= MS_CELL_MAX;
+            mover = fabs(cx) <= GRID_CELL_MAX && fabs(cy) <= GRID_CELL_MAX && fabs(cz) <= GRID_CELL_MAX;
             oob = !mover;
-            if (mover) key = make_key(b, (int)cx + MS_CELL_BIAS, (int)cy + MS_CELL_BIAS, (int)cz + MS_CELL_BIAS);
+            if (mover) key = grid_key(b, (int)cx + GRID_CELL_BIAS, (int)cy + GRID_CELL_BIAS, (int)cz + GRID_CELL_BIAS);
         }
         a.key[i] = key;
         a.val[i] = i;
@@ -108,8 +88,8 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_keys(const SegArgs a) {
         a.size[i] = 0;
         a.labels[i] = oob ? -3 : -1;
     }
-    count_into(a, uniform, b, 0, mover ? 1 : 0);
-    count_into(a, uniform, b, 3, oob ? 1 : 0);
+    count_into(a.stats, uniform, b, 0, mover ? 1 : 0);
+    count_into(a.stats, uniform, b, 3, oob ? 1 : 0);
 }
 
 __device__ __forceinline__ int load_parent(const int32_t *parent, int x) {
@@ -148,12 +128,12 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_link(const SegArgs a) {
     const float x = a.pc[i], y = a.pc[a.pc_ld + i], z = a.pc[2 * a.pc_ld + i];
     const float *f = a.flow + (int64_t)i * a.fsp;
     const float fx = f[0], fy = f[a.fsc], fz = f[2 * a.fsc];
-    const u64 cell_mask = ((u64)1 << MS_CELL_BITS) - 1;
-    const int cx = (int)((key >> (2 * MS_CELL_BITS)) & cell_mask), cy = (int)((key >> MS_CELL_BITS) & cell_mask);
-    const int cz = (int)(key & cell_mask), b = (int)(key >> (3 * MS_CELL_BITS));
+    int c[3];
+    grid_cell(key, c);
+    const int b = grid_group(key);
     for (int dx = -1; dx <= 1; ++dx) {
         for (int dy = -1; dy <= 1; ++dy) {
-            const u64 klo = make_key(b, cx + dx, cy + dy, cz - 1), khi = make_key(b, cx + dx, cy + dy, cz + 1);
+            const u64 klo = grid_key(b, c[0] + dx, c[1] + dy, c[2] - 1), khi = grid_key(b, c[0] + dx, c[1] + dy, c[2] + 1);
             // every link is made once, by its later-indexed end
             for (int t = lower_bound(a.skey, a.n, klo); t < a.n && a.skey[t] <= khi; ++t) {
                 const int j = a.sval[t];
@@ -216,7 +196,7 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_label(const SegArgs a) {
         }
         a.okey[i] = k;
     }
-    count_into(a, uniform, b, 2, member ? 1 : 0);
+    count_into(a.stats, uniform, b, 2, member ? 1 : 0);
 }
 
 __global__ void __launch_bounds__(MS_BLOCK) k_seg_objects(const SegArgs a) {
@@ -251,14 +231,12 @@ __global__ void __launch_bounds__(MS_BLOCK) k_seg_objects(const SegArgs a) {
     if (t < 6) motion[t] = (float)(red[t][0] / (double)m);
 }
 
+// the two sorts and the scan share the room: enough for any of them
 size_t temp_bytes(int64_t n) {
-    size_t s1 = 0, s2 = 0, sc = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, s1, (const u64 *)nullptr, (u64 *)nullptr, (const int32_t *)nullptr,
-                                    (int32_t *)nullptr, (size_t)n, 0u, 64u, (hipStream_t) nullptr);
-    (void)rocprim::radix_sort_pairs(nullptr, s2, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
-                                    (int32_t *)nullptr, (size_t)n, 0u, 32u, (hipStream_t) nullptr);
+    size_t sc = 0;
     (void)rocprim::exclusive_scan(nullptr, sc, (const int32_t *)nullptr, (int32_t *)nullptr, 0, (size_t)(n + 1),
                                   rocprim::plus<int32_t>(), (hipStream_t) nullptr);
+    const size_t s1 = radix_temp_bytes<u64, int32_t>(n, 64u), s2 = radix_temp_bytes<uint32_t, int32_t>(n, 32u);
     const size_t m = s1 > s2 ? s1 : s2;
     return m > sc ? m : sc;
 }
@@ -284,12 +262,7 @@ struct Layout {                  // byte offsets
     }
 };
 
-// rocPRIM does not promise that its temporary storage grows with n: the room kept for it covers n and the next power of two
-inline int64_t temp_room(int64_t n) {
-    int64_t cap = 1024;
-    while (cap < n) cap <<= 1;
-    return align256((int64_t)imax((int64_t)temp_bytes(n), (int64_t)temp_bytes(cap)));
-}
+inline int64_t temp_room(int64_t n) { return room_next_pow2(n, temp_bytes); }
 
 int64_t workspace_bytes(int64_t n) { return Layout(n).bytes + temp_room(n); }
 
@@ -330,7 +303,7 @@ extern "C" int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *f
     a.tau = tau;
     a.eps2 = eps * eps;                          // rounded once to float32, as the predicate states
     a.dv2 = dv * dv;
-    a.inv_cell = 1.0 / (MS_CELL_MARGIN * (double)eps);
+    a.inv_cell = 1.0 / (GRID_CELL_MARGIN * (double)eps);
     a.n = (int32_t)N; a.batch = batch; a.min_points = min_points; a.max_objects = max_objects;
     a.key = carved<u64>(workspace, L.key); a.skey = carved<u64>(workspace, L.skey);
     a.val = carved<int32_t>(workspace, L.val); a.sval = carved<int32_t>(workspace, L.sval);

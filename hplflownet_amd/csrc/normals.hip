@@ -3,8 +3,9 @@
 // eigenvalue of their float64 scatter matrix, oriented towards a viewpoint.
 //
 // The definition of a neighbourhood is the all-pairs one of include/hpl_bcl.h; the grid only finds the candidates.  The cell
-// edge is 1.001 radius and a point's cell floor(x / (1.001 radius)) is taken in float64 (the key and the cell are icp.hip's,
-// restated here), so a point within radius of another (even by the rounded float32 d2) lies in its cell or an adjacent one.
+// edge is 1.001 radius and a point's cell floor(x / (1.001 radius)) is taken in float64 (the key, the cell and the record are
+// grid_common.h's), so a point within radius of another (even by the rounded float32 d2) lies in
+// its cell or an adjacent one.
 //
 //   k_normals_keys  a lane per point: the 64-bit key (cloud, cell x, y, z) -- a point that takes no part carries the largest
 //                   key -- and its 16-byte (x, y, z, index) record
@@ -18,11 +19,10 @@
 //
 // No floating-point atomic, no read-back, no lane waits for another; every loop is bounded by a cell population or a search
 // depth.  The bits depend on the cloud alone.
-#include "cloud_common.h"
+#include "grid_common.h"
 
 #include <limits.h>
 #include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace hpl;
 
@@ -33,18 +33,6 @@ constexpr int NR_MIN_K = 3;
 constexpr int NR_MAX_K = 32;
 constexpr int NR_AHEAD = 4;                          // records of a run loaded before they are compared
 constexpr int NR_SWEEPS = 12;                        // ground_fit.hip's GF_SWEEPS
-constexpr int NR_CELL_BITS = 19;
-constexpr int NR_CELL_BIAS = 1 << (NR_CELL_BITS - 1);
-constexpr int NR_CELL_MASK = (1 << NR_CELL_BITS) - 1;
-constexpr double NR_CELL_MAX = (double)(NR_CELL_BIAS - 2);          // |cell| <= 2^18 - 2: the neighbours' fields stay in 19 bits
-constexpr double NR_CELL_MARGIN = 1.001;
-
-typedef unsigned long long u64;
-
-struct __attribute__((aligned(16))) Rec {
-    float x, y, z;
-    int32_t i;                  // the packed index
-};
 
 struct NormalsArgs {
     const float *pc;
@@ -55,7 +43,7 @@ struct NormalsArgs {
     int32_t *count, *nbr;
     float *nbr_d2;
     u64 *key, *skey;
-    Rec *rec, *srec;
+    GridRec *rec, *srec;
     double inv_cell;
     float r2;
     int32_t n, batch, k;
@@ -63,32 +51,11 @@ struct NormalsArgs {
     float view[CLOUD_MAX_BATCH][3];
 };
 
-__device__ __forceinline__ u64 make_key(int b, int cx, int cy, int cz) {
-    return ((u64)b << (3 * NR_CELL_BITS)) | ((u64)cx << (2 * NR_CELL_BITS)) | ((u64)cy << NR_CELL_BITS) | (u64)cz;
-}
-
-// the cell of (x, y, z), biased; false when the point is non-finite or its cell is outside the field range
-__device__ __forceinline__ bool cell_of(double inv_cell, float x, float y, float z, int *c) {
-    const double cx = floor((double)x * inv_cell), cy = floor((double)y * inv_cell), cz = floor((double)z * inv_cell);
-    if (!(fabs(cx) <= NR_CELL_MAX && fabs(cy) <= NR_CELL_MAX && fabs(cz) <= NR_CELL_MAX)) return false;         // (NaN fails)
-    c[0] = (int)cx + NR_CELL_BIAS;
-    c[1] = (int)cy + NR_CELL_BIAS;
-    c[2] = (int)cz + NR_CELL_BIAS;
-    return true;
-}
-
 __global__ void __launch_bounds__(NR_BLOCK) k_normals_keys(const NormalsArgs a) {
     const int64_t j64 = (int64_t)blockIdx.x * NR_BLOCK + threadIdx.x;
     if (j64 >= a.n) return;
     const int j = (int)j64;
-    const float x = a.pc[j], y = a.pc[a.pc_ld + j], z = a.pc[2 * a.pc_ld + j];
-    int c[3];
-    u64 key = ~0ull;
-    if (cell_of(a.inv_cell, x, y, z, c)) key = make_key(group_of(a.prefix, a.batch, j), c[0], c[1], c[2]);
-    a.key[j] = key;
-    Rec r;
-    r.x = x; r.y = y; r.z = z; r.i = j;
-    a.rec[j] = r;
+    grid_store(a, a.prefix, j, a.pc[j], a.pc[a.pc_ld + j], a.pc[2 * a.pc_ld + j]);
 }
 
 // The element `which` of v[0 .. 8], written with compile-time indices only.  The compiler turns the chain back into an index
@@ -106,7 +73,7 @@ __global__ void __launch_bounds__(NR_BLOCK) k_normals(const NormalsArgs a) {
     if (s64 >= a.n) return;
     const int s = (int)s64;
     const u64 key = a.skey[s];
-    const Rec me = a.srec[s];
+    const GridRec me = a.srec[s];
     const int64_t i = me.i;
 
     float ld[K];                                 // the list: ascending (d2, index); unused entries (+inf, INT_MAX)
@@ -115,18 +82,18 @@ __global__ void __launch_bounds__(NR_BLOCK) k_normals(const NormalsArgs a) {
     for (int t = 0; t < K; ++t) { ld[t] = INFINITY; lj[t] = INT_MAX; }
 
     if (key != ~0ull) {
-        const int b = (int)(key >> (3 * NR_CELL_BITS));
-        const int c0 = (int)(key >> (2 * NR_CELL_BITS)) & NR_CELL_MASK, c1 = (int)(key >> NR_CELL_BITS) & NR_CELL_MASK,
-                  c2 = (int)key & NR_CELL_MASK;
+        const int b = grid_group(key);
+        int c[3], lo[9], hi[9];
+        grid_cell(key, c);
         // The 9 runs [lo, hi): lower_bound of the run's first key and of the key behind its last, all 18 searches in lockstep
-        // (the step sizes depend on n alone, so the 18 loads of a step are independent).
-        int lo[9], hi[9];
+        // (the step sizes depend on n alone, so the 18 loads of a step are independent).  match_point of icp_common.h has the
+        // same text: through one function for both, k_normals<32> was 0.4 % slower (rule R).
         {
             u64 klo[9], khi[9];
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
-                klo[k] = make_key(b, c0 + k / 3 - 1, c1 + k % 3 - 1, c2 - 1);
-                khi[k] = make_key(b, c0 + k / 3 - 1, c1 + k % 3 - 1, c2 + 1) + 1;
+                klo[k] = grid_key(b, c[0] + k / 3 - 1, c[1] + k % 3 - 1, c[2] - 1);
+                khi[k] = grid_key(b, c[0] + k / 3 - 1, c[1] + k % 3 - 1, c[2] + 1) + 1;
                 lo[k] = hi[k] = 0;
             }
             int n = a.n;                         // the answer lies in [lo, lo + n]
@@ -150,7 +117,7 @@ __global__ void __launch_bounds__(NR_BLOCK) k_normals(const NormalsArgs a) {
             const int end = pick9(hi, run);
 #pragma unroll 1
             for (int t = pick9(lo, run); t < end; t += NR_AHEAD) {
-                Rec r[NR_AHEAD];                 // independent loads, in flight together; those past the run repeat its last
+                GridRec r[NR_AHEAD];             // independent loads, in flight together; those past the run repeat its last
 #pragma unroll
                 for (int v = 0; v < NR_AHEAD; ++v) r[v] = a.srec[min(t + v, end - 1)];
 #pragma unroll
@@ -226,7 +193,7 @@ __global__ void __launch_bounds__(NR_BLOCK) k_normals(const NormalsArgs a) {
             const double len = sqrt((nv[0] * nv[0] + nv[1] * nv[1]) + nv[2] * nv[2]);
 #pragma unroll
             for (int c = 0; c < 3; ++c) nv[c] = nv[c] / len;
-            const int b = (int)(key >> (3 * NR_CELL_BITS));
+            const int b = grid_group(key);
             const double sx = nv[0] * ((double)a.view[b][0] - (double)me.x), sy = nv[1] * ((double)a.view[b][1] - (double)me.y),
                          sz = nv[2] * ((double)a.view[b][2] - (double)me.z);
             const double sd = (sx + sy) + sz;
@@ -242,18 +209,9 @@ __global__ void __launch_bounds__(NR_BLOCK) k_normals(const NormalsArgs a) {
     if (a.curvature) a.curvature[i] = out[3];
 }
 
-size_t temp_bytes(int64_t n) {
-    size_t s = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, s, (const u64 *)nullptr, (u64 *)nullptr, (const Rec *)nullptr, (Rec *)nullptr,
-                                    (size_t)n, 0u, 64u, (hipStream_t) nullptr);
-    return s;
-}
-
-// rocPRIM does not promise that its temporary storage grows with n: the room kept for it covers n and the next power of two
+// the room of the one sort of (key, record)
 inline int64_t temp_room(int64_t n) {
-    int64_t cap = 1024;
-    while (cap < n) cap <<= 1;
-    return align256((int64_t)imax((int64_t)temp_bytes(n), (int64_t)temp_bytes(cap)));
+    return room_next_pow2(n, [](int64_t c) { return radix_temp_bytes<u64, GridRec>(c, 64u); });
 }
 
 // workspace: key | sorted key | records | sorted records | rocPRIM temporaries
@@ -263,8 +221,8 @@ struct Layout {                  // byte offsets
         Carver c;
         key = c.take(n * 8);
         skey = c.take(n * 8);
-        rec = c.take(n * (int64_t)sizeof(Rec));
-        srec = c.take(n * (int64_t)sizeof(Rec));
+        rec = c.take(n * (int64_t)sizeof(GridRec));
+        srec = c.take(n * (int64_t)sizeof(GridRec));
         bytes = c.bytes;
     }
 };
@@ -321,8 +279,8 @@ extern "C" int hpl_normals(const float *pc, int64_t pc_ld, int batch, const int6
     a.pc = pc; a.pc_ld = pc_ld; a.normal = normal; a.normal_ld = normal_ld; a.curvature = curvature;
     a.count = count; a.nbr = nbr; a.nbr_d2 = nbr_d2;
     a.key = carved<u64>(workspace, L.key); a.skey = carved<u64>(workspace, L.skey);
-    a.rec = carved<Rec>(workspace, L.rec); a.srec = carved<Rec>(workspace, L.srec);
-    a.inv_cell = 1.0 / (NR_CELL_MARGIN * (double)radius);
+    a.rec = carved<GridRec>(workspace, L.rec); a.srec = carved<GridRec>(workspace, L.srec);
+    a.inv_cell = 1.0 / (GRID_CELL_MARGIN * (double)radius);
     a.r2 = radius * radius;                      // rounded once to float32, as the acceptance states
     a.n = (int32_t)N; a.batch = batch; a.k = k;
     narrow_prefix(prefix, batch, NR_BLOCK, a.prefix, nullptr);
@@ -334,7 +292,7 @@ extern "C" int hpl_normals(const float *pc, int64_t pc_ld, int batch, const int6
     k_normals_keys<<<blocks, NR_BLOCK, 0, s>>>(a);
     HPL_CHECK_LAUNCH("hpl_normals (keys)");
     size_t tb = (size_t)temp_room(N);
-    const hipError_t e = rocprim::radix_sort_pairs(temp, tb, (const u64 *)a.key, a.skey, (const Rec *)a.rec, a.srec, (size_t)N, 0u,
+    const hipError_t e = rocprim::radix_sort_pairs(temp, tb, (const u64 *)a.key, a.skey, (const GridRec *)a.rec, a.srec, (size_t)N, 0u,
                                                    64u, s);      // (the largest key, of the points left out, has every bit set)
     if (e != hipSuccess) { set_error("hpl_normals: radix sort failed: %s", hipGetErrorString(e)); return HPL_EHIP; }
     if (k <= 8) k_normals<8><<<blocks, NR_BLOCK, 0, s>>>(a);

@@ -20,10 +20,9 @@
 // and beside other work.
 //
 // The arithmetic is part of the interface (include/hpl_bcl.h; tests/selfsup_oracle.py restates it in numpy).
-#include "cloud_common.h"
+#include "grid_common.h"
 
 #include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
 
 using namespace hpl;
 
@@ -33,8 +32,6 @@ constexpr int SS_MAX_K = 8;
 constexpr int SS_BLOCK = 256;
 constexpr int SS_TILE = 1024;            // records per LDS tile: 16 KiB
 constexpr int SS_SHORT = 16;             // a longer incoming run is summed by its wave together
-
-typedef unsigned long long u64;
 
 struct SsArgs {
     const float *pc1;
@@ -341,19 +338,9 @@ __global__ void __launch_bounds__(SS_BLOCK) k_ss_fold(const SsArgs a) {
     o[3] = (float)S;
 }
 
-size_t temp_bytes(int64_t n) {
-    size_t s = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, s, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const int32_t *)nullptr,
-                                    (int32_t *)nullptr, (size_t)n, 0u, 32u, (hipStream_t) nullptr);
-    return s;
-}
-
-// rocPRIM does not promise that its temporary storage grows with n: the room kept for it covers n and every power of two up
-// to the next one, so it never shrinks as n grows
+// the room of one sort of n (key, index) pairs (grid_common.h)
 inline int64_t temp_room(int64_t n) {
-    int64_t room = (int64_t)temp_bytes(n);
-    for (int64_t cap = 1024; cap < 2 * imax(n, 1024); cap <<= 1) room = imax(room, (int64_t)temp_bytes(cap));
-    return align256(room);
+    return room_all_pow2(n, [](int64_t c) { return radix_temp_bytes<uint32_t, int32_t>(c, 32u); });
 }
 
 // workspace: the three partial arrays | nn12 | nn21 | nbr | k_i | the two sorts' keys and values, unsorted and sorted | rocPRIM

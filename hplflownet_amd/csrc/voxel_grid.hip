@@ -20,11 +20,11 @@
 // one order and the voxel numbering is the cloud's own: a cloud's outputs are the same bits alone, anywhere in a batch and
 // beside other work.
 //
-// The arithmetic is part of the interface (include/hpl_bcl.h; tests/voxel_oracle.py restates it in numpy).
-#include "cloud_common.h"
+// The arithmetic is part of the interface (include/hpl_bcl.h; tests/voxel_oracle.py restates it in numpy).  The key, its
+// limits, the counter and the room of the sort are grid_common.h's.
+#include "grid_common.h"
 
 #include <math.h>
-#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 using namespace hpl;
@@ -34,14 +34,7 @@ namespace {
 constexpr int VX_MAX_CHANNELS = 8;
 constexpr int VX_BLOCK = 256;
 constexpr int VX_SHORT = 32;             // a longer run is summed by its wave together
-constexpr int VX_CELL_BITS = 19;
-constexpr int VX_CELL_BIAS = 1 << (VX_CELL_BITS - 1);
-constexpr double VX_CELL_MAX = (double)(VX_CELL_BIAS - 2);           // |cell| <= 2^18 - 2, the range of hpl_motion_segment
-constexpr int VX_KEY_BITS = 3 * VX_CELL_BITS;                        // below the cloud digit
-
-typedef unsigned long long u64;
-
-constexpr u64 VX_CELLS_MASK = ((u64)1 << VX_KEY_BITS) - 1;           // all ones: no cell (a biased cell is at most 2^19 - 2)
+constexpr u64 VX_CELLS_MASK = ((u64)1 << GRID_KEY_BITS) - 1;         // all ones: no cell (a biased cell is at most 2^19 - 2)
 
 struct VxArgs {
     const float *pc;
@@ -64,16 +57,6 @@ struct VxArgs {
 
 __device__ __forceinline__ int cloud_of(const VxArgs &a, int i) { return group_of(a.pprefix, a.batch, i); }
 
-// adds v to stats[cloud][slot] for every lane with v != 0; a workgroup inside one cloud sends one atomic
-__device__ __forceinline__ void count_into(const VxArgs &a, bool uniform, int b, int slot, int v) {
-    if (uniform) {
-        const int total = __syncthreads_count(v);
-        if (threadIdx.x == 0 && total) atomicAdd(&a.stats[b * 4 + slot], total);
-    } else if (v) {
-        atomicAdd(&a.stats[b * 4 + slot], 1);
-    }
-}
-
 __global__ void __launch_bounds__(VX_BLOCK) k_vx_keys(const VxArgs a) {
     const int64_t i0 = (int64_t)blockIdx.x * VX_BLOCK;
     const int64_t i64 = i0 + threadIdx.x;
@@ -84,24 +67,22 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vx_keys(const VxArgs a) {
     bool valid = false, nonfinite = false, oob = false;
     if (in) {
         const float x = a.pc[i], y = a.pc[a.pc_ld + i], z = a.pc[2 * a.pc_ld + i];
-        u64 key = ((u64)b << VX_KEY_BITS) | VX_CELLS_MASK;
+        u64 key = ((u64)b << GRID_KEY_BITS) | VX_CELLS_MASK;
         if (isfinite(x) && isfinite(y) && isfinite(z)) {
             const double cx = floor(((double)x - a.org[0]) * a.inv), cy = floor(((double)y - a.org[1]) * a.inv),
                          cz = floor(((double)z - a.org[2]) * a.inv);
-            valid = fabs(cx) <= VX_CELL_MAX && fabs(cy) <= VX_CELL_MAX && fabs(cz) <= VX_CELL_MAX;
+            valid = fabs(cx) <= GRID_CELL_MAX && fabs(cy) <= GRID_CELL_MAX && fabs(cz) <= GRID_CELL_MAX;
             oob = !valid;
-            if (valid)
-                key = ((u64)b << VX_KEY_BITS) | ((u64)((int)cx + VX_CELL_BIAS) << (2 * VX_CELL_BITS)) |
-                      ((u64)((int)cy + VX_CELL_BIAS) << VX_CELL_BITS) | (u64)((int)cz + VX_CELL_BIAS);
+            if (valid) key = grid_key(b, (int)cx + GRID_CELL_BIAS, (int)cy + GRID_CELL_BIAS, (int)cz + GRID_CELL_BIAS);
         } else {
             nonfinite = true;
         }
         a.key[i] = key;
         a.val[i] = i;
     }
-    count_into(a, uniform, b, 1, valid ? 1 : 0);
-    count_into(a, uniform, b, 2, nonfinite ? 1 : 0);
-    count_into(a, uniform, b, 3, oob ? 1 : 0);
+    count_into(a.stats, uniform, b, 1, valid ? 1 : 0);
+    count_into(a.stats, uniform, b, 2, nonfinite ? 1 : 0);
+    count_into(a.stats, uniform, b, 3, oob ? 1 : 0);
 }
 
 __device__ __forceinline__ bool has_cell(u64 key) { return (key & VX_CELLS_MASK) != VX_CELLS_MASK; }
@@ -280,24 +261,18 @@ __global__ void __launch_bounds__(VX_BLOCK) k_vx_reduce(const VxArgs a) {
     }
 }
 
-int sort_bits(int batch) { return VX_KEY_BITS + count_bits(batch - 1); }
+int sort_bits(int batch) { return GRID_KEY_BITS + count_bits(batch - 1); }
 
+// the sort and the scan share the room: enough for either
 size_t temp_bytes(int64_t n) {
-    size_t ss = 0, sc = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, ss, (const u64 *)nullptr, (u64 *)nullptr, (const int32_t *)nullptr,
-                                    (int32_t *)nullptr, (size_t)n, 0u, 64u, (hipStream_t) nullptr);
+    size_t sc = 0;
     (void)rocprim::inclusive_scan(nullptr, sc, (const int32_t *)nullptr, (int32_t *)nullptr, (size_t)n, rocprim::plus<int32_t>(),
                                   (hipStream_t) nullptr);
+    const size_t ss = radix_temp_bytes<u64, int32_t>(n, 64u);
     return ss > sc ? ss : sc;
 }
 
-// rocPRIM does not promise that its temporary storage grows with n: the room kept for it covers n and every power of two up
-// to the next one, so it never shrinks as n grows
-inline int64_t temp_room(int64_t n) {
-    int64_t room = (int64_t)temp_bytes(n);
-    for (int64_t cap = 1024; cap < 2 * imax(n, 1024); cap <<= 1) room = imax(room, (int64_t)temp_bytes(cap));
-    return align256(room);
-}
+inline int64_t temp_room(int64_t n) { return room_all_pow2(n, temp_bytes); }
 
 // workspace: key | sorted key | val | sorted val | heads | their inclusive sums | run starts | rocPRIM temporaries
 struct Layout {                  // byte offsets

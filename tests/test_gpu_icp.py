@@ -133,6 +133,22 @@ def test_a_point_just_past_max_dist_is_no_match():
     assert got[4].tolist() == [-1] and got[5].tolist() == [float('inf')] and got[2][0].tolist() == [0, 0, 0, 0, 0, 0]
 
 
+def test_the_last_cells_of_the_key_and_the_ones_past_them():
+    """tests/grid_edge.py: queries and dst points in the cells +-(2^18 - 2) of each axis match among themselves; those one cell
+    further out, within max_dist of them, take no part on either side (tests/test_grid_edge.py checks the cloud on the CPU)."""
+    import grid_edge as E
+    dst, inside, cluster = E.cloud()
+    src = dst + np.float32(0.0625)
+    E.check_cells(dst, inside, cluster)
+    E.check_cells(src, inside, cluster)
+    want = O.finish(src, dst, *O.IDENTITY, None, MD)
+    got = run(src, dst, iters=0)
+    match, dist2 = got[4].cpu().numpy(), got[5].cpu().numpy()
+    assert np.array_equal(match, want['match']) and np.array_equal(dist2.view(np.int32), want['dist2'].view(np.int32))
+    assert (match[~inside] == -1).all() and np.isposinf(dist2[~inside]).all()
+    assert (match[inside] >= 0).all() and (cluster[match[inside]] == cluster[inside]).all()    # no other edge, nothing from outside
+
+
 # ----------------------------------------------------------------------------- 2. one round
 def bars(src, dst, w, R0, t0, matched=None, what=''):
     """The restatement's round from the float32 motion (R0, t0) in both modes -> (o64, bar_R, bar_t, scale)."""

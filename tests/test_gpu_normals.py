@@ -112,6 +112,24 @@ def test_far_points_take_part_when_the_cells_are_large():
     assert np.array_equal(got[4].cpu().numpy().view(np.int32), want[2].view(np.int32))
 
 
+def test_the_last_cells_of_the_key_and_the_ones_past_them():
+    """tests/grid_edge.py: clusters in the cells +-(2^18 - 2) of each axis find each other and nothing else; the clusters one cell
+    further out, within the radius of them, take no part (tests/test_grid_edge.py checks the cloud on the CPU)."""
+    import grid_edge as E
+    pc, inside, cluster = E.cloud()
+    E.check_cells(pc, inside, cluster)
+    want = O.normals(pc, 8, 1.0)
+    normal, curv, count, nbr, nd2 = [x.cpu().numpy() for x in run(pc, k=8, radius=1.0)]
+    assert np.array_equal(count, want['count']) and np.array_equal(nbr, want['nbr'])
+    assert np.array_equal(nd2.view(np.int32), want['nbr_d2'].view(np.int32))
+    assert (count[inside] == 4).all() and (count[~inside] == 0).all()
+    assert (cluster[nbr[inside, :4]] == cluster[inside][:, None]).all()           # nothing from another edge, nothing from outside
+    assert (nbr[~inside] == -1).all() and (normal[:, ~inside] == 0).all() and (curv[~inside] == 0).all()
+    cmp_ = want['valid'] & (want['gap'] >= 1e-3)
+    assert np.array_equal(cmp_, inside)                                            # every inner point has a normal that stands apart
+    assert np.abs(normal.astype(np.float64) - want['normal'].astype(np.float64))[:, cmp_].max() <= BAR
+
+
 # ----------------------------------------------------------------------------- 2. normals and curvature
 _NORMALS = {}
 
