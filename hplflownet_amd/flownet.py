@@ -11,6 +11,7 @@ the reference forward by writes into column slices of one buffer per layer input
 Level L (0-based) hosts bcn{L+1} (Down, shared by both clouds), bcn{L+1}_ (Up) and, for
 L >= 2, corr{L-1}.
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -582,21 +583,76 @@ def load_reference_checkpoint(model, checkpoint, strict=True):
 
 
 # ----------------------------------------------------------------------------- rigid refinement
-def _pair_counts(lat_or_counts, total, who='rigid_refine'):
-    """Points per pair of a packed cloud of `total` points: from a lattice (a ragged one: its point_counts of cloud 1; an
-    equal batch: total / batch) or a sequence of counts."""
+def _prefix_of(counts):
+    """[0, c0, c0 + c1, ...]: where each cloud of a packed tensor starts, and the total."""
+    prefix = [0]
+    for c in counts:
+        prefix.append(prefix[-1] + int(c))
+    return prefix
+
+
+def _stated_counts(lat_or_counts, total=None, cloud=None):
+    """The points per pair that lat_or_counts states -- a ragged lattice: its point_counts (of the second cloud for cloud=1); an
+    equal batch's lattice: total / batch; a sequence of counts; with `cloud` given also a pair (counts of pc1, counts of pc2)
+    -- or None where it states none: None itself, and an equal batch's lattice without a total."""
     if lat_or_counts is None:
-        return [total]
+        return None
     if getattr(lat_or_counts, 'ragged', False):
-        counts = [int(c[0]) for c in lat_or_counts.point_counts]
-    elif hasattr(lat_or_counts, 'levels') or hasattr(lat_or_counts, 'batch'):
+        return [int(c[cloud or 0]) for c in lat_or_counts.point_counts]
+    if hasattr(lat_or_counts, 'levels') or hasattr(lat_or_counts, 'batch'):
         b = int(getattr(lat_or_counts, 'batch', 1) or 1)
-        counts = [total // b] * b
-    else:
-        counts = [int(c) for c in lat_or_counts]
+        return None if total is None else [total // b] * b
+    if cloud is not None and len(lat_or_counts) == 2 and all(isinstance(c, (list, tuple)) for c in lat_or_counts):
+        lat_or_counts = lat_or_counts[cloud]
+    return [int(c) for c in lat_or_counts]
+
+
+def _pair_counts(lat_or_counts, total, who='rigid_refine', cloud=None, what=''):
+    """Points per pair of a packed cloud of `total` points, as _stated_counts reads them (nothing stated: one pair); what:
+    ' of pc1', where the refusal has to say which cloud."""
+    counts = _stated_counts(lat_or_counts, total, cloud)
+    if counts is None:
+        return [total]
     if sum(counts) != total or any(c < 0 for c in counts):
-        raise _lib.HplError('%s: the point counts %s do not add up to %d points' % (who, counts, total))
+        raise _lib.HplError('%s: the point counts %s%s do not add up to %d points' % (who, counts, what, total))
     return counts
+
+
+def _cloud_forms(x, who, what, rows3=False):
+    """One cloud operand in the forms rigid_refine takes -> (clouds, form): the (3, N_b) views of its clouds, and form None for
+    a (B, 3, N) tensor, False for a (3, N) one -- one cloud, or a packed (3, sum N_b) one whose counts the caller knows --,
+    else a list's per-cloud flags (True: the entry came as (1, 3, N_b)).  rows3: every cloud must hold 3 rows here, and there
+    must be one (the callers that lay clouds side by side before an op sees them)."""
+    listed = isinstance(x, (list, tuple))
+    if listed:
+        form = [torch.is_tensor(c) and c.dim() == 3 for c in x]
+        clouds = [c[0] if lead else c for c, lead in zip(x, form)]
+    elif torch.is_tensor(x) and x.dim() == 3:
+        clouds, form = [x[b] for b in range(x.shape[0])], None
+    else:
+        clouds, form = [x], False
+    if (not clouds and (listed or rows3)) or any(not torch.is_tensor(c) or c.dim() != 2 or (rows3 and c.shape[0] != 3) for c in clouds):
+        raise _lib.HplError(('%s: %s is a tensor or a non-empty list of (3, N_b) tensors' if listed and not rows3 else
+                             '%s: %s is a (3, N) or (B, 3, N) tensor or a list of (3, N_b) tensors') % (who, what))
+    return clouds, form
+
+
+def _packed(x, clouds, form):
+    """The (3, sum N_b) cloud of an operand _cloud_forms read: the operand itself or a view where it holds one cloud, else one
+    copy."""
+    if form is None and len(clouds) != 1:
+        return x.transpose(0, 1).reshape(3, x.shape[0] * x.shape[2])
+    return clouds[0] if len(clouds) == 1 else torch.cat(clouds, dim=1)
+
+
+def _rows_as(rows, form, prefix):
+    """The [sum N_b, 3] rows of a per-point result in the form of an operand: (B, 3, N) (form None), (3, N) (False) or a list of
+    (3, N_b) / (1, 3, N_b) views (the flags of _cloud_forms)."""
+    if form is None:
+        return rows.view(len(prefix) - 1, prefix[1], 3).transpose(1, 2)
+    if form is False:
+        return rows.t()
+    return [rows[prefix[b]:prefix[b + 1]].t().unsqueeze(0) if lead else rows[prefix[b]:prefix[b + 1]].t() for b, lead in enumerate(form)]
 
 
 def _packed_rows(fls):
@@ -613,8 +669,9 @@ def _packed_rows(fls):
 
 def _packed_pairs(pc1, flow, lat_or_counts, who):
     """The packed operands of ops.rigid_fit / ops.motion_segment for the forms the models take and return (rigid_refine's
-    docstring lists them).  -> (pc (3, sum N_b), flow, prefix, counts, shape): shape None for a (B, 3, N) pair of tensors,
-    False for a packed pair, else the function that gives pair b's rows the form of flow[b]."""
+    docstring lists them).  -> (pc (3, sum N_b), flow, prefix, counts, form): the form of `flow` as _rows_as takes it -- None for a
+    (B, 3, N) pair of tensors, False for a packed pair, else the flags of a list.  (It reads its lists itself, not through
+    _cloud_forms: the flows are packed as rows, in place where they are a ragged forward's.)"""
     if isinstance(pc1, (list, tuple)) or isinstance(flow, (list, tuple)):
         if not isinstance(pc1, (list, tuple)) or not isinstance(flow, (list, tuple)) or len(pc1) != len(flow) or not pc1:
             raise _lib.HplError('%s: pc1 and flow are both lists of as many clouds, or both tensors' % who)
@@ -628,7 +685,7 @@ def _packed_pairs(pc1, flow, lat_or_counts, who):
         fl = fls[0] if len(fls) == 1 else _packed_rows(fls)
         if fl is None:
             fl = torch.cat([f.t() for f in fls], dim=0)
-        shape = lambda r, b: r.t().unsqueeze(0) if lead[b] else r.t()       # noqa: E731
+        shape = lead
     elif pc1.dim() == 3:
         B, _, n = pc1.shape
         if flow.dim() != 3 or flow.shape[0] != B:
@@ -640,10 +697,7 @@ def _packed_pairs(pc1, flow, lat_or_counts, who):
     else:
         counts = _pair_counts(lat_or_counts, int(pc1.shape[1]))
         pc, fl, shape = pc1, flow, False
-    prefix = [0]
-    for c in counts:
-        prefix.append(prefix[-1] + c)
-    return pc, fl, prefix, counts, shape
+    return pc, fl, _prefix_of(counts), counts, shape
 
 
 def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
@@ -659,38 +713,12 @@ def rigid_refine(pc1, flow, lat_or_counts=None, **kw):
     pc, fl, prefix, counts, shape = _packed_pairs(pc1, flow, lat_or_counts, 'rigid_refine')
     res = ops.rigid_fit(pc, fl, prefix=prefix, **kw)
     ref = res[3]
-    if shape is None:
-        ref = ref.view(len(counts), counts[0], 3).transpose(1, 2)
-    elif shape is False:
-        ref = ref.t() if tuple(flow.shape) == (3, ref.shape[0]) else ref
-    else:
-        ref = [shape(ref[prefix[b]:prefix[b + 1]], b) for b in range(len(counts))]
+    if shape is not False or tuple(flow.shape) == (3, ref.shape[0]):         # (a packed [N, 3] flow gets its rows as they are)
+        ref = _rows_as(ref, shape, prefix)
     return res[:3] + (ref,) + res[4:]
 
 
 # ----------------------------------------------------------------------------- rigid registration
-def _packed_cloud(pc, counts, who, what):
-    """One cloud operand of `who` in the forms rigid_refine takes -> (pc (3, sum N_b), counts, shape): shape None for a
-    (B, 3, N) tensor, False for a packed (3, sum N_b) one (its counts are `counts`, or one pair), else the per-pair flags of
-    a list (True: the entry came as (1, 3, N_b))."""
-    if isinstance(pc, (list, tuple)):
-        if not pc or not all(torch.is_tensor(p) and p.dim() in (2, 3) for p in pc):
-            raise _lib.HplError('%s: %s is a tensor or a non-empty list of (3, N_b) tensors' % (who, what))
-        lead = [p.dim() == 3 for p in pc]
-        pcs = [p[0] if p.dim() == 3 else p for p in pc]
-        return (pcs[0] if len(pcs) == 1 else torch.cat(pcs, dim=1)), [int(p.shape[1]) for p in pcs], lead
-    if not torch.is_tensor(pc) or pc.dim() not in (2, 3):
-        raise _lib.HplError('%s: %s is a (3, N) or (B, 3, N) tensor or a list of (3, N_b) tensors' % (who, what))
-    if pc.dim() == 3:
-        B, _, n = pc.shape
-        return (pc[0] if B == 1 else pc.transpose(0, 1).reshape(3, B * n)), [int(n)] * B, None
-    total = int(pc.shape[1])
-    counts = [total] if counts is None else [int(c) for c in counts]
-    if sum(counts) != total or any(c < 0 for c in counts):
-        raise _lib.HplError('%s: the point counts %s of %s do not add up to %d points' % (who, counts, what, total))
-    return pc, counts, False
-
-
 def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
     """The rigid registration of pc1 onto pc2 in ONE ops.icp call: per pair the motion (R, t) with
     R pc1 + t ~ pc2, from the clouds alone.  pc1 / pc2 in the forms rigid_refine takes, each on its own: a (B, 3, N) tensor
@@ -704,31 +732,19 @@ def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
     the origin.
     -> (R (B, 3, 3), t (B, 3), stats (B, 6), flow[, match, dist2]), flow = R p + t - p in the form of pc1: views of one
     [sum N_b, 3] tensor; match and dist2 stay packed."""
-    c1 = c2 = None
-    if lat_or_counts is not None:
-        if getattr(lat_or_counts, 'ragged', False):
-            c1, c2 = [int(c[0]) for c in lat_or_counts.point_counts], [int(c[1]) for c in lat_or_counts.point_counts]
-        elif hasattr(lat_or_counts, 'levels') or hasattr(lat_or_counts, 'batch'):
-            b = int(getattr(lat_or_counts, 'batch', 1) or 1)
-            c1 = c2 = b
-        elif len(lat_or_counts) == 2 and all(isinstance(c, (list, tuple)) for c in lat_or_counts):
-            c1, c2 = lat_or_counts
-        else:
-            c1 = c2 = list(lat_or_counts)
-
-    def counts_of(c, pc):                        # (an equal batch's lattice gives the number of pairs only)
-        return [int(pc.shape[1]) // c] * c if isinstance(c, int) and torch.is_tensor(pc) and pc.dim() == 2 else c
-    src, n1, shape = _packed_cloud(pc1, counts_of(c1, pc1), 'icp_register', 'pc1')
-    dst, n2, _ = _packed_cloud(pc2, counts_of(c2, pc2), 'icp_register', 'pc2')
+    read = []
+    for cloud, (pc, what) in enumerate(((pc1, 'pc1'), (pc2, 'pc2'))):
+        clouds, form = _cloud_forms(pc, 'icp_register', what)
+        n = _pair_counts(lat_or_counts, int(pc.shape[1]), 'icp_register', cloud, ' of %s' % what) if form is False else \
+            [int(c.shape[1]) for c in clouds]
+        read.append((_packed(pc, clouds, form), n, form))
+    (src, n1, shape), (dst, n2, shape2) = read
     if len(n1) != len(n2):
         raise _lib.HplError('icp_register: pc1 holds %d clouds, pc2 %d' % (len(n1), len(n2)))
-    for what, c, n in (('pc1', c1, n1), ('pc2', c2, n2)):
-        if c is not None and not isinstance(c, int) and [int(x) for x in c] != n:
+    for cloud, (what, n, form) in enumerate((('pc1', n1, shape), ('pc2', n2, shape2))):
+        if form is not False and _stated_counts(lat_or_counts, None, cloud) not in (None, n):
             raise _lib.HplError('icp_register: the clouds of %s hold %s points, the lattice or counts say otherwise' % (what, n))
-    sp, dp = [0], [0]
-    for a, b in zip(n1, n2):
-        sp.append(sp[-1] + a)
-        dp.append(dp[-1] + b)
+    sp, dp = _prefix_of(n1), _prefix_of(n2)
     metric, normals = kw.pop('metric', 'point'), kw.pop('normals', None)
     normals_k, normals_radius = kw.pop('normals_k', 16), kw.pop('normals_radius', None)
     if metric == 'plane':
@@ -741,14 +757,7 @@ def icp_register(pc1, pc2, lat_or_counts=None, init=None, **kw):
     elif metric != 'point' or normals is not None:
         raise _lib.HplError('icp_register: metric = %r (\'point\', or \'plane\' with normals (3, M) or None)' % (metric,))
     res = ops.icp(src, dst, init=init, src_prefix=sp, dst_prefix=dp, **kw)
-    fl = res[3]
-    if shape is None:
-        fl = fl.view(len(n1), n1[0], 3).transpose(1, 2)
-    elif shape is False:
-        fl = fl.t()
-    else:
-        fl = [fl[sp[b]:sp[b + 1]].t().unsqueeze(0) if shape[b] else fl[sp[b]:sp[b + 1]].t() for b in range(len(n1))]
-    return res[:3] + (fl,) + res[4:]
+    return res[:3] + (_rows_as(res[3], shape, sp),) + res[4:]
 
 
 # ----------------------------------------------------------------------------- surface normals
@@ -760,16 +769,12 @@ def estimate_normals(pc, lat_or_counts=None, k=16, radius=1.0, viewpoint=None):
     k, radius, viewpoint: of ops.normals (viewpoint: three numbers for every cloud, or B triples; None: the origin).
     -> (normal, curvature, count): normal in the form of pc -- (B, 3, N), (3, N) or a list of views of one (3, sum N_b)
     tensor --, curvature and count (B, N) for a (B, 3, N) tensor, else packed (sum N_b,)."""
-    counts = None
-    if torch.is_tensor(pc) and pc.dim() == 2 and lat_or_counts is not None:
-        counts = _pair_counts(lat_or_counts, int(pc.shape[1]), 'estimate_normals')
-    cloud, counts, shape = _packed_cloud(pc, counts, 'estimate_normals', 'pc')
-    if shape is not None and shape is not False and lat_or_counts is not None and \
-            _pair_counts(lat_or_counts, sum(counts), 'estimate_normals') != counts:
+    who = 'estimate_normals'
+    clouds, shape = _cloud_forms(pc, who, 'pc')
+    counts = _pair_counts(lat_or_counts, int(pc.shape[1]), who) if shape is False else [int(c.shape[1]) for c in clouds]
+    if shape and lat_or_counts is not None and _pair_counts(lat_or_counts, sum(counts), who) != counts:
         raise _lib.HplError('estimate_normals: the clouds hold %s points, the lattice or counts say otherwise' % (counts,))
-    prefix = [0]
-    for c in counts:
-        prefix.append(prefix[-1] + c)
+    cloud, prefix = _packed(pc, clouds, shape), _prefix_of(counts)
     normal, curvature, count = ops.normals(cloud, k=k, radius=radius, viewpoint=viewpoint, prefix=prefix)
     B = len(counts)
     if shape is None:
@@ -820,9 +825,7 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
         opc, ofl = pc[:, order].contiguous(), flt[:, order].contiguous()
         Rs, ts, sts = [], [], []
         for c in range(0, K, 64):
-            pre = [0]
-            for m in sizes[c:c + 64]:
-                pre.append(pre[-1] + m)
+            pre = _prefix_of(sizes[c:c + 64])
             lo = sum(sizes[:c])
             R, t, st, _ = ops.rigid_fit(opc[:, lo:lo + pre[-1]], ofl[:, lo:lo + pre[-1]], iters=iters, tau=tau, prefix=pre)
             Rs.append(R)
@@ -833,17 +836,53 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
 
 
 # ----------------------------------------------------------------------------- ground removal
+_Pairs = collections.namedtuple('_Pairs', 'c1 c2 fl joint clouds prefix')
+
+
 def _clouds(x, who, what):
-    """The (3, N_b) clouds of a (3, N) tensor, a (B, 3, N) tensor or a list of (3, N_b) / (1, 3, N_b) tensors."""
-    if isinstance(x, (list, tuple)):
-        out = [c[0] if torch.is_tensor(c) and c.dim() == 3 else c for c in x]
-    elif torch.is_tensor(x) and x.dim() == 3:
-        out = [x[b] for b in range(x.shape[0])]
-    else:
-        out = [x]
-    if not out or any(not torch.is_tensor(c) or c.dim() != 2 or c.shape[0] != 3 for c in out):
-        raise _lib.HplError('%s: %s is a (3, N) or (B, 3, N) tensor or a list of (3, N_b) tensors' % (who, what))
-    return out
+    return _cloud_forms(x, who, what, True)[0]
+
+
+def _pairs_in(who, pc1, pc2, sf, corr):
+    """The operands of voxel_downsample and fps_sample, in the forms remove_ground takes (pc2 and sf may be None) -> _Pairs: the
+    clouds c1, c2, fl of each; joint: the pairs stay pairs (corr, or no pc2; at most 64), else the op runs over the 2 B clouds
+    c1 + c2 (at most 32 pairs); clouds: those it runs over, and their prefix."""
+    c1 = _clouds(pc1, who, 'pc1')
+    c2 = _clouds(pc2, who, 'pc2') if pc2 is not None else None
+    fl = _clouds(sf, who, 'sf') if sf is not None else None
+    B = len(c1)
+    if (c2 is not None and len(c2) != B) or (fl is not None and (len(fl) != B or any(f.shape[1] != c.shape[1] for f, c in zip(fl, c1)))):
+        raise _lib.HplError('%s: pc1, pc2 and sf hold as many clouds, and sf as many points as pc1' % who)
+    joint = corr or c2 is None
+    if corr and c2 is not None and any(a.shape[1] != b.shape[1] for a, b in zip(c1, c2)):
+        raise _lib.HplError('%s: corr=True takes clouds that correspond point to point (as many points in pc1 and pc2)' % who)
+    if not 1 <= (B if joint else 2 * B) <= 64:
+        raise _lib.HplError('%s: %d pairs (1 .. %d a call)' % (who, B, 64 if joint else 32))
+    clouds = c1 if joint else c1 + c2
+    return _Pairs(c1, c2, fl, joint, clouds, _prefix_of(c.shape[1] for c in clouds))
+
+
+def _pairs_packed(p):
+    """(the packed cloud, attrs) of _pairs_in's operands: what rides with pc1's points -- pc2 when the pairs stay pairs, and sf
+    (zero over the pc2 clouds where those are clouds of their own) -- as attribute channels, or None."""
+    pc = torch.cat(p.clouds, dim=1)
+    riders = []
+    if p.joint and p.c2 is not None:
+        riders.append(torch.cat(p.c2, dim=1))
+    if p.fl is not None:
+        f = torch.cat(p.fl, dim=1)
+        riders.append(f if p.joint else torch.cat([f, f.new_zeros((3, p.prefix[-1] - p.prefix[len(p.c1)]))], dim=1))
+    return pc, torch.cat(riders, dim=0) if riders else None
+
+
+def _pairs_out(p, out_pc, out_attrs, stats, spans):
+    """(pc1 list, pc2 list or None, sf list or None, stats) of the op's outputs: spans[i] = the columns (first, end) that hold
+    the results of p.clouds[i]."""
+    B = len(p.c1)
+    cols = [out_pc[:, a:b] for a, b in spans]
+    o2 = None if p.c2 is None else cols[B:] if not p.joint else [out_attrs[:3, a:b] for a, b in spans[:B]]
+    of = None if p.fl is None else [out_attrs[out_attrs.shape[0] - 3:, a:b] for a, b in spans[:B]]
+    return cols[:B], o2, of, stats if p.joint else stats.view(2, B, 4)
 
 
 def remove_ground(pc1, pc2, sf=None, corr=True, return_mask=False, **kw):
@@ -871,9 +910,7 @@ def remove_ground(pc1, pc2, sf=None, corr=True, return_mask=False, **kw):
         raise _lib.HplError('%s: return_mask comes with corr=True' % who)
     if not 1 <= 2 * B <= 64:
         raise _lib.HplError('%s: %d pairs (1 .. 32 a call)' % (who, B))
-    prefix = [0]
-    for c in c1 + c2:
-        prefix.append(prefix[-1] + int(c.shape[1]))
+    prefix = _prefix_of(c.shape[1] for c in c1 + c2)
     pc = torch.cat(c1 + c2, dim=1)
     plane, stats, ground, keep = ops.ground_fit(pc, prefix=prefix, **kw)
     n1 = prefix[B]
@@ -919,43 +956,15 @@ def voxel_downsample(pc1, pc2=None, sf=None, voxel=0.1, mode='centroid', corr=Tr
     int64, the member nearest to the mean as an index into the cloud."""
     who = 'voxel_downsample'
     ops.voxel_args(who, voxel, origin, mode)
-    c1 = _clouds(pc1, who, 'pc1')
-    c2 = _clouds(pc2, who, 'pc2') if pc2 is not None else None
-    fl = _clouds(sf, who, 'sf') if sf is not None else None
-    B = len(c1)
-    if (c2 is not None and len(c2) != B) or (fl is not None and (len(fl) != B or any(f.shape[1] != c.shape[1] for f, c in zip(fl, c1)))):
-        raise _lib.HplError('%s: pc1, pc2 and sf hold as many clouds, and sf as many points as pc1' % who)
-    joint = corr or c2 is None
-    if corr and c2 is not None and any(a.shape[1] != b.shape[1] for a, b in zip(c1, c2)):
-        raise _lib.HplError('%s: corr=True takes clouds that correspond point to point (as many points in pc1 and pc2)' % who)
-    if not 1 <= (B if joint else 2 * B) <= 64:
-        raise _lib.HplError('%s: %d pairs (1 .. %d a call)' % (who, B, 64 if joint else 32))
-    clouds = c1 if joint else c1 + c2
-    prefix = [0]
-    for c in clouds:
-        prefix.append(prefix[-1] + int(c.shape[1]))
-    pc = torch.cat(clouds, dim=1)
-    n1 = prefix[B]
-    riders = []
-    if joint and c2 is not None:
-        riders.append(torch.cat(c2, dim=1))
-    if fl is not None:
-        f = torch.cat(fl, dim=1)
-        riders.append(f if joint else torch.cat([f, f.new_zeros((3, prefix[-1] - n1))], dim=1))
-    attrs = torch.cat(riders, dim=0) if riders else None
+    p = _pairs_in(who, pc1, pc2, sf, corr)
+    pc, attrs = _pairs_packed(p)
+    prefix = p.prefix
     out_pc, out_attrs, _, rep, voxel_of, stats = ops.voxel_downsample(pc, attrs, voxel=voxel, origin=origin, mode=mode, prefix=prefix)
     V = stats[:, 0].cpu().tolist()                                              # the one read-back
-    cols = [out_pc[:, prefix[b]:prefix[b] + V[b]] for b in range(len(clouds))]
-    o1 = cols[:B]
-    o2 = None if c2 is None else cols[B:] if not joint else [out_attrs[:3, prefix[b]:prefix[b] + V[b]] for b in range(B)]
-    of = None
-    if fl is not None:
-        r0 = out_attrs.shape[0] - 3
-        of = [out_attrs[r0:, prefix[b]:prefix[b] + V[b]] for b in range(B)]
-    res = (o1, o2, of, stats if joint else stats.view(2, B, 4))
+    res = _pairs_out(p, out_pc, out_attrs, stats, [(prefix[b], prefix[b] + V[b]) for b in range(len(p.clouds))])
     if return_index:
         vo, rp = [], []
-        for b in range(len(clouds)):
+        for b in range(len(p.clouds)):
             w = voxel_of[prefix[b]:prefix[b + 1]].long()
             vo.append(torch.where(w >= 0, w - prefix[b], w))
             rp.append(rep[prefix[b]:prefix[b] + V[b]].long() - prefix[b])
@@ -978,18 +987,8 @@ def fps_sample(pc1, pc2=None, sf=None, num_points=8192, corr=True, start=None, s
     -> (pc1 list of (3, count_b), pc2 list or None, sf list or None, stats (B, 4) int32 -- corr=False with pc2: (2, B, 4) --
     [, idx list]): return_index appends, per sampled cloud, idx (count_b,) int64 into the cloud, in selection order."""
     who = 'fps_sample'
-    c1 = _clouds(pc1, who, 'pc1')
-    c2 = _clouds(pc2, who, 'pc2') if pc2 is not None else None
-    fl = _clouds(sf, who, 'sf') if sf is not None else None
-    B = len(c1)
-    if (c2 is not None and len(c2) != B) or (fl is not None and (len(fl) != B or any(f.shape[1] != c.shape[1] for f, c in zip(fl, c1)))):
-        raise _lib.HplError('%s: pc1, pc2 and sf hold as many clouds, and sf as many points as pc1' % who)
-    joint = corr or c2 is None
-    if corr and c2 is not None and any(a.shape[1] != b.shape[1] for a, b in zip(c1, c2)):
-        raise _lib.HplError('%s: corr=True takes clouds that correspond point to point (as many points in pc1 and pc2)' % who)
-    if not 1 <= (B if joint else 2 * B) <= 64:
-        raise _lib.HplError('%s: %d pairs (1 .. %d a call)' % (who, B, 64 if joint else 32))
-    clouds = c1 if joint else c1 + c2
+    p = _pairs_in(who, pc1, pc2, sf, corr)
+    clouds = p.clouds
     ops.fps_args(who, num_points, len(clouds))
     if start is not None and seed is not None:
         raise _lib.HplError('%s: start and seed together (give one)' % who)
@@ -1000,29 +999,11 @@ def fps_sample(pc1, pc2=None, sf=None, num_points=8192, corr=True, start=None, s
             raise _lib.HplError('%s: seed = %r (an int in 0 .. 2^32 - 1)' % (who, seed))
         rs = np.random.RandomState(seed)
         start = [int(rs.randint(0, n)) if n > 0 else 0 for n in sizes]
-    prefix = [0]
-    for n in sizes:
-        prefix.append(prefix[-1] + n)
-    pc = torch.cat(clouds, dim=1)
-    n1 = prefix[B]
-    riders = []
-    if joint and c2 is not None:
-        riders.append(torch.cat(c2, dim=1))
-    if fl is not None:
-        f = torch.cat(fl, dim=1)
-        riders.append(f if joint else torch.cat([f, f.new_zeros((3, prefix[-1] - n1))], dim=1))
-    attrs = torch.cat(riders, dim=0) if riders else None
-    out_pc, out_attrs, idx, _, _, stats = ops.fps(pc, num_points, attrs, start=start, prefix=prefix)
+    pc, attrs = _pairs_packed(p)
+    out_pc, out_attrs, idx, _, _, stats = ops.fps(pc, num_points, attrs, start=start, prefix=p.prefix)
     K = stats[:, 0].cpu().tolist()                                              # the one read-back
     m = num_points
-    cols = [out_pc[:, b * m:b * m + K[b]] for b in range(len(clouds))]
-    o1 = cols[:B]
-    o2 = None if c2 is None else cols[B:] if not joint else [out_attrs[:3, b * m:b * m + K[b]] for b in range(B)]
-    of = None
-    if fl is not None:
-        r0 = out_attrs.shape[0] - 3
-        of = [out_attrs[r0:, b * m:b * m + K[b]] for b in range(B)]
-    res = (o1, o2, of, stats if joint else stats.view(2, B, 4))
+    res = _pairs_out(p, out_pc, out_attrs, stats, [(b * m, b * m + K[b]) for b in range(len(clouds))])
     if return_index:
         res += ([idx[b, :K[b]].long() for b in range(len(clouds))],)
     return res
@@ -1119,10 +1100,7 @@ def selfsup_loss(flow, pc1, pc2, k=8, w_chamfer=1.0, w_smooth=1.0):
         q = pc2[0] if B == 1 else pc2.transpose(0, 1).reshape(3, B * counts2[0])
     else:
         counts2, q = [int(pc2.shape[1])], pc2
-    prefix2 = [0]
-    for c in counts2:
-        prefix2.append(prefix2[-1] + c)
-    L, comps = ops.SelfSupLossFn.apply(fl, pc, q, k, w_chamfer, w_smooth, prefix1, prefix2)
+    L, comps = ops.SelfSupLossFn.apply(fl, pc, q, k, w_chamfer, w_smooth, prefix1, _prefix_of(counts2))
     return L.mean(), comps
 
 
@@ -1159,10 +1137,7 @@ class DenseState(object):
                 counts = [n] * B
                 packed = (pc1.reshape(1, 3, n) if B == 1 else pc1).transpose(0, 1).reshape(3, B * n).clone()
                 rows = flow.transpose(1, 2).reshape(B * n, 3).clone()
-            prefix = [0]
-            for c in counts:
-                prefix.append(prefix[-1] + c)
-            self._fill = (packed.contiguous(), rows.contiguous(), prefix)
+            self._fill = (packed.contiguous(), rows.contiguous(), _prefix_of(counts))
             self._pc1 = self._flow = None
         return self._fill
 
@@ -1252,9 +1227,7 @@ class DenseFlow(object):
                 raise _lib.HplError('every query cloud is a (3, Q) float32 tensor on %s' % dev)
         counts = [int(t.shape[1]) for t in qs]
         Q = sum(counts)
-        prefix = [0]
-        for c in counts:
-            prefix.append(prefix[-1] + c)
+        prefix = _prefix_of(counts)
         qcat = (qs[0] if len(qs) == 1 else torch.cat(qs, dim=1)).contiguous()
         qflow = torch.empty((Q, 3), dtype=torch.float32, device=dev)
         cov = torch.empty((Q,), dtype=torch.float32, device=dev)

@@ -7,7 +7,10 @@ row stride may exceed the channel count: column slices of wider buffers are fine
 """
 import collections
 import ctypes
+import math
+import operator
 import os
+import struct
 
 import torch
 
@@ -376,7 +379,7 @@ def _soa3(x, what, op='knn_interpolate'):
     n = x.shape[1]
     if x.stride(0) < max(n, 1) or (n > 1 and x.stride(1) != 1):
         x = x.contiguous()           # (after which a row starts max(n, 1) elements behind the previous one)
-    return x, max(n, 1) if x.is_contiguous() else x.stride(0)
+    return x, _soa_ld(x, n)
 
 
 def _int_in(who, name, v, lo, hi):
@@ -389,7 +392,7 @@ def _int_in(who, name, v, lo, hi):
 def _prefix(prefix, n, who, what='the prefix'):
     """The host list of B + 1 <= 65 non-decreasing ints from 0 to n (None: one pair)."""
     pp = [0, n] if prefix is None else [int(x) for x in prefix]
-    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != n or any(b < a for a, b in zip(pp, pp[1:])):
+    if len(pp) < 2 or len(pp) > 65 or pp[0] != 0 or pp[-1] != n or pp != sorted(pp):
         raise _lib.HplError('%s: %s holds B + 1 <= 65 non-decreasing entries from 0 to %d, got %s' % (who, what, n, pp))
     return pp
 
@@ -415,15 +418,110 @@ def _flow_view(flow, N, dev, who, raw_op_hint=None):
 _WORKSPACES = {}
 
 
-def _workspace(op, device, st, nbytes):
-    """Per-(op, device, stream) scratch, one buffer per size class (the next power of two): a call on another stream never
-    shares the partial sums of one in flight."""
-    size = 1 << max(12, int(nbytes - 1).bit_length())
-    key = (op, device, st, size)
+def _room(who, dev, nbytes, limits, *counts):
+    """(workspace, stream) of a launch on the current stream; nbytes: the answer of the op's hpl_*_workspace_bytes, negative
+    when the counts are outside the limits -- `limits % counts` says which.  The scratch is per (op, device, stream), one
+    buffer per size class (the next power of two): a call on another stream never shares the partial sums of one in flight."""
+    if nbytes < 0:
+        raise _lib.HplError('%s: %s' % (who, limits % counts))
+    st = stream()
+    size = 1 << max(12, (nbytes - 1).bit_length())
+    key = (who, dev, st, size)
     ws = _WORKSPACES.get(key)
     if ws is None:
-        ws = _WORKSPACES[key] = torch.empty(size, dtype=torch.uint8, device=device)
-    return ws
+        ws = _WORKSPACES[key] = torch.empty(size, dtype=torch.uint8, device=dev)
+    return ws, st
+
+
+_INF = float('inf')
+
+
+def _scalar(who, name, v, zero_ok=False, inf_ok=False):
+    """v as a float when it is finite and > 0 (zero_ok: >= 0; inf_ok: any value > 0, +inf too); what is no number counts as NaN."""
+    try:
+        v = float(v)
+    except (TypeError, ValueError):
+        v = float('nan')
+    if not ((v >= 0 if zero_ok else v > 0) and (inf_ok or v < _INF)):
+        raise _lib.HplError('%s: %s = %r (%s %s 0)' % (who, name, v, 'any value' if inf_ok else 'finite and', '>=' if zero_ok else '>'))
+    return v
+
+
+def _vector(who, name, t, n, dev):
+    """An (n,) float32 tensor on dev without grad, contiguous."""
+    if not torch.is_tensor(t) or tuple(t.shape) != (n,) or t.dtype != torch.float32 or t.device != dev or t.requires_grad:
+        raise _lib.HplError('%s: %s must be a (%d,) float32 tensor on %s without grad' % (who, name, n, dev))
+    return t.contiguous()
+
+
+def _attrs(who, attrs, n, dev):
+    """(attrs, C, row stride) of the (C, n) float32 channels, 1 <= C <= 8, that ride with a cloud's points (rows may be views
+    of a wider buffer); None: (None, 0, 0)."""
+    if attrs is None:
+        return None, 0, 0
+    if not torch.is_tensor(attrs) or attrs.dim() != 2 or attrs.shape[1] != n or attrs.dtype != torch.float32 or \
+            attrs.device != dev or not 1 <= attrs.shape[0] <= 8:
+        raise _lib.HplError('%s: attrs must be a (C, %d) float32 tensor on %s with 1 <= C <= 8, got %s' % (
+            who, n, dev, (tuple(attrs.shape), attrs.dtype, attrs.device) if torch.is_tensor(attrs) else type(attrs)))
+    if attrs.requires_grad:
+        raise _lib.HplError('%s has no autograd: attrs requires grad' % who)
+    C = attrs.shape[0]
+    if (C > 1 and attrs.stride(0) < max(n, 1)) or (n > 1 and attrs.stride(1) != 1):
+        attrs = attrs.contiguous()
+    return attrs, C, max(n, 1) if C == 1 or attrs.is_contiguous() else attrs.stride(0)
+
+
+def _rows_out(who, out, n, dev):
+    """`out` as the contiguous [n, 3] float32 tensor on dev that takes a per-point result (None: a new one)."""
+    if out is None:
+        return torch.empty((n, 3), dtype=torch.float32, device=dev)
+    if not torch.is_tensor(out) or tuple(out.shape) != (n, 3) or out.dtype != torch.float32 or out.device != dev or \
+            not out.is_contiguous() or out.requires_grad:
+        raise _lib.HplError('%s: out must be a contiguous (%d, 3) float32 tensor on %s' % (who, n, dev))
+    return out
+
+
+def _soa_ok(o, n, dev):
+    return torch.is_tensor(o) and tuple(o.shape) == (3, n) and o.dtype == torch.float32 and o.device == dev and \
+        not o.requires_grad and o.stride(0) >= max(n, 1) and (n <= 1 or o.stride(1) == 1)
+
+
+def _soa_ld(x, n):
+    """The row stride of a (3, n) tensor that _soa3 or _soa_ok passed: max(n, 1) for a contiguous one, else its stride(0) --
+    which is a contiguous one's stride(0) too whenever n >= 1."""
+    return max(n, 1) if x.is_contiguous() else x.stride(0)
+
+
+def _soa_out(who, out, n, dev, along):
+    """(out, row stride): `out` as a (3, n) float32 tensor on dev with unit stride along `along` (rows may be views of a wider
+    buffer; None: a new one)."""
+    if out is None:
+        return torch.empty((3, n), dtype=torch.float32, device=dev), max(n, 1)
+    if not _soa_ok(out, n, dev):
+        raise _lib.HplError('%s: out must be a (3, %d) float32 tensor on %s with unit stride along %s' % (who, n, dev, along))
+    return out, _soa_ld(out, n)
+
+
+_PAIR_LIMITS = '%d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)'
+_CLOUD_LIMITS = '%d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)'
+
+
+_I64_ARRAYS = {}
+
+
+def _c_prefix(pp):
+    """A host prefix as the int64 array the library takes (the array types are made once a length)."""
+    t = _I64_ARRAYS.get(len(pp))
+    if t is None:
+        t = _I64_ARRAYS[len(pp)] = ctypes.c_int64 * len(pp)
+    return t(*pp)
+
+
+def _identity_rt(B, dev):
+    """The (B, 12) rows (R | t) of B identities: what a fit of empty pairs returns."""
+    Rt = torch.zeros((B, 12), dtype=torch.float32, device=dev)
+    Rt[:, 0:9:4] = 1.0
+    return Rt
 
 
 def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=None, return_neighbors=False, out=None,
@@ -474,7 +572,7 @@ def knn_interpolate(ref, values, q, k=3, eps=1e-8, ref_prefix=None, q_prefix=Non
     if Q == 0:
         return (out, idx, dist2) if return_neighbors else out
     check(_lib.load().hpl_knn_interp(ref.data_ptr(), ref_ld, values.data_ptr(), C, q.data_ptr(), q_ld, k, float(eps), B,
-                                     (ctypes.c_int64 * (B + 1))(*rp), (ctypes.c_int64 * (B + 1))(*qp), ptr(idx), ptr(dist2),
+                                     _c_prefix(rp), _c_prefix(qp), ptr(idx), ptr(dist2),
                                      out.data_ptr(), ptr(coverage), stream()), 'hpl_knn_interp')
     return (out, idx, dist2) if return_neighbors else out
 
@@ -492,54 +590,32 @@ def rigid_fit(pc, flow, weight=None, iters=4, tau=0.1, prefix=None, return_resid
     flow bit for bit.  status 0 (fewer than 3 points, or no weight): R = I, t = 0, refined = flow.  out: a contiguous [N, 3]
     float32 tensor that takes the refined flow (it must not overlap flow).  No autograd, no host synchronisation."""
     _int_in('rigid_fit', 'iters', iters, 0, 16)
-    tau = float(tau)
-    if not (tau > 0 and tau < float('inf')):
-        raise _lib.HplError('rigid_fit: tau = %r (finite and > 0)' % (tau,))
+    tau = _scalar('rigid_fit', 'tau', tau)
     pc, pc_ld = _soa3(pc, 'pc', 'rigid_fit')
     N, dev = pc.shape[1], pc.device
     flow = _flow_view(flow, N, dev, 'rigid_fit')
     if weight is not None:
-        if not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32 or weight.device != dev \
-                or weight.requires_grad:
-            raise _lib.HplError('rigid_fit: weight must be a (%d,) float32 tensor on %s without grad' % (N, dev))
-        weight = weight.contiguous()
+        weight = _vector('rigid_fit', 'weight', weight, N, dev)
     pp = _prefix(prefix, N, 'rigid_fit')
     B = len(pp) - 1
-    if out is not None:
-        if not torch.is_tensor(out) or tuple(out.shape) != (N, 3) or out.dtype != torch.float32 or out.device != dev or \
-                not out.is_contiguous() or out.requires_grad:
-            raise _lib.HplError('rigid_fit: out must be a contiguous (%d, 3) float32 tensor on %s' % (N, dev))
-    else:
-        out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    out = _rows_out('rigid_fit', out, N, dev)
     residual = torch.empty(N, dtype=torch.float32, device=dev) if return_residual else None
     lib = _lib.load()
     if N == 0:                                   # nothing to launch: every pair is empty
-        Rt = torch.zeros((B, 12), dtype=torch.float32, device=dev)
-        Rt[:, 0:9:4] = 1.0
+        Rt = _identity_rt(B, dev)
         stats = torch.zeros((B, 4), dtype=torch.float32, device=dev)
     else:
         Rt = torch.empty((B, 12), dtype=torch.float32, device=dev)
         stats = torch.empty((B, 4), dtype=torch.float32, device=dev)
-        nbytes = lib.hpl_rigid_fit_workspace_bytes(B, N)
-        if nbytes < 0:
-            raise _lib.HplError('rigid_fit: %d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)' % (B, N))
-        st = stream()
-        ws = _workspace('rigid_fit', dev, st, nbytes)
+        ws, st = _room('rigid_fit', dev, lib.hpl_rigid_fit_workspace_bytes(B, N), _PAIR_LIMITS, B, N)
         check(lib.hpl_rigid_fit(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), ptr(weight), B,
-                                (ctypes.c_int64 * (B + 1))(*pp), iters, tau, Rt.data_ptr(), stats.data_ptr(), ptr(residual),
+                                _c_prefix(pp), iters, tau, Rt.data_ptr(), stats.data_ptr(), ptr(residual),
                                 out.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_rigid_fit')
     res = (Rt[:, :9].view(B, 3, 3), Rt[:, 9:], stats, out)
     return res + (residual,) if return_residual else res
 
 
 # --------------------------------------------------------------------------- rigid registration of a cloud pair
-def _icp_scalar(name, v, zero_ok=False):
-    v = float(v)
-    if not ((v >= 0 if zero_ok else v > 0) and v < float('inf')):
-        raise _lib.HplError('icp: %s = %r (finite and %s 0)' % (name, v, '>=' if zero_ok else '>'))
-    return v
-
-
 def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_rot=0.0, tol_trans=0.0, src_prefix=None,
         dst_prefix=None, return_matches=False, out=None, metric='point', dst_normal=None):
     """hpl_icp on the current stream: per pair the rigid motion q = R p + t that lays src (3, N) onto dst (3, M)
@@ -562,8 +638,8 @@ def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_r
     if (metric == 'plane') != (dst_normal is not None):
         raise _lib.HplError('icp: metric \'plane\' takes dst_normal (3, M), metric \'point\' takes none')
     _int_in('icp', 'iters', iters, 0, 64)
-    max_dist, tau = _icp_scalar('max_dist', max_dist), _icp_scalar('tau', tau)
-    tol_rot, tol_trans = _icp_scalar('tol_rot', tol_rot, True), _icp_scalar('tol_trans', tol_trans, True)
+    max_dist, tau = _scalar('icp', 'max_dist', max_dist), _scalar('icp', 'tau', tau)
+    tol_rot, tol_trans = _scalar('icp', 'tol_rot', tol_rot, True), _scalar('icp', 'tol_trans', tol_trans, True)
     src, src_ld = _soa3(src, 'src', 'icp')
     dst, dst_ld = _soa3(dst, 'dst', 'icp')
     N, M, dev = src.shape[1], dst.shape[1], src.device
@@ -574,10 +650,7 @@ def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_r
         if dst_normal.shape[1] != M or dst_normal.device != dev:
             raise _lib.HplError('icp: dst_normal must be a (3, %d) float32 tensor on %s' % (M, dev))
     if weight is not None:
-        if not torch.is_tensor(weight) or tuple(weight.shape) != (N,) or weight.dtype != torch.float32 or weight.device != dev \
-                or weight.requires_grad:
-            raise _lib.HplError('icp: weight must be a (%d,) float32 tensor on %s without grad' % (N, dev))
-        weight = weight.contiguous()
+        weight = _vector('icp', 'weight', weight, N, dev)
     sp = _prefix(src_prefix, N, 'icp', 'the prefix of src')
     dp = _prefix(dst_prefix, M, 'icp', 'the prefix of dst')
     if len(sp) != len(dp):
@@ -591,32 +664,20 @@ def icp(src, dst, weight=None, init=None, iters=30, max_dist=1.0, tau=0.3, tol_r
                     t_.requires_grad:
                 raise _lib.HplError('icp: init is a pair (R (%d, 3, 3), t (%d, 3)) of float32 tensors on %s without grad' % (B, B, dev))
         init = torch.cat([init[0].reshape(B, 9), init[1]], dim=1).contiguous()
-    if out is not None:
-        if not torch.is_tensor(out) or tuple(out.shape) != (N, 3) or out.dtype != torch.float32 or out.device != dev or \
-                not out.is_contiguous() or out.requires_grad:
-            raise _lib.HplError('icp: out must be a contiguous (%d, 3) float32 tensor on %s' % (N, dev))
-    else:
-        out = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    out = _rows_out('icp', out, N, dev)
     match = torch.empty(N, dtype=torch.int32, device=dev) if return_matches else None
     dist2 = torch.empty(N, dtype=torch.float32, device=dev) if return_matches else None
     lib = _lib.load()
     if N == 0:                                   # nothing to launch: every src cloud is empty
-        if init is None:
-            Rt = torch.zeros((B, 12), dtype=torch.float32, device=dev)
-            Rt[:, 0:9:4] = 1.0
-        else:
-            Rt = init
+        Rt = _identity_rt(B, dev) if init is None else init
         stats = torch.zeros((B, 6), dtype=torch.float32, device=dev)
     else:
         Rt = torch.empty((B, 12), dtype=torch.float32, device=dev)
         stats = torch.empty((B, 6), dtype=torch.float32, device=dev)
         nbytes = (lib.hpl_icp_plane_workspace_bytes if metric == 'plane' else lib.hpl_icp_workspace_bytes)(B, N, M)
-        if nbytes < 0:
-            raise _lib.HplError('icp: %d pairs of %d and %d points together are outside the limits (64 pairs, N, M < 2^31 / 3)'
-                                % (B, N, M))
-        st = stream()
-        ws = _workspace('icp', dev, st, nbytes)
-        tail = (ptr(weight), ptr(init), B, (ctypes.c_int64 * (B + 1))(*sp), (ctypes.c_int64 * (B + 1))(*dp), iters, max_dist, tau,
+        ws, st = _room('icp', dev, nbytes, '%d pairs of %d and %d points together are outside the limits (64 pairs, N, M < 2^31 / 3)',
+                       B, N, M)
+        tail = (ptr(weight), ptr(init), B, _c_prefix(sp), _c_prefix(dp), iters, max_dist, tau,
                 tol_rot, tol_trans, Rt.data_ptr(), stats.data_ptr(), ptr(match), ptr(dist2), out.data_ptr(), ws.data_ptr(),
                 ws.numel(), st)
         if metric == 'plane':
@@ -641,9 +702,7 @@ def normals(pc, k=16, radius=1.0, viewpoint=None, prefix=None, return_neighbors=
     tensor with unit stride along its points (rows may be views of a wider buffer) that takes the normal.  No autograd, no host
     synchronisation."""
     _int_in('normals', 'k', k, 3, 32)
-    radius = float(radius)
-    if not (radius > 0 and radius < float('inf')):
-        raise _lib.HplError('normals: radius = %r (finite and > 0)' % (radius,))
+    radius = _scalar('normals', 'radius', radius)
     pc, pc_ld = _soa3(pc, 'pc', 'normals')
     N, dev = pc.shape[1], pc.device
     pp = _prefix(prefix, N, 'normals')
@@ -659,25 +718,16 @@ def normals(pc, k=16, radius=1.0, viewpoint=None, prefix=None, return_neighbors=
         if len(v) != 3 * B:
             raise _lib.HplError('normals: viewpoint holds three numbers or %d triples, got %r' % (B, viewpoint))
         view = (ctypes.c_float * (3 * B))(*v)
-    if out is not None:
-        if not torch.is_tensor(out) or tuple(out.shape) != (3, N) or out.dtype != torch.float32 or out.device != dev or \
-                out.requires_grad or (N > 1 and out.stride(1) != 1) or out.stride(0) < max(N, 1):
-            raise _lib.HplError('normals: out must be a (3, %d) float32 tensor on %s with unit stride along its points' % (N, dev))
-    else:
-        out = torch.empty((3, N), dtype=torch.float32, device=dev)
+    out, out_ld = _soa_out('normals', out, N, dev, 'its points')
     curvature = torch.empty(N, dtype=torch.float32, device=dev)
     count = torch.empty(N, dtype=torch.int32, device=dev)
     nbr = torch.empty((N, k), dtype=torch.int32, device=dev) if return_neighbors else None
     nbr_d2 = torch.empty((N, k), dtype=torch.float32, device=dev) if return_neighbors else None
     if N > 0:
         lib = _lib.load()
-        nbytes = lib.hpl_normals_workspace_bytes(B, N)
-        if nbytes < 0:
-            raise _lib.HplError('normals: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (B, N))
-        st = stream()
-        ws = _workspace('normals', dev, st, nbytes)
-        check(lib.hpl_normals(pc.data_ptr(), pc_ld, B, (ctypes.c_int64 * (B + 1))(*pp), k, radius, view, out.data_ptr(),
-                              out.stride(0), ptr(curvature), ptr(count), ptr(nbr), ptr(nbr_d2), ws.data_ptr(), ws.numel(), st),
+        ws, st = _room('normals', dev, lib.hpl_normals_workspace_bytes(B, N), _CLOUD_LIMITS, B, N)
+        check(lib.hpl_normals(pc.data_ptr(), pc_ld, B, _c_prefix(pp), k, radius, view, out.data_ptr(),
+                              out_ld, ptr(curvature), ptr(count), ptr(nbr), ptr(nbr_d2), ws.data_ptr(), ws.numel(), st),
               'hpl_normals')
     res = (out, curvature, count)
     return res + (nbr, nbr_d2) if return_neighbors else res
@@ -695,24 +745,14 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
     flow, unused rows 0; stats (B, 4) int32: movers, objects -- the true count, also past max_objects --, points in objects,
     points out of range).  out: a contiguous (N,) int32 tensor that takes the labels.  The same bits for a pair alone and in
     any batch.  No autograd, no host synchronisation, no read-back."""
-    def scalar(v, name, inf_ok=False):
-        try:
-            v = float(v)
-        except (TypeError, ValueError):
-            v = float('nan')
-        if not (v > 0 and (inf_ok or v < float('inf'))):
-            raise _lib.HplError('motion_segment: %s = %r (%s > 0)' % (name, v, 'any value' if inf_ok else 'finite and'))
-        return v
-    tau, eps, dv = scalar(tau, 'tau'), scalar(eps, 'eps'), scalar(dv, 'dv', True)
+    tau, eps = _scalar('motion_segment', 'tau', tau), _scalar('motion_segment', 'eps', eps)
+    dv = _scalar('motion_segment', 'dv', dv, inf_ok=True)
     _int_in('motion_segment', 'min_points', min_points, 1, 2 ** 31 - 1)
     _int_in('motion_segment', 'max_objects', max_objects, 1, 4096)
     pc, pc_ld = _soa3(pc, 'pc', 'motion_segment')
     N, dev = pc.shape[1], pc.device
     flow = _flow_view(flow, N, dev, 'motion_segment')
-    if not torch.is_tensor(residual) or tuple(residual.shape) != (N,) or residual.dtype != torch.float32 or \
-            residual.device != dev or residual.requires_grad:
-        raise _lib.HplError('motion_segment: residual must be a (%d,) float32 tensor on %s without grad' % (N, dev))
-    residual = residual.contiguous()
+    residual = _vector('motion_segment', 'residual', residual, N, dev)
     pp = _prefix(prefix, N, 'motion_segment')
     B = len(pp) - 1
     if out is not None:
@@ -731,13 +771,9 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
     info = torch.empty((B, max_objects, 2), dtype=torch.int32, device=dev)
     motion = torch.empty((B, max_objects, 6), dtype=torch.float32, device=dev)
     stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    nbytes = lib.hpl_motion_segment_workspace_bytes(B, N)
-    if nbytes < 0:
-        raise _lib.HplError('motion_segment: %d pairs of %d points together are outside the limits (64 pairs, N < 2^31 / 3)' % (B, N))
-    st = stream()
-    ws = _workspace('motion_segment', dev, st, nbytes)
+    ws, st = _room('motion_segment', dev, lib.hpl_motion_segment_workspace_bytes(B, N), _PAIR_LIMITS, B, N)
     check(lib.hpl_motion_segment(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), residual.data_ptr(), B,
-                                 (ctypes.c_int64 * (B + 1))(*pp), tau, eps, dv, min_points, max_objects, labels.data_ptr(),
+                                 _c_prefix(pp), tau, eps, dv, min_points, max_objects, labels.data_ptr(),
                                  info.data_ptr(), motion.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st),
           'hpl_motion_segment')
     return labels, info, motion, stats
@@ -746,8 +782,6 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
 # --------------------------------------------------------------------------- ground removal
 def ground_min_cos(max_tilt_deg):
     """The float32 cosine hpl_ground_fit takes for a largest tilt in degrees (0 <= tilt < 90)."""
-    import math
-    import struct
     t = float(max_tilt_deg)
     if not 0 <= t < 90:
         raise _lib.HplError('ground_fit: max_tilt_deg = %r (0 <= tilt < 90 degrees)' % (max_tilt_deg,))
@@ -768,11 +802,7 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
     hypothesis, fewer than 3 points): plane 0, nothing ground, every index kept.  No autograd, no host synchronisation."""
     _int_in('ground_fit', 'hyps', hyps, 1, 1024)
     _int_in('ground_fit', 'refine', refine, 0, 8)
-    tau, cut = float(tau), float(cut)
-    if not (tau > 0 and tau < float('inf')):
-        raise _lib.HplError('ground_fit: tau = %r (finite and > 0)' % (tau,))
-    if not (cut >= 0 and cut < float('inf')):
-        raise _lib.HplError('ground_fit: cut = %r (finite and >= 0)' % (cut,))
+    tau, cut = _scalar('ground_fit', 'tau', tau), _scalar('ground_fit', 'cut', cut, True)
     min_cos = ground_min_cos(max_tilt_deg)
     try:
         upv = [float(x) for x in up]
@@ -807,12 +837,8 @@ def ground_fit(pc, prefix=None, up=(0, 1, 0), max_tilt_deg=20.0, hyps=256, tau=0
             votes = torch.empty((B, hyps), dtype=torch.int32, device=dev)
         if return_height:
             height = torch.empty(N, dtype=torch.float32, device=dev)
-        nbytes = lib.hpl_ground_fit_workspace_bytes(B, N, hyps)
-        if nbytes < 0:
-            raise _lib.HplError('ground_fit: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (B, N))
-        st = stream()
-        ws = _workspace('ground_fit', dev, st, nbytes)
-        check(lib.hpl_ground_fit(pc.data_ptr(), pc_ld, B, (ctypes.c_int64 * (B + 1))(*pp), (ctypes.c_float * 3)(*upv), min_cos,
+        ws, st = _room('ground_fit', dev, lib.hpl_ground_fit_workspace_bytes(B, N, hyps), _CLOUD_LIMITS, B, N)
+        check(lib.hpl_ground_fit(pc.data_ptr(), pc_ld, B, _c_prefix(pp), (ctypes.c_float * 3)(*upv), min_cos,
                                  hyps, tau, refine, cut, seed, call, plane.data_ptr(), stats.data_ptr(), ptr(votes), ptr(height),
                                  ground.data_ptr(), keep.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_ground_fit')
     res = (plane, stats, ground, keep)
@@ -829,7 +855,6 @@ VOXEL_MODES = {'centroid': 0, 'nearest': 1}
 
 def voxel_args(who, voxel, origin, mode):
     """(voxel as the float32 the library takes, origin as three floats, the mode's number) or an HplError."""
-    import struct
     try:
         v = struct.unpack('f', struct.pack('f', float(voxel)))[0]
     except (TypeError, ValueError, OverflowError):
@@ -864,28 +889,10 @@ def voxel_downsample(pc, attrs=None, voxel=0.1, origin=(0, 0, 0), mode='centroid
     v, org, m = voxel_args(who, voxel, origin, mode)
     pc, pc_ld = _soa3(pc, 'pc', who)
     N, dev = pc.shape[1], pc.device
-    C, attr_ld = 0, 0
-    if attrs is not None:
-        if not torch.is_tensor(attrs) or attrs.dim() != 2 or attrs.shape[1] != N or attrs.dtype != torch.float32 or \
-                attrs.device != dev or not 1 <= attrs.shape[0] <= 8:
-            raise _lib.HplError('%s: attrs must be a (C, %d) float32 tensor on %s with 1 <= C <= 8, got %s' % (
-                who, N, dev, (tuple(attrs.shape), attrs.dtype, attrs.device) if torch.is_tensor(attrs) else type(attrs)))
-        if attrs.requires_grad:
-            raise _lib.HplError('%s has no autograd: attrs requires grad' % who)
-        C = attrs.shape[0]
-        if (C > 1 and attrs.stride(0) < max(N, 1)) or (N > 1 and attrs.stride(1) != 1):
-            attrs = attrs.contiguous()
-        attr_ld = max(N, 1) if C == 1 or attrs.is_contiguous() else attrs.stride(0)
+    attrs, C, attr_ld = _attrs(who, attrs, N, dev)
     pp = _prefix(prefix, N, who)
     B = len(pp) - 1
-    if out is not None:
-        if not torch.is_tensor(out) or tuple(out.shape) != (3, N) or out.dtype != torch.float32 or out.device != dev or \
-                out.requires_grad or out.stride(0) < max(N, 1) or (N > 1 and out.stride(1) != 1):
-            raise _lib.HplError('%s: out must be a (3, %d) float32 tensor on %s with unit stride along the points' % (who, N, dev))
-        out_pc = out
-    else:
-        out_pc = torch.empty((3, N), dtype=torch.float32, device=dev)
-    out_ld = max(N, 1) if out_pc.is_contiguous() else out_pc.stride(0)
+    out_pc, out_ld = _soa_out(who, out, N, dev, 'the points')
     out_attrs = torch.empty((C, N), dtype=torch.float32, device=dev) if C else None
     count = torch.empty(N, dtype=torch.int32, device=dev)
     rep = torch.empty(N, dtype=torch.int32, device=dev)
@@ -894,12 +901,8 @@ def voxel_downsample(pc, attrs=None, voxel=0.1, origin=(0, 0, 0), mode='centroid
         return out_pc, out_attrs, count, rep, voxel_of, torch.zeros((B, 4), dtype=torch.int32, device=dev)
     stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
     lib = _lib.load()
-    nbytes = lib.hpl_voxel_downsample_workspace_bytes(B, N, C)
-    if nbytes < 0:
-        raise _lib.HplError('%s: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (who, B, N))
-    st = stream()
-    ws = _workspace(who, dev, st, nbytes)
-    check(lib.hpl_voxel_downsample(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, (ctypes.c_int64 * (B + 1))(*pp), v,
+    ws, st = _room(who, dev, lib.hpl_voxel_downsample_workspace_bytes(B, N, C), _CLOUD_LIMITS, B, N)
+    check(lib.hpl_voxel_downsample(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, _c_prefix(pp), v,
                                    (ctypes.c_float * 3)(*org), m, out_pc.data_ptr(), out_ld, ptr(out_attrs), max(N, 1),
                                    count.data_ptr(), rep.data_ptr(), voxel_of.data_ptr(), stats.data_ptr(), ws.data_ptr(),
                                    ws.numel(), st), 'hpl_voxel_downsample')
@@ -941,25 +944,13 @@ def fps(pc, m, attrs=None, start=None, prefix=None, path='auto', return_cover=Fa
     who = 'fps'
     pc, pc_ld = _soa3(pc, 'pc', who)
     N, dev = pc.shape[1], pc.device
-    C, attr_ld = 0, 0
-    if attrs is not None:
-        if not torch.is_tensor(attrs) or attrs.dim() != 2 or attrs.shape[1] != N or attrs.dtype != torch.float32 or \
-                attrs.device != dev or not 1 <= attrs.shape[0] <= 8:
-            raise _lib.HplError('%s: attrs must be a (C, %d) float32 tensor on %s with 1 <= C <= 8, got %s' % (
-                who, N, dev, (tuple(attrs.shape), attrs.dtype, attrs.device) if torch.is_tensor(attrs) else type(attrs)))
-        if attrs.requires_grad:
-            raise _lib.HplError('%s has no autograd: attrs requires grad' % who)
-        C = attrs.shape[0]
-        if (C > 1 and attrs.stride(0) < max(N, 1)) or (N > 1 and attrs.stride(1) != 1):
-            attrs = attrs.contiguous()
-        attr_ld = max(N, 1) if C == 1 or attrs.is_contiguous() else attrs.stride(0)
+    attrs, C, attr_ld = _attrs(who, attrs, N, dev)
     pp = _prefix(prefix, N, who)
     B = len(pp) - 1
     m, pnum = fps_args(who, m, B, path)
     M = B * m
     st = None
     if start is not None:
-        import operator
         try:
             st = [None if isinstance(x, bool) else operator.index(x) for x in start]
         except TypeError:
@@ -967,14 +958,7 @@ def fps(pc, m, attrs=None, start=None, prefix=None, path='auto', return_cover=Fa
         if st is None or len(st) != B or None in st or any(pp[b + 1] > pp[b] and not 0 <= st[b] < pp[b + 1] - pp[b] for b in range(B)):
             raise _lib.HplError('%s: start holds %d ints, each an index into its cloud, got %r' % (who, B, start))
         st = (ctypes.c_int32 * B)(*[x if pp[b + 1] > pp[b] else 0 for b, x in enumerate(st)])
-    if out is not None:
-        if not torch.is_tensor(out) or tuple(out.shape) != (3, M) or out.dtype != torch.float32 or out.device != dev or \
-                out.requires_grad or out.stride(0) < M or (M > 1 and out.stride(1) != 1):
-            raise _lib.HplError('%s: out must be a (3, %d) float32 tensor on %s with unit stride along the samples' % (who, M, dev))
-        out_pc = out
-    else:
-        out_pc = torch.empty((3, M), dtype=torch.float32, device=dev)
-    out_ld = M if out_pc.is_contiguous() else out_pc.stride(0)
+    out_pc, out_ld = _soa_out(who, out, M, dev, 'the samples')
     if N == 0:                                   # nothing to launch: every cloud is empty
         out_pc.zero_()
         return (out_pc, torch.zeros((C, M), dtype=torch.float32, device=dev) if C else None,
@@ -987,12 +971,8 @@ def fps(pc, m, attrs=None, start=None, prefix=None, path='auto', return_cover=Fa
     cover = torch.empty(N, dtype=torch.float32, device=dev) if return_cover else None
     stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
     lib = _lib.load()
-    nbytes = lib.hpl_fps_workspace_bytes(B, N, m, C)
-    if nbytes < 0:
-        raise _lib.HplError('%s: %d clouds of %d points together are outside the limits (64 clouds, N < 2^31 / 3)' % (who, B, N))
-    s = stream()
-    ws = _workspace(who, dev, s, nbytes)
-    check(lib.hpl_fps(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, (ctypes.c_int64 * (B + 1))(*pp), st, m, pnum,
+    ws, s = _room(who, dev, lib.hpl_fps_workspace_bytes(B, N, m, C), _CLOUD_LIMITS, B, N)
+    check(lib.hpl_fps(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, _c_prefix(pp), st, m, pnum,
                       idx.data_ptr(), dist.data_ptr(), out_pc.data_ptr(), out_ld, ptr(out_attrs), M, ptr(cover),
                       stats.data_ptr(), ws.data_ptr(), ws.numel(), s), 'hpl_fps')
     return out_pc, out_attrs, idx, dist, cover, stats
@@ -1030,21 +1010,16 @@ def _frames_outputs(who, out, N, B, dev):
     along the pixels (rows may be views of a wider buffer)."""
     if out is None:
         out = (torch.empty((3, N), dtype=torch.float32, device=dev), torch.empty((3, N), dtype=torch.float32, device=dev))
-    if not isinstance(out, (list, tuple)) or len(out) != 2 or any(
-            not torch.is_tensor(o) or tuple(o.shape) != (3, N) or o.dtype != torch.float32 or o.device != dev or o.requires_grad or
-            o.stride(0) < max(N, 1) or (N > 1 and o.stride(1) != 1) for o in out):
+    if not isinstance(out, (list, tuple)) or len(out) != 2 or not (_soa_ok(out[0], N, dev) and _soa_ok(out[1], N, dev)):
         raise _lib.HplError('%s: out must be a pair of (3, %d) float32 tensors on %s with unit stride along the pixels' % (who, N, dev))
-    lds = [max(N, 1) if o.is_contiguous() else o.stride(0) for o in out]
     pixel = torch.empty(N, dtype=torch.int32, device=dev)
     counts = torch.zeros(B, dtype=torch.int32, device=dev) if N == 0 else torch.empty(B, dtype=torch.int32, device=dev)
-    return out[0], lds[0], out[1], lds[1], pixel, counts
+    return out[0], _soa_ld(out[0], N), out[1], _soa_ld(out[1], N), pixel, counts
 
 
-def _frames_workspace(who, lib, B, N, dev, st):
-    nbytes = lib.hpl_frames_workspace_bytes(B, N)
-    if nbytes < 0:
-        raise _lib.HplError('%s: %d frames of %d pixels together are outside the limits (64 frames, N < 2^31 / 3)' % (who, B, N))
-    return _workspace(who, dev, st, nbytes)
+def _frames_room(who, lib, B, N, dev):
+    return _room(who, dev, lib.hpl_frames_workspace_bytes(B, N),
+                 '%d frames of %d pixels together are outside the limits (64 frames, N < 2^31 / 3)', B, N)
 
 
 _U16 = (torch.uint16, torch.int16)          # (the same bits: a PNG's raw values)
@@ -1076,10 +1051,9 @@ def frames_from_kitti(disp1, disp2, flow, P, heights, widths, baseline=0.54, out
         raise _lib.HplError('%s: P holds the (3, 4) P_rect_02 of each of the %d frames' % (who, B))
     o1, ld1, o2, ld2, pixel, counts = _frames_outputs(who, out, N, B, dev)
     lib = _lib.load()
-    st = stream()
-    ws = _frames_workspace(who, lib, B, N, dev, st)
+    ws, st = _frames_room(who, lib, B, N, dev)
     check(lib.hpl_frames_from_kitti(disp1.data_ptr(), disp2.data_ptr(), flow.data_ptr(), B, (ctypes.c_int32 * B)(*hh),
-                                    (ctypes.c_int32 * B)(*ww), (ctypes.c_int64 * (B + 1))(*pp),
+                                    (ctypes.c_int32 * B)(*ww), _c_prefix(pp),
                                     Pm.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), float(baseline), o1.data_ptr(), ld1,
                                     o2.data_ptr(), ld2, pixel.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel(), st),
           'hpl_frames_from_kitti')
@@ -1107,10 +1081,9 @@ def frames_from_ft3d(disp, dchange, flow, occ1, occ2, heights, widths, f=-1050.0
         raise _lib.HplError('%s: near = %r (None or a number)' % (who, near))
     o1, ld1, o2, ld2, pixel, counts = _frames_outputs(who, out, N, B, dev)
     lib = _lib.load()
-    st = stream()
-    ws = _frames_workspace(who, lib, B, N, dev, st)
+    ws, st = _frames_room(who, lib, B, N, dev)
     check(lib.hpl_frames_from_ft3d(disp.data_ptr(), dchange.data_ptr(), flow.data_ptr(), occ1.data_ptr(), occ2.data_ptr(), B,
-                                   (ctypes.c_int32 * B)(*hh), (ctypes.c_int32 * B)(*ww), (ctypes.c_int64 * (B + 1))(*pp), float(f),
+                                   (ctypes.c_int32 * B)(*hh), (ctypes.c_int32 * B)(*ww), _c_prefix(pp), float(f),
                                    float(cx), float(cy), 0 if near is None else 1, 0.0 if near is None else float(near),
                                    o1.data_ptr(), ld1, o2.data_ptr(), ld2, pixel.data_ptr(), counts.data_ptr(), ws.data_ptr(),
                                    ws.numel(), st), 'hpl_frames_from_ft3d')
@@ -1180,14 +1153,10 @@ def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None,
     else:
         lib = _lib.load()
         loss = torch.empty((B, 4), dtype=torch.float32, device=dev)
-        nbytes = lib.hpl_selfsup_loss_workspace_bytes(B, N1, N2, k)
-        if nbytes < 0:
-            raise _lib.HplError('%s: %d pairs of %d / %d points together, k = %d are outside the limits (64 pairs, counts < 2^31 / 3, '
-                                'k N1 < 2^31)' % (who, B, N1, N2, k))
-        st = stream()
-        ws = _workspace(who, dev, st, nbytes)
+        ws, st = _room(who, dev, lib.hpl_selfsup_loss_workspace_bytes(B, N1, N2, k), '%d pairs of %d / %d points together, k = %d are '
+                       'outside the limits (64 pairs, counts < 2^31 / 3, k N1 < 2^31)', B, N1, N2, k)
         check(lib.hpl_selfsup_loss(pc1.data_ptr(), ld1, flow.data_ptr(), flow.stride(0), flow.stride(1), pc2.data_ptr(), ld2, B,
-                                   (ctypes.c_int64 * (B + 1))(*p1), (ctypes.c_int64 * (B + 1))(*p2), k, w_chamfer, w_smooth,
+                                   _c_prefix(p1), _c_prefix(p2), k, w_chamfer, w_smooth,
                                    loss.data_ptr(), ptr(dflow), ptr(nn12), ptr(nn21), ptr(nbr) if k > 0 else None, ws.data_ptr(),
                                    ws.numel(), st), 'hpl_selfsup_loss')
     return (loss, dflow, nn12, nn21, nbr) if return_neighbors else (loss, dflow)

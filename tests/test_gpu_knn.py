@@ -255,22 +255,6 @@ def test_same_bits_beside_a_busy_stream():
         assert torch.equal(x, y)
 
 
-def test_op_refusals():
-    from hplflownet_amd import _lib, ops
-    ref, val, q = torch.zeros(3, 10, device=DEV), torch.zeros(10, 3, device=DEV), torch.zeros(3, 5, device=DEV)
-    for kw in (dict(k=0), dict(k=9), dict(eps=-1.0), dict(eps=float('nan')), dict(ref_prefix=[0, 4, 10]),
-               dict(ref_prefix=[0, 12, 10], q_prefix=[0, 2, 5]), dict(ref_prefix=[0, 0, 10], q_prefix=[0, 2, 5])):
-        with pytest.raises(_lib.HplError):
-            ops.knn_interpolate(ref, val, q, **kw)
-    for bad in ((ref.requires_grad_(), val, q), (torch.zeros(3, 10, device=DEV), torch.zeros(10, 3, device=DEV, requires_grad=True), q),
-                (torch.zeros(3, 10, device=DEV), torch.zeros(10, 17, device=DEV), q),
-                (torch.zeros(3, 10, device=DEV), torch.zeros(9, 3, device=DEV), q),
-                (torch.zeros(3, 10, device=DEV).double(), torch.zeros(10, 3, device=DEV), q)):
-        with pytest.raises(_lib.HplError):
-            ops.knn_interpolate(*bad)
-    assert ops.knn_interpolate(torch.zeros(3, 10, device=DEV), val, q[:, :0]).shape == (0, 3)
-
-
 # ----------------------------------------------------------------------------- DenseFlow.query(fill='knn')
 def fill_queries(p1, p2, n, seed):
     """pc1 itself (coverage 1), jittered pc1 and pc2 points (partial coverage), points far outside the box (coverage 0)."""

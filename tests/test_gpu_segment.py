@@ -243,21 +243,6 @@ def test_operand_forms_are_read_in_place():
     assert bool(torch.isnan(wide_p[1][:, :7]).all()) and bool(torch.isnan(wide_f[1][:, 7 + n:]).all())
 
 
-def test_op_refusals():
-    from hplflownet_amd import _lib, ops
-    pc, fl, r = torch.zeros(3, 10, device=DEV), torch.zeros(10, 3, device=DEV), torch.zeros(10, device=DEV)
-    for kw in (dict(tau=0.0), dict(tau=float('inf')), dict(eps=0.0), dict(eps=float('inf')), dict(eps=float('nan')), dict(dv=0.0),
-               dict(dv=float('nan')), dict(min_points=0), dict(min_points=2.0), dict(max_objects=0), dict(max_objects=4097),
-               dict(prefix=[0, 4]), dict(prefix=[1, 10]), dict(prefix=[0, 12, 10]), dict(prefix=[0] * 65 + [10]),
-               dict(out=torch.zeros(10, dtype=torch.int32)), dict(out=torch.zeros(10, device=DEV))):
-        with pytest.raises(_lib.HplError):
-            ops.motion_segment(pc, fl, r, **kw)
-    for bad in ((pc.double(), fl, r), (pc, fl.double(), r), (pc, torch.zeros(9, 3, device=DEV), r), (pc, fl, r[:9]), (pc, fl, r.double()),
-                (pc, fl.clone().requires_grad_(), r), (pc.cpu(), fl, r)):
-        with pytest.raises(_lib.HplError):
-            ops.motion_segment(*bad)
-
-
 def test_same_bits_twice_and_beside_a_busy_stream():
     from hplflownet_amd import ops
     p, f, _, _ = the_scene(4099)
