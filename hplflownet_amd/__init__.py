@@ -8,6 +8,7 @@ Public surface (mirrors the reference's operator interface for the path):
     icp_register                                                 (rigid registration of a cloud pair; flownet.py, ops.icp)
     estimate_normals                                             (surface normals of clouds; flownet.py, ops.normals)
     segment_motion                                               (moving objects from flow; flownet.py, ops.motion_segment)
+    piecewise_rigid                                              (ego-motion + a rigid motion per object; flownet.py, ops.object_fit)
     selfsup_loss                                                 (Chamfer + smoothness loss; flownet.py, ops.selfsup_loss)
     remove_ground                                                (fitted-plane ground removal; flownet.py, ops.ground_fit)
     voxel_downsample                                             (voxel-grid downsampling; flownet.py, ops.voxel_downsample)
@@ -18,7 +19,8 @@ The arithmetic lives in libhplbcl.so (csrc/*.hip, C ABI in include/hpl_bcl.h).
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, Conv2dReLU, Conv3dReLU,  # noqa: F401
                   sparse_sum)
 from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, estimate_normals, fps_sample,  # noqa: F401
-                      frames_from_ft3d, frames_from_kitti, icp_register, remove_ground, rigid_refine, segment_motion, selfsup_loss,
+                      frames_from_ft3d, frames_from_kitti, icp_register, piecewise_rigid, remove_ground, rigid_refine, segment_motion,
+                      selfsup_loss,
                       voxel_downsample)
 from .lattice import GenerateDataUnsymmetric, to_reference_format  # noqa: F401
 

@@ -222,6 +222,9 @@ _SIGNATURES = {
     'hpl_motion_segment_workspace_bytes': (c_i64, [ctypes.c_int, c_i64]),
     'hpl_motion_segment': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, ctypes.c_int, ctypes.POINTER(c_i64), c_f32, c_f32,
                                           c_f32, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'hpl_object_fit_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, ctypes.c_int]),
+    'hpl_object_fit': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp, ctypes.c_int, ctypes.POINTER(c_i64), ctypes.c_int,
+                                      ctypes.c_int, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'hpl_selfsup_loss_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, c_i64, ctypes.c_int]),
     'hpl_selfsup_loss': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_i64, ctypes.c_int, ctypes.POINTER(c_i64),
                                         ctypes.POINTER(c_i64), ctypes.c_int, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -307,7 +307,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None, segment=None,
-                 icp=None):
+                 icp=None, objects=None):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -342,7 +342,14 @@ class Trainer(object):
         papers, independent of the model's output -- or, with init='rigid' (which takes rigid), starting from that forward's
         rigid fit: network + ICP.  The flow R p + t - p goes through one more metrics launch into an array of its own; the
         (B, 6) statistics stay on the device and come back with the read-back.  The keys gain icp_<metric> plus icp_matched,
-        icp_rmse, icp_angle_deg, icp_trans and icp_rounds, means over pairs."""
+        icp_rmse, icp_angle_deg, icp_trans and icp_rounds, means over pairs.
+
+        objects={'iters': T, 'tau': tau} (with rigid and segment; {}: the fit's values): one ops.object_fit call
+        per forward fits every listed object's own rigid motion on the labels just computed -- no read-back -- and the
+        piecewise-rigid flow (the ego-motion's rigid flow at its inliers, an object's at the inliers of its fit, the sampled flow
+        elsewhere) goes through one more metrics launch into an array of its own.  Behind every other key, and changing none,
+        the keys gain piecewise_<metric> plus piecewise_object_inliers: the share of a pair's points whose flow an object fit
+        replaced, from integer counts that stay on the device until the read-back."""
         if dense_fill is not None and not dense:
             raise HplError('validate: dense_fill applies to dense=True')
         if rigid is not None:
@@ -353,6 +360,10 @@ class Trainer(object):
             if rigid is None:
                 raise HplError('validate: segment applies to rigid')
             segment = segment_options(segment)
+        if objects is not None:
+            if rigid is None or segment is None:
+                raise HplError('validate: objects applies to rigid with segment')
+            objects = object_options(objects, rigid)
         if icp is not None:
             if not isinstance(icp, dict) or set(icp) - {'iters', 'max_dist', 'tau', 'init', 'metric', 'normals_k', 'normals_radius'} or \
                     icp.get('init', 'identity') not in ('identity', 'rigid') or icp.get('metric', 'point') not in ('point', 'plane') or \
@@ -373,6 +384,7 @@ class Trainer(object):
         rkeys = ['rigid_' + k for k in keys] + list(RIGID_STATS) if rigid is not None else []
         rkeys = rkeys + list(SEGMENT_STATS) if segment is not None else rkeys
         rkeys = rkeys + ['icp_' + k for k in keys] + list(ICP_STATS) if icp is not None else rkeys
+        rkeys = rkeys + ['piecewise_' + k for k in keys] + list(OBJECT_STATS) if objects is not None else rkeys
         self.val_batches = 0
         self.val_pairs = []
         self._dense = None
@@ -392,6 +404,10 @@ class Trainer(object):
                 rstage = ops.MetricsStage(n, self.device)
                 rstats = []                              # every forward's (B, 4) fit statistics, on the device
                 sstats, scounts = [], []                 # segment: every forward's (B, 4) integer counts, on the device
+            if objects is not None:
+                osums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
+                ostage = ops.MetricsStage(n, self.device)
+                ocounts = []                             # every forward's (B,) counts of the rows an object fit replaced
             if icp is not None:
                 isums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
                 istage = ops.MetricsStage(n, self.device)
@@ -418,6 +434,15 @@ class Trainer(object):
                     if segment is None:
                         fit = rigid_refine(pc1, flow, **rigid)
                         st, refined = fit[2], fit[3]
+                    elif objects is not None:
+                        from .flownet import _piecewise
+                        whole = _piecewise(pc1, flow, None, rigid['iters'], rigid['tau'], objects['iters'], objects['tau'], None,
+                                           segment, keep_ego=True)
+                        fit = whole.fit
+                        st, refined = fit[2], fit[3]
+                        sstats.append(whole.seg[3])
+                        scounts.extend(int(s_[0].shape[1]) for s_ in samples)
+                        ocounts.append(whole.replaced)
                     else:
                         from .flownet import segment_motion
                         fit = rigid_refine(pc1, flow, return_residual=True, **rigid)
@@ -428,6 +453,9 @@ class Trainer(object):
                     rstats.append(st)            # (sample order: the groups are runs of consecutive samples)
                     ops.flow_metrics_pairs(list(refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
                                            cameras_of(samples), rsums, nxt[0], rstage)
+                    if objects is not None:
+                        ops.flow_metrics_pairs(list(whole.refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
+                                               cameras_of(samples), osums, nxt[0], ostage)
                 if icp is not None:
                     from .flownet import icp_register
                     res = icp_register([s_[0] for s_ in samples], [s_[1] for s_ in samples],
@@ -454,6 +482,8 @@ class Trainer(object):
                     rwords, rst = rsums.cpu().numpy(), torch.cat(rstats).cpu().numpy()
                     if segment is not None:
                         sst = torch.cat(sstats).cpu().numpy()
+                    if objects is not None:
+                        owords, oct_ = osums.cpu().numpy(), torch.cat(ocounts).cpu().numpy()
                 if icp is not None:
                     iwords, ist = isums.cpu().numpy(), torch.cat(istats).cpu().numpy()
             finally:
@@ -474,6 +504,10 @@ class Trainer(object):
                 for i, v in self.val_pairs:
                     v.update({'icp_' + k: x for k, x in ops.flow_metrics_fold(iwords[i], cams).items()})
                     v.update(zip(ICP_STATS, (float(x) for x in ist[i, 1:])))
+            if objects is not None:
+                for i, v in self.val_pairs:
+                    v.update({'piecewise_' + k: x for k, x in ops.flow_metrics_fold(owords[i], cams).items()})
+                    v['piecewise_object_inliers'] = int(oct_[i]) / max(1, scounts[i])
         keys = keys + dkeys + rkeys
         agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
         # every rank evaluated its own shard (shards may differ in length by one): sums and the sample count are
@@ -634,6 +668,20 @@ def segment_options(segment):
     return o
 
 
+#: validate(objects=...): the per-pair key beside the piecewise_<metric> keys
+OBJECT_STATS = ('piecewise_object_inliers',)
+
+
+def object_options(objects, rigid):
+    """validate's objects argument, checked and with its defaults: the rigid fit's iters and tau."""
+    if not isinstance(objects, dict) or set(objects) - {'iters', 'tau'}:
+        raise HplError('validate: objects takes {\'iters\': T, \'tau\': tau}, got %r' % (objects,))
+    o = {'iters': int(objects.get('iters', rigid['iters'])), 'tau': float(objects.get('tau', rigid['tau']))}
+    if not 0 <= o['iters'] <= 16 or not 0 < o['tau'] < float('inf'):
+        raise HplError('validate: objects needs iters in 0 .. 16 and tau finite and > 0, got %r' % (objects,))
+    return o
+
+
 def segment_fold(row, points):
     """(seg_objects, seg_moving, seg_noise) of one pair of `points` points from its (movers, objects, points in objects, out of
     range) counts."""
@@ -763,6 +811,15 @@ def parse_args(argv=None):
                     help='with --evaluate --rigid-refine: group the points the rigid fit leaves unexplained (residual above '
                          '--rigid-tau) into moving objects on the device and report seg_objects / seg_moving / seg_noise '
                          '(DESIGN.md §19)')
+    ap.add_argument('--object-refine', action='store_true',
+                    help='with --evaluate --rigid-refine --segment: fit every listed object\'s own rigid motion on the device and '
+                         'also report the metrics of the piecewise-rigid flow -- ego-motion on the static points, each '
+                         'object\'s motion on its points -- as piecewise_<metric>, with piecewise_object_inliers (DESIGN.md §32)')
+    ap.add_argument('--object-iters', type=int, default=None, metavar='T',
+                    help='reweighted solves of --object-refine after the least-squares one (0 .. 16, default: --rigid-iters)')
+    ap.add_argument('--object-tau', type=float, default=None, metavar='TAU',
+                    help='--object-refine: inlier threshold and weight scale of the object fits in metres (> 0, default: '
+                         '--rigid-tau)')
     ap.add_argument('--segment-eps', type=float, default=None, metavar='E',
                     help='--segment: link radius in metres (finite and > 0, default 0.5)')
     ap.add_argument('--segment-dv', type=float, default=None, metavar='V',
@@ -867,6 +924,14 @@ def parse_args(argv=None):
     a.segment = {'eps': 0.5 if a.segment_eps is None else a.segment_eps,
                  'dv': float('inf') if a.segment_dv is None else a.segment_dv,
                  'min_points': 5 if a.segment_min_points is None else a.segment_min_points} if a.segment else None
+    if a.object_refine and not (a.evaluate and a.rigid_refine and a.segment):
+        ap.error('--object-refine applies to --evaluate --rigid-refine --segment')
+    if a.object_iters is not None and (not a.object_refine or not 0 <= a.object_iters <= 16):
+        ap.error('--object-iters takes 0 .. 16 and applies to --object-refine')
+    if a.object_tau is not None and (not a.object_refine or not 0 < a.object_tau < float('inf')):
+        ap.error('--object-tau takes a finite value > 0 and applies to --object-refine')
+    a.objects = {'iters': a.rigid['iters'] if a.object_iters is None else a.object_iters,
+                 'tau': a.rigid['tau'] if a.object_tau is None else a.object_tau} if a.object_refine else None
     on = a.baseline == 'icp'
     if on and not a.evaluate:
         ap.error('--baseline applies to --evaluate')
@@ -958,7 +1023,7 @@ def main(argv=None):
         return _real_data(a, tr, dev, rank, world)
     if a.evaluate:
         res = tr.validate(SyntheticPairs(a.pairs, a.points, dev, first_seed=1000 + rank * a.pairs), a.batch_size, a.ragged,
-                          rigid=a.rigid, segment=a.segment, icp=a.icp)
+                          rigid=a.rigid, segment=a.segment, icp=a.icp, objects=a.objects)
         if rank == 0:
             print(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
@@ -1085,7 +1150,7 @@ def _real_data(a, tr, dev, rank, world):
     val = _Shard(val, rank, world, cap)
     if train is None:
         res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid,
-                          segment=a.segment, icp=a.icp)
+                          segment=a.segment, icp=a.icp, objects=a.objects)
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -799,7 +799,11 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
     not for an evaluation loop), gathers each listed object's points in object order and fits every object's own rigid
     motion with ops.rigid_fit, the objects as its segments, 64 a call.  The result gains a fifth entry: per pair a tuple
     (R (K_b, 3, 3), t (K_b, 3), stats (K_b, 4)) over the pair's first K_b = min(objects, max_objects) objects (an object of fewer
-    than 3 points has status 0, R = I, t = 0, as that op defines)."""
+    than 3 points has status 0, R = I, t = 0, as that op defines).
+    object_fits='device' is the form without a read-back: ONE ops.object_fit call on the labels just computed,
+    with the fit's iters and tau and, as object_fits=True, no weight.  The fifth entry is then (obj_Rt (B, max_objects, 12),
+    obj_stats (B, max_objects, 4)): the rows of a pair's first min(objects, max_objects) objects hold the bits object_fits=True
+    returns, the rows behind them R = I, t = 0, stats 0."""
     pc, fl, prefix, counts, _ = _packed_pairs(pc1, flow, lat_or_counts, 'segment_motion')
     if rigid is None:
         residual = ops.rigid_fit(pc, fl, weight=weight, iters=iters, tau=tau, prefix=prefix, return_residual=True)[4]
@@ -810,6 +814,9 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
     labels, info, motion, stats = ops.motion_segment(pc, fl, residual, tau=tau, prefix=prefix, **kw)
     if not object_fits:
         return labels, info, motion, stats
+    if object_fits == 'device':
+        return labels, info, motion, stats, ops.object_fit(pc, fl, labels, max_objects=info.shape[1], iters=iters, tau=tau,
+                                                           prefix=prefix)
     host = info.cpu().numpy()                                # the one read-back (it follows the launches on this stream)
     dev = pc.device
     fits = []
@@ -833,6 +840,48 @@ def segment_motion(pc1, flow, lat_or_counts=None, rigid=None, object_fits=False,
             sts.append(st)
         fits.append((torch.cat(Rs), torch.cat(ts), torch.cat(sts)))
     return labels, info, motion, stats, fits
+
+
+def piecewise_rigid(pc1, flow, lat_or_counts=None, iters=4, tau=0.1, obj_iters=None, obj_tau=None, weight=None, **segment_kw):
+    """The piecewise-rigid flow of a forward's flow in three stream-ordered calls without a read-back:
+    ops.rigid_fit(return_residual=True) for the ego-motion, ops.motion_segment on its residuals for the objects, and
+    ops.object_fit on the fit's refined flow and residual for each object's own motion.  pc1 / flow / lat_or_counts: the forms
+    rigid_refine takes, read in place the same way.  iters, tau, weight: of the ego fit (tau is the movers' threshold too);
+    obj_iters, obj_tau: of the object fits (None: iters and tau; the object fits take the same weight); segment_kw: eps, dv,
+    min_points, max_objects of ops.motion_segment.
+    -> (R (B, 3, 3), t (B, 3), stats (B, 4), labels (sum N_b,), obj_info, obj_Rt (B, max_objects, 12), obj_stats
+    (B, max_objects, 4), refined): refined in the form of `flow`, as rigid_refine returns it -- the ego-motion's rigid flow at
+    its inliers, an object's at the inliers of its fit, the input flow's bits at every other point."""
+    w = _piecewise(pc1, flow, lat_or_counts, iters, tau, obj_iters, obj_tau, weight, segment_kw)
+    return w.fit[:3] + (w.seg[0], w.seg[1], w.obj_Rt, w.obj_stats, w.refined)
+
+
+_Piecewise = collections.namedtuple('_Piecewise', 'fit seg obj_Rt obj_stats refined replaced')
+
+
+def _piecewise(pc1, flow, lat_or_counts, iters, tau, obj_iters, obj_tau, weight, segment_kw, keep_ego=False):
+    """piecewise_rigid's three calls -> _Piecewise: fit = ops.rigid_fit's five results and seg = ops.motion_segment's four, of the
+    packed operands; refined in the form of `flow`.  By default the object fits update the ego fit's refined rows where they
+    lie (fit[3] is then the piecewise-rigid flow too).  keep_ego (validate(objects=...), which reports both flows): the object
+    fits write into rows of their own, fit[3] -- in the form of `flow` -- stays the ego fit's, and replaced (B,) int64 counts
+    each pair's rows that an object fit wrote, on the device."""
+    pc, fl, prefix, counts, shape = _packed_pairs(pc1, flow, lat_or_counts, 'piecewise_rigid')
+    fit = ops.rigid_fit(pc, fl, weight=weight, iters=iters, tau=tau, prefix=prefix, return_residual=True)
+    seg = ops.motion_segment(pc, fl, fit[4], tau=tau, prefix=prefix, **segment_kw)
+    # (a row an object fit writes is finite -- an inlier has a finite residual --, so NaN marks the rows it left alone)
+    rows = torch.full_like(fit[3], float('nan')) if keep_ego else fit[3]
+    obj_Rt, obj_stats = ops.object_fit(pc, fl, seg[0], weight=weight, max_objects=seg[1].shape[1],
+                                       iters=iters if obj_iters is None else obj_iters, tau=tau if obj_tau is None else obj_tau,
+                                       prefix=prefix, residual=None if keep_ego else fit[4], refined=rows)[:2]
+    replaced = None
+    if keep_ego:
+        wrote = rows[:, 0] == rows[:, 0]
+        rows = torch.where(wrote[:, None], rows, fit[3])
+        replaced = torch.stack([wrote[a:b].sum() for a, b in zip(prefix[:-1], prefix[1:])])
+    as_flow = shape is not False or tuple(flow.shape) == (3, rows.shape[0])    # (a packed [N, 3] flow gets its rows as they are)
+    if keep_ego and as_flow:
+        fit = fit[:3] + (_rows_as(fit[3], shape, prefix),) + fit[4:]
+    return _Piecewise(fit, seg, obj_Rt, obj_stats, _rows_as(rows, shape, prefix) if as_flow else rows, replaced)
 
 
 # ----------------------------------------------------------------------------- ground removal

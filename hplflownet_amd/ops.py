@@ -779,6 +779,70 @@ def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_po
     return labels, info, motion, stats
 
 
+# --------------------------------------------------------------------------- object motions from flow
+def _inplace(who, name, t, shape, dtype, dev):
+    """t as the contiguous tensor of that shape and dtype on dev that a kernel reads or updates where it lies."""
+    if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dtype or t.device != dev or not t.is_contiguous() or \
+            t.requires_grad:
+        raise _lib.HplError('%s: %s must be a contiguous %s %s tensor on %s without grad' % (
+            who, name, shape, str(dtype).replace('torch.', ''), dev))
+    return t
+
+
+def object_fit(pc, flow, labels, weight=None, max_objects=256, iters=4, tau=0.1, prefix=None, residual=None, refined=None,
+               out=None):
+    """hpl_object_fit on the current stream: ops.rigid_fit per labelled object.  pc (3, N) float32, flow (3, N)
+    or [N, 3] float32 of any strides, weight, iters, tau, prefix: exactly as ops.rigid_fit takes them (read in place); labels
+    (N,) int32 as ops.motion_segment returns them, or any other labelling: object o of a pair is its points of label o, in
+    ascending index, and a label outside 0 .. max_objects - 1 belongs to no object.
+    -> (obj_Rt (B, max_objects, 12): R row-major, then t; obj_stats (B, max_objects, 4): status, the inlier share of the
+    object's members, the rotation angle in degrees, |t| [, residual][, refined]): every row is what ops.rigid_fit returns for
+    the object's members gathered as one pair, bit for bit; a row without members holds R = I, t = 0, stats 0.
+    residual (N,) and refined [N, 3] (contiguous float32) are UPDATED IN PLACE and returned when given: residual at every
+    member of a listed object, refined at the inliers of a fitted object (R_o p + t_o - p); every other row keeps its bits.
+    Handed what ops.rigid_fit(return_residual=True) returned, they become the piecewise-rigid flow and its residual.
+    out: a pair of contiguous float32 tensors (B, max_objects, 12) and (B, max_objects, 4) that take obj_Rt and obj_stats.
+    No autograd, no host synchronisation, no read-back."""
+    _int_in('object_fit', 'max_objects', max_objects, 1, 4096)
+    _int_in('object_fit', 'iters', iters, 0, 16)
+    tau = _scalar('object_fit', 'tau', tau)
+    pc, pc_ld = _soa3(pc, 'pc', 'object_fit')
+    N, dev = pc.shape[1], pc.device
+    flow = _flow_view(flow, N, dev, 'object_fit')
+    labels = _inplace('object_fit', 'labels', labels, (N,), torch.int32, dev)
+    if weight is not None:
+        weight = _vector('object_fit', 'weight', weight, N, dev)
+    pp = _prefix(prefix, N, 'object_fit')
+    B = len(pp) - 1
+    if residual is not None:
+        residual = _inplace('object_fit', 'residual', residual, (N,), torch.float32, dev)
+    if refined is not None:
+        refined = _inplace('object_fit', 'refined', refined, (N, 3), torch.float32, dev)
+    if out is not None:
+        if not isinstance(out, (list, tuple)) or len(out) != 2:
+            raise _lib.HplError('object_fit: out is a pair of tensors (obj_Rt, obj_stats)')
+        Rt = _inplace('object_fit', 'out[0]', out[0], (B, max_objects, 12), torch.float32, dev)
+        stats = _inplace('object_fit', 'out[1]', out[1], (B, max_objects, 4), torch.float32, dev)
+    else:
+        Rt = torch.empty((B, max_objects, 12), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, max_objects, 4), dtype=torch.float32, device=dev)
+    if N == 0:                                   # nothing to launch: every object is empty
+        Rt.copy_(_identity_rt(B * max_objects, dev).view(B, max_objects, 12))
+        stats.zero_()
+    else:
+        lib = _lib.load()
+        ws, st = _room('object_fit', dev, lib.hpl_object_fit_workspace_bytes(B, N, max_objects), _PAIR_LIMITS, B, N)
+        check(lib.hpl_object_fit(pc.data_ptr(), pc_ld, flow.data_ptr(), flow.stride(0), flow.stride(1), ptr(weight),
+                                 labels.data_ptr(), B, _c_prefix(pp), max_objects, iters, tau, Rt.data_ptr(), stats.data_ptr(),
+                                 ptr(residual), ptr(refined), ws.data_ptr(), ws.numel(), st), 'hpl_object_fit')
+    res = (Rt, stats)
+    if residual is not None:
+        res += (residual,)
+    if refined is not None:
+        res += (refined,)
+    return res
+
+
 # --------------------------------------------------------------------------- ground removal
 def ground_min_cos(max_tilt_deg):
     """The float32 cosine hpl_ground_fit takes for a largest tilt in degrees (0 <= tilt < 90)."""

@@ -1070,6 +1070,46 @@ int hpl_motion_segment(const float *pc, int64_t pc_ld, const float *flow, int64_
                        void *workspace, int64_t workspace_bytes, hplStream stream);
 
 /* ------------------------------------------------------------------------ *
+ * Object motions from flow (csrc/object_fit.hip): hpl_rigid_fit per labelled object -- the rigid motion of every object that
+ * hpl_motion_segment (or any other labelling) lists -- and the piecewise-rigid flow, without a read-back.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_object_fit for `batch` pairs of n_total points together and max_objects objects a pair, in bytes (monotone
+ * in all three); -1 for a batch outside 1 .. 64, n_total outside 0 .. 2^31 / 3 - 1 or max_objects outside 1 .. 4096. */
+int64_t hpl_object_fit_workspace_bytes(int batch, int64_t n_total, int max_objects);
+/* pc, pc_ld, flow, flow_sc / flow_sp, weight (N) or NULL, prefix (HOST, batch + 1 ints, batch 1 .. 64), iters (0 .. 16) and
+ * tau exactly as hpl_rigid_fit takes them; labels (N) int32, 1 <= max_objects <= 4096.
+ * MEMBERS: object o (0 <= o < max_objects) of pair b has as members that pair's points i with labels[i] == o, in ascending
+ * point index.  The labels alone decide (hpl_motion_segment's obj_info is not read; any labelling will do); a label that is
+ * negative or >= max_objects belongs to no object.
+ * FIT: an object's outputs are hpl_rigid_fit's on its members, gathered in that order as one pair, bit for bit: the same
+ * effective base weight (the gathered weight), rounds, pivot (the object's first member: the root hpl_motion_segment
+ * reports), status rule (fewer than 3 members or a W that is not > 0: status 0, R = I, t = 0), quaternion and order of every
+ * sum (spans of 1024 consecutive members, lane l of 256 taking members l, l + 256, l + 512, l + 768 of a span, one LDS tree a
+ * span, the spans in 16 strided runs, then the runs in order).
+ * obj_Rt [batch][max_objects][12] float32: R row-major, then t.  obj_stats [batch][max_objects][4] float32: status, the
+ * inlier share of the object's members, the rotation angle in degrees, |t|.  A row without members: R = I, t = 0, stats 0.
+ * residual (N) or NULL and refined [N][3] point-major or NULL are UPDATED IN PLACE: residual[i] is written for every member
+ * of a listed object (r_i against its own object's last solve), refined[i] only for the inliers of a fitted object
+ * (R_o p_i + t_o - p_i, rounded as hpl_rigid_fit rounds it); every other row of both is not touched.  Handed the arrays that
+ * hpl_rigid_fit wrote, with hpl_motion_segment's labels of that fit's residuals, the call leaves the piecewise-rigid flow and
+ * its residual: the movers have r > tau against the ego-motion, so the two sets of replaced rows are disjoint.
+ * No floating-point atomic (no atomic at all): an object's outputs are the same bits alone, anywhere in a batch and beside
+ * other work.  Stream-ordered, a fixed number of launches whose sizes depend on N, batch, max_objects and iters alone, no copy
+ * back, no host synchronisation; no lane or workgroup waits for another; every loop is bounded by a member count or a search
+ * depth.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_object_fit_workspace_bytes(batch, N, max_objects); residual and refined must
+ * not overlap the inputs.
+ * HPL_EINVAL before any launch (and without a device): batch, max_objects, iters or tau out of range; a prefix that does not
+ * start at 0 or decreases; pc_ld < N; flow strides < 1 or overlapping; null pc / flow / labels / obj_Rt / obj_stats / prefix /
+ * workspace; a workspace that is too small; misaligned arrays; N >= 2^31 / 3.  N == 0 is a no-op. */
+int hpl_object_fit(const float *pc, int64_t pc_ld, const float *flow, int64_t flow_sc, int64_t flow_sp,
+                   const float *weight /* (N) or NULL */, const int32_t *labels /* (N) */, int batch,
+                   const int64_t *prefix /* HOST */, int max_objects, int iters, float tau,
+                   float *obj_Rt /* [batch][max_objects][12] */, float *obj_stats /* [batch][max_objects][4] */,
+                   float *residual /* (N) or NULL, in/out */, float *refined /* [N][3] or NULL, in/out */,
+                   void *workspace, int64_t workspace_bytes, hplStream stream);
+
+/* ------------------------------------------------------------------------ *
  * Self-supervised loss (csrc/selfsup_loss.hip): Chamfer distance between the warped cloud pc1 + flow and pc2, plus the
  * smoothness of the flow over pc1's k-nearest-neighbour graph, with the gradient by the flow.
  * ------------------------------------------------------------------------ */
