@@ -11,6 +11,7 @@ Public surface (mirrors the reference's operator interface for the path):
     piecewise_rigid                                              (ego-motion + a rigid motion per object; flownet.py, ops.object_fit)
     selfsup_loss                                                 (Chamfer + smoothness loss; flownet.py, ops.selfsup_loss)
     remove_ground                                                (fitted-plane ground removal; flownet.py, ops.ground_fit)
+    remove_outliers                                              (statistical / radius outlier removal; flownet.py, ops.outlier_filter)
     voxel_downsample                                             (voxel-grid downsampling; flownet.py, ops.voxel_downsample)
     fps_sample                                                   (farthest point sampling; flownet.py, ops.fps)
     frames_from_kitti, frames_from_ft3d                          (clouds from raw disparity / flow maps; flownet.py, ops.frames_from_*)
@@ -19,7 +20,7 @@ The arithmetic lives in libhplbcl.so (csrc/*.hip, C ABI in include/hpl_bcl.h).
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, Conv2dReLU, Conv3dReLU,  # noqa: F401
                   sparse_sum)
 from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, estimate_normals, fps_sample,  # noqa: F401
-                      frames_from_ft3d, frames_from_kitti, icp_register, piecewise_rigid, remove_ground, rigid_refine, segment_motion,
+                      frames_from_ft3d, frames_from_kitti, icp_register, piecewise_rigid, remove_ground, remove_outliers, rigid_refine, segment_motion,
                       selfsup_loss,
                       voxel_downsample)
 from .lattice import GenerateDataUnsymmetric, to_reference_format  # noqa: F401

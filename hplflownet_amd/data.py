@@ -445,9 +445,11 @@ class KITTI(_PairFolder):
 
     #: the keyword arguments of flownet.remove_ground that `ground` may hold
     GROUND_KEYS = ('up', 'max_tilt_deg', 'hyps', 'tau', 'refine', 'cut')
+    #: the keys `outlier` may hold: the arguments of ops.outlier_filter, and flownet.remove_outliers' `by`
+    OUTLIER_KEYS = ('mode', 'k', 'radius', 'std_ratio', 'min_neighbors', 'by')
 
     def __init__(self, transform, data_root, remove_ground=True, mapping_file=None, device='cuda', calib_dir=None, ground=None,
-                 voxel=None, voxel_mode='centroid', fps=None):
+                 voxel=None, voxel_mode='centroid', fps=None, outlier=None):
         """remove_ground: True -- the reference's rule, a correspondence is dropped when y < -1.4 in both clouds --, False, or
         'plane': the same pair rule on a plane fitted to each cloud on the device (flownet.remove_ground(corr=True, seed=0,
         call=<frame number>, **ground), DESIGN.md §21: a frame's result does not depend on the order of reading).
@@ -456,9 +458,23 @@ class KITTI(_PairFolder):
         one correspondence per occupied cell of pc1.
         fps (None: off): after the ground removal and the voxel grid and before the transform, the pair is sampled to `fps`
         correspondences by farthest point sampling on the device (flownet.fps_sample(corr=True, num_points=fps), DESIGN.md §30);
-        a frame of fewer distinct positions keeps that many."""
+        a frame of fewer distinct positions keeps that many.
+        outlier (None: off; a dict of OUTLIER_KEYS): after the ground removal and before the voxel grid, the stray points are
+        removed on the device (flownet.remove_outliers(corr=True, **outlier)): by default a correspondence is
+        dropped when it is an outlier in either cloud."""
         from . import _lib, ops
         super(KITTI, self).__init__(transform, device)
+        if outlier is not None:
+            if torch.device(device).type != 'cuda':
+                raise _lib.HplError('KITTI: outlier filters on the device, got device %s (there is no CPU fallback)' % (device,))
+            if not isinstance(outlier, dict) or set(outlier) - set(self.OUTLIER_KEYS):
+                raise _lib.HplError('KITTI: outlier holds %s, got %r' % (', '.join(self.OUTLIER_KEYS), outlier))
+            if outlier.get('by', 'either') not in ('either', 'pc1'):
+                raise _lib.HplError('KITTI: outlier[\'by\'] = %r (\'either\' or \'pc1\')' % (outlier['by'],))
+            ops.outlier_args('KITTI: outlier', outlier.get('mode', 'statistical'), outlier.get('k', 16), outlier.get('radius', 1.0),
+                             outlier.get('std_ratio', 2.0), outlier.get('min_neighbors'))
+            outlier = dict(outlier)
+        self.outlier = outlier
         if fps is not None:
             if torch.device(device).type != 'cuda':
                 raise _lib.HplError('KITTI: fps samples on the device, got device %s (there is no CPU fallback)' % (device,))
@@ -522,6 +538,11 @@ class KITTI(_PairFolder):
             pc1, pc2 = pc1[keep], pc2[keep]
         elif self.remove_ground:
             keep = ~((pc1[:, 1] < -1.4) & (pc2[:, 1] < -1.4))
+            pc1, pc2 = pc1[keep], pc2[keep]
+        if self.outlier is not None:
+            from .flownet import remove_outliers
+            t1, t2 = (torch.from_numpy(np.ascontiguousarray(p[:, :3].T, dtype=np.float32)).to(self.device) for p in (pc1, pc2))
+            keep = remove_outliers(t1, t2, corr=True, return_mask=True, **self.outlier)[-1][0]
             pc1, pc2 = pc1[keep], pc2[keep]
         if self.voxel is not None:
             from .flownet import voxel_downsample
@@ -621,12 +642,13 @@ class KITTIRaw(KITTI):
     for the tree process_kitti.py would have written; the keywords are KITTI's."""
 
     def __init__(self, transform, raw_root, calib_dir, remove_ground=True, mapping_file=None, device='cuda', ground=None,
-                 voxel=None, voxel_mode='centroid', fps=None):
+                 voxel=None, voxel_mode='centroid', fps=None, outlier=None):
         _need_device('KITTIRaw', device)
         if calib_dir is None or not os.path.isdir(calib_dir):
             raise FileNotFoundError('KITTIRaw: calib_dir %r is not a directory (the back-projection needs every frame\'s P_rect_02)' % (calib_dir,))
         super(KITTIRaw, self).__init__(transform, raw_root, remove_ground=remove_ground, mapping_file=mapping_file, device=device,
-                                       calib_dir=calib_dir, ground=ground, voxel=voxel, voxel_mode=voxel_mode, fps=fps)
+                                       calib_dir=calib_dir, ground=ground, voxel=voxel, voxel_mode=voxel_mode, fps=fps,
+                                       outlier=outlier)
         self.P = {nm: read_kitti_P(os.path.join(calib_dir, nm + '.txt')) for nm in (os.path.basename(d) for d in self.samples)}
 
     def _sample_dirs(self, raw_root):

@@ -865,6 +865,18 @@ def parse_args(argv=None):
                          '(flownet.voxel_downsample, DESIGN.md §24); default off')
     ap.add_argument('--voxel-mode', default=None, choices=['centroid', 'nearest'],
                     help='--voxel: a cell becomes the mean of its points (centroid, the default) or the point nearest to it')
+    ap.add_argument('--outlier', default=None, choices=['statistical', 'radius'],
+                    help='--dataset KITTI: remove every frame\'s stray points on the device after the ground removal and before '
+                         '--voxel: a correspondence is dropped when it is an outlier in either cloud (flownet.remove_outliers, '
+                         'DESIGN.md §33); default off')
+    ap.add_argument('--outlier-k', type=int, default=None, metavar='K',
+                    help='--outlier statistical: the nearest neighbours of the mean distance, 1 .. 32 (default 16)')
+    ap.add_argument('--outlier-radius', type=float, default=None, metavar='R',
+                    help='--outlier: the search radius in metres, finite and > 0 (default 1.0)')
+    ap.add_argument('--outlier-std-ratio', type=float, default=None, metavar='S',
+                    help='--outlier statistical: kept up to mu + S sigma of the mean distances, finite and >= 0 (default 2.0)')
+    ap.add_argument('--outlier-min-neighbors', type=int, default=None, metavar='M',
+                    help='--outlier radius: kept with at least M neighbours within the radius, >= 1 (default 2)')
     ap.add_argument('--fps', type=int, default=None, metavar='K',
                     help='--dataset KITTI: sample every frame to K correspondences (an int >= 1) by farthest point sampling on the '
                          'device, after the ground removal and --voxel and before the sampling of --points '
@@ -998,6 +1010,24 @@ def parse_args(argv=None):
         ap.error('--voxel takes a finite value > 0')
     if a.voxel_mode is not None and a.voxel is None:
         ap.error('--voxel-mode applies to --voxel')
+    if a.outlier is not None and a.dataset != 'KITTI':
+        ap.error('--outlier applies to --dataset KITTI')
+    if a.outlier_k is not None and (a.outlier != 'statistical' or not 1 <= a.outlier_k <= 32):
+        ap.error('--outlier-k takes 1 .. 32 and applies to --outlier statistical')
+    if a.outlier_radius is not None and (a.outlier is None or not 0 < a.outlier_radius < float('inf')):
+        ap.error('--outlier-radius takes a finite value > 0 and applies to --outlier')
+    if a.outlier_std_ratio is not None and (a.outlier != 'statistical' or not 0 <= a.outlier_std_ratio < float('inf')):
+        ap.error('--outlier-std-ratio takes a finite value >= 0 and applies to --outlier statistical')
+    if a.outlier_min_neighbors is not None and (a.outlier != 'radius' or not 1 <= a.outlier_min_neighbors <= 2 ** 31 - 1):
+        ap.error('--outlier-min-neighbors takes an int >= 1 and applies to --outlier radius')
+    a.outlier_filter = None
+    if a.outlier is not None:
+        a.outlier_filter = {'mode': a.outlier, 'radius': 1.0 if a.outlier_radius is None else a.outlier_radius}
+        if a.outlier == 'statistical':
+            a.outlier_filter.update(k=16 if a.outlier_k is None else a.outlier_k,
+                                    std_ratio=2.0 if a.outlier_std_ratio is None else a.outlier_std_ratio)
+        else:
+            a.outlier_filter.update(min_neighbors=2 if a.outlier_min_neighbors is None else a.outlier_min_neighbors)
     if a.fps is not None and a.dataset != 'KITTI':
         ap.error('--fps applies to --dataset KITTI')
     if a.fps is not None and a.fps < 1:
@@ -1124,7 +1154,7 @@ def _real_data(a, tr, dev, rank, world):
         kitti = data_mod.KITTIRaw if a.raw_root is not None else data_mod.KITTI
         val = kitti(process(True), a.raw_root if a.raw_root is not None else a.data_root, device=dev, calib_dir=a.kitti_calib,
                     remove_ground='plane' if a.ground_fit else True, ground=a.ground_fit, voxel=a.voxel,
-                    voxel_mode=a.voxel_mode or 'centroid', fps=a.fps)
+                    voxel_mode=a.voxel_mode or 'centroid', fps=a.fps, outlier=a.outlier_filter)
         train = None
         if a.kitti_calib is None:
             log('note: 2D metrics (EPE2D, Acc2D) need the frames\' cameras: pass --kitti-calib DIR (calib_cam_to_cam)')
@@ -1151,6 +1181,9 @@ def _real_data(a, tr, dev, rank, world):
     if train is None:
         res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid,
                           segment=a.segment, icp=a.icp, objects=a.objects)
+        if a.outlier_filter:                # the run's report carries the filter it ran with (the mode as OUTLIER_MODES' number)
+            res['outlier_mode'] = float(ops.OUTLIER_MODES[a.outlier_filter['mode']])
+            res.update(('outlier_' + k, float(v)) for k, v in a.outlier_filter.items() if k != 'mode')
         log(' '.join('%s %.4f' % kv for kv in res.items()))
         return res
     return tr.fit(_Shard(train, rank, world, a.pairs, equal=True), val, a.epochs, a.ckpt_dir, log=log, shuffle=True,

@@ -987,6 +987,70 @@ def remove_ground(pc1, pc2, sf=None, corr=True, return_mask=False, **kw):
     return res + (masks,) if return_mask else res
 
 
+# ----------------------------------------------------------------------------- outlier removal
+OUTLIER_BY = ('either', 'pc1')
+
+
+def remove_outliers(pc1, pc2=None, sf=None, corr=True, by='either', return_mask=False, **kw):
+    """The pair(s) without their stray points, by ONE ops.outlier_filter call.  pc1 / pc2 / sf in the forms
+    voxel_downsample takes: (3, N) tensors (one pair), (B, 3, N) tensors, or lists of B (3, N_b) tensors; pc2 and sf may be
+    None.  kw: mode, k, radius, std_ratio, min_neighbors of ops.outlier_filter.
+    corr=True (the clouds of a pair correspond point to point, so they hold as many points), by='either': the op runs over the
+    2 B clouds -- the pc1 clouds first, then the pc2 clouds -- and a correspondence is dropped when it is an outlier in either
+    cloud; pc1, pc2 and sf are indexed together, so pc2' - pc1' keeps sf' exactly.  At most 32 pairs a call.  (Without pc2:
+    as by='pc1'.)
+    corr=True, by='pc1': pc1's clouds decide; pc2 and sf follow through keep_idx.  At most 64 pairs a call.
+    corr=False: each of the 2 B clouds is filtered on its own; sf follows pc1.  At most 32 pairs a call.
+    One read-back: the pair masks (by='either', or return_mask) or the kept counts.
+    -> (pc1 list of (3, K_b), pc2 list or None, sf list or None, thresh (B, 4) float32, stats (B, 4) int32 -- (2, B, 4) both
+    where the op ran over 2 B clouds --[, masks]): return_mask (with corr=True) appends the pairs' keep masks as host numpy
+    bool arrays."""
+    who = 'remove_outliers'
+    if set(kw) - {'mode', 'k', 'radius', 'std_ratio', 'min_neighbors'}:
+        raise _lib.HplError('%s takes mode, k, radius, std_ratio and min_neighbors of ops.outlier_filter, got %s' % (
+            who, sorted(set(kw) - {'mode', 'k', 'radius', 'std_ratio', 'min_neighbors'})))
+    if by not in OUTLIER_BY:
+        raise _lib.HplError('%s: by = %r (%s)' % (who, by, ' or '.join(repr(x) for x in OUTLIER_BY)))
+    if return_mask and not corr:
+        raise _lib.HplError('%s: return_mask comes with corr=True' % who)
+    ops.outlier_args(who, kw.get('mode', 'statistical'), kw.get('k', 16), kw.get('radius', 1.0), kw.get('std_ratio', 2.0),
+                     kw.get('min_neighbors'))
+    p = _pairs_in(who, pc1, pc2, sf, corr)
+    c1, c2, fl = p.c1, p.c2, p.fl
+    B = len(c1)
+    both = c2 is not None and not (corr and by == 'pc1')         # the op runs over the 2 B clouds
+    if both and 2 * B > 64:
+        raise _lib.HplError('%s: %d pairs (1 .. 32 a call)' % (who, B))
+    clouds = c1 + c2 if both else c1
+    prefix = _prefix_of(c.shape[1] for c in clouds)
+    keep, keep_idx, _, _, thresh, stats = ops.outlier_filter(torch.cat(clouds, dim=1), prefix=prefix, **kw)
+    n1 = prefix[B]
+    o1, o2, of, masks = [], ([] if c2 is not None else None), ([] if fl is not None else None), []
+    if corr and (both or return_mask):
+        host = ((keep[:n1] & keep[n1:]) if both else keep).bool().cpu().numpy()        # the one read-back
+        for b in range(B):
+            m = host[prefix[b]:prefix[b + 1]]
+            masks.append(m)
+            idx = torch.from_numpy(m.nonzero()[0]).to(keep.device)
+            o1.append(c1[b].index_select(1, idx))
+            if c2 is not None:
+                o2.append(c2[b].index_select(1, idx))
+            if fl is not None:
+                of.append(fl[b].index_select(1, idx))
+    else:
+        kept = stats[:, 1].cpu().tolist()                                               # the one read-back
+        for b in range(B):
+            i1 = keep_idx[prefix[b]:prefix[b] + kept[b]].long() - prefix[b]
+            o1.append(c1[b].index_select(1, i1))
+            if c2 is not None:
+                o2.append(c2[b].index_select(1, i1 if corr else
+                                             keep_idx[prefix[B + b]:prefix[B + b] + kept[B + b]].long() - prefix[B + b]))
+            if fl is not None:
+                of.append(fl[b].index_select(1, i1))
+    res = (o1, o2, of, thresh.view(2, B, 4) if both else thresh, stats.view(2, B, 4) if both else stats)
+    return res + (masks,) if return_mask else res
+
+
 # ----------------------------------------------------------------------------- voxel-grid downsampling
 def voxel_downsample(pc1, pc2=None, sf=None, voxel=0.1, mode='centroid', corr=True, origin=(0, 0, 0), return_index=False):
     """The pair(s) on a voxel grid of edge `voxel`, one point per occupied cell, by ONE ops.voxel_downsample call (DESIGN.md

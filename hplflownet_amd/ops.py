@@ -733,6 +733,79 @@ def normals(pc, k=16, radius=1.0, viewpoint=None, prefix=None, return_neighbors=
     return res + (nbr, nbr_d2) if return_neighbors else res
 
 
+# --------------------------------------------------------------------------- outlier removal
+OUTLIER_MODES = {'statistical': 0, 'radius': 1}
+
+
+def outlier_args(who, mode, k, radius, std_ratio, min_neighbors):
+    """(the mode's number, k, radius, std_ratio, min_neighbors as the library takes them) or an HplError: k 1 .. 32 and std_ratio
+    finite and >= 0 in mode 'statistical', which refuses min_neighbors; min_neighbors 1 .. 2^31 - 1 required in mode 'radius'."""
+    if mode not in OUTLIER_MODES:
+        raise _lib.HplError('%s: mode = %r (%s)' % (who, mode, ' or '.join(repr(m) for m in OUTLIER_MODES)))
+    radius = _scalar(who, 'radius', radius)
+    if mode == 'statistical':
+        _int_in(who, 'k', k, 1, 32)
+        std_ratio = _scalar(who, 'std_ratio', std_ratio, True)
+        if min_neighbors is not None:
+            raise _lib.HplError('%s: min_neighbors applies to mode \'radius\', got %r in mode \'statistical\'' % (who, min_neighbors))
+        min_neighbors = 0
+    else:
+        if min_neighbors is None:
+            raise _lib.HplError('%s: mode \'radius\' needs min_neighbors (an int in 1 .. %d)' % (who, 2 ** 31 - 1))
+        _int_in(who, 'min_neighbors', min_neighbors, 1, 2 ** 31 - 1)
+        k, std_ratio = 0, 0.0
+    return OUTLIER_MODES[mode], k, radius, std_ratio, min_neighbors
+
+
+def outlier_filter(pc, mode='statistical', k=16, radius=1.0, std_ratio=2.0, min_neighbors=None, prefix=None,
+                   return_neighbors=False, out=None):
+    """hpl_outlier_filter on the current stream: the stray points of pc (3, N), exact over all pairs of a cloud
+    (a sorted grid over the cloud, built once a call, finds the candidates).  A point's neighbours are the OTHER points of its
+    cloud within radius.  mode 'statistical': mean_dist = the mean distance to the k (1 .. 32) nearest neighbours, a missing one
+    counted at the radius; per cloud mu and the sample sigma of mean_dist; kept iff mean_dist <= T = mu + std_ratio sigma (the
+    float32 values as returned).  mode 'radius': kept iff the point has at least min_neighbors neighbours.  A point that is not
+    finite or out of the grid's range is removed and takes no part.  prefix (host sequence of B + 1 ints from 0 to N): B <= 64
+    clouds, each filtered on its own.
+    -> (keep (N,) uint8, keep_idx (N,) int32: per cloud from prefix[b] on the packed indices of its kept points, ascending,
+    then -1, mean_dist (N,) float32 (None in mode 'radius'), count (N,) int32: min(k, neighbours), or all neighbours in mode
+    'radius', thresh (B, 4) float32 = (mu, sigma, T, 0), zeros in mode 'radius', stats (B, 4) int32 = (taking part, kept, removed
+    though taking part, not taking part)[, nbr_d2 (N, k) float32: the squared distances ascending, then +inf; mode
+    'statistical' only]).  out: a contiguous (N,) uint8 tensor that takes keep.  The same bits for a cloud alone and in any
+    batch.  No autograd, no host synchronisation, no read-back."""
+    who = 'outlier_filter'
+    m, k, radius, std_ratio, min_neighbors = outlier_args(who, mode, k, radius, std_ratio, min_neighbors)
+    if return_neighbors and m != 0:
+        raise _lib.HplError('outlier_filter: return_neighbors applies to mode \'statistical\'')
+    pc, pc_ld = _soa3(pc, 'pc', who)
+    N, dev = pc.shape[1], pc.device
+    pp = _prefix(prefix, N, who)
+    B = len(pp) - 1
+    if out is None:
+        keep = torch.empty(N, dtype=torch.uint8, device=dev)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (N,) or out.dtype != torch.uint8 or out.device != dev or \
+            not out.is_contiguous():
+        raise _lib.HplError('outlier_filter: out must be a contiguous (%d,) uint8 tensor on %s' % (N, dev))
+    else:
+        keep = out
+    keep_idx = torch.empty(N, dtype=torch.int32, device=dev)
+    mean_dist = torch.empty(N, dtype=torch.float32, device=dev) if m == 0 else None
+    count = torch.empty(N, dtype=torch.int32, device=dev)
+    nbr_d2 = torch.empty((N, k), dtype=torch.float32, device=dev) if return_neighbors else None
+    if N == 0:                                   # nothing to launch: every cloud is empty
+        thresh = torch.zeros((B, 4), dtype=torch.float32, device=dev)
+        stats = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+    else:
+        thresh = torch.empty((B, 4), dtype=torch.float32, device=dev)
+        stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+        lib = _lib.load()
+        ws, st = _room(who, dev, lib.hpl_outlier_filter_workspace_bytes(B, N), _CLOUD_LIMITS, B, N)
+        check(lib.hpl_outlier_filter(pc.data_ptr(), pc_ld, B, _c_prefix(pp), m, k, radius, std_ratio, min_neighbors,
+                                     keep.data_ptr(), keep_idx.data_ptr(), ptr(mean_dist), count.data_ptr(), ptr(nbr_d2),
+                                     thresh.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), st), 'hpl_outlier_filter')
+    res = (keep, keep_idx, mean_dist, count, thresh, stats)
+    return res + (nbr_d2,) if return_neighbors else res
+
+
 # --------------------------------------------------------------------------- moving objects from flow
 def motion_segment(pc, flow, residual, tau=0.1, eps=0.5, dv=float('inf'), min_points=5, max_objects=256, prefix=None, out=None):
     """hpl_motion_segment on the current stream: the points whose residual against a rigid fit exceeds tau

@@ -1494,6 +1494,69 @@ int hpl_icp_plane(const float *src, int64_t src_ld, const float *dst, int64_t ds
                   float *Rt, float *stats, int32_t *match, float *dist2, float *flow, void *workspace, int64_t workspace_bytes,
                   hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Outlier removal on packed ragged clouds (csrc/outlier_filter.hip): the statistical filter (mean distance to the k nearest
+ * neighbours against the cloud's mu + std_ratio sigma) and the radius filter (at least min_neighbors within a radius),
+ * exact, on a sorted grid over the cloud itself.
+ * ------------------------------------------------------------------------ */
+/* Workspace of hpl_outlier_filter for `batch` clouds of n_total points together, in bytes (monotone in n_total); -1 for a
+ * batch outside 1 .. 64 or a count outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_outlier_filter_workspace_bytes(int batch, int64_t n_total);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N).  batch (1 .. 64) clouds: prefix (HOST, batch + 1 ints from 0 to N,
+ * non-decreasing, empty clouds allowed) travels in the kernel arguments.  mode 0 statistical (k 1 .. 32, std_ratio finite and
+ * >= 0; min_neighbors is not read), 1 radius (min_neighbors 1 .. 2^31 - 1; k and std_ratio are not read; mean_dist and nbr_d2
+ * must be NULL).  radius finite and > 0 in both.
+ * The definition is over ALL PAIRS of a cloud; the grid is an accelerator only (tests/outlier_oracle.py restates the
+ * definition in numpy without a grid).
+ * TAKING PART (hpl_normals' rule): cell_k = floor(x_k * (1 / (1.001 * radius))) in float64 (the product 1.001 * radius, the
+ * quotient and the product with x_k each rounded once); a point takes part when its three coordinates are finite and
+ * |cell_k| <= 2^18 - 2 for k = x, y, z.  A point that does not is REMOVED: keep 0, count 0, mean_dist +inf (nbr_d2 +inf); it
+ * is in nobody's neighbourhood and in no statistic.
+ * DISTANCE d2(i, j) = (dx * dx + dy * dy) + dz * dz in float32 with dx = p_i.x - p_j.x, every operation rounded, no
+ * contraction (the arithmetic of hpl_knn_interp and hpl_normals).  r2 = float32(radius * radius), the product in float32.
+ * NEIGHBOURS of a point i that takes part: the OTHER indices j != i of the same cloud that take part with d2(i, j) <= r2 (and
+ * d2 < +inf: a distance that overflows float32 is nobody's).  Another index at the same position is a neighbour with d2 = 0.
+ * STATISTICAL: c_i = min(k, neighbours); the c_i smallest d2, ascending (values only: ties need no index rule);
+ * S = sum_t sqrt((double)d2_t) in float64 in that order from 0, the root correctly rounded;
+ * s = S + (double)(k - c_i) * (double)radius -- a neighbour that was not found counts at the radius: an isolated point gets
+ * `radius`, a stray pair does not look dense --; mean_dist[i] = float32(s / (double)k); count[i] = c_i; nbr_d2 [N][k] float32 =
+ * the list, then +inf.
+ * Per cloud b over its n' participating points and their float32 mean_dist m widened to float64: mu = (sum m) / n';
+ * sigma = sqrt(sum (m - mu)^2 / (n' - 1)) (two passes, the sample form; 0 for n' < 2; mu = 0 for n' = 0);
+ * T = mu + (double)std_ratio * sigma; thresh[b] = float32(mu, sigma, T, 0).  KEEP iff the point takes part and
+ * mean_dist[i] <= thresh[b][2]: the float32 values compared as published, so the classification can be recomputed from the
+ * two outputs alone.  Order of the float64 sums: workgroups of 1024 consecutive points that never straddle clouds; lane l of
+ * 256 adds its points l, l + 256, l + 512, l + 768 in that order from 0; one LDS tree over the lanes (halving strides); the
+ * workgroups' partials folded in 16 strided runs in index order, then the runs in order.  The order depends on the cloud's
+ * point count alone.
+ * RADIUS: count[i] = the number of neighbours (not capped); KEEP iff the point takes part and count[i] >= min_neighbors;
+ * thresh[b] = 0.
+ * keep (N) uint8; keep_idx (N) int32: per cloud from prefix[b] on the packed indices of its kept points, ascending, then -1;
+ * stats [batch][4] int32 = (points taking part, kept, removed though taking part, not taking part); thresh [batch][4]
+ * float32.  An empty cloud of a batch with N > 0 gets zeros in thresh and stats from the call itself.  Each of keep, keep_idx,
+ * mean_dist, count, nbr_d2 may be NULL.
+ * No floating-point atomic; a cloud's outputs are the same bits alone, anywhere in a batch and beside other work.
+ * Stream-ordered, a fixed number of launches: keys, one stable radix sort of (key, 16-byte record), one search launch (a
+ * lane per sorted record; the list of the smallest d2 in registers, instances of 8, 16 and 32 entries, and a count-only
+ * instance for the radius mode); statistical only: two sum launches; then thresh (a workgroup per cloud), classify, scan (a
+ * workgroup per cloud; writes stats) and, with keep_idx, emit.  Beside the sort: 8 launches statistical, 6 radius, one
+ * fewer without keep_idx.  No copy back, no host synchronisation; no lane or workgroup waits for another; every loop is
+ * bounded by a cell's population, log2 N or a cloud's workgroups.  The search costs the population of 27 cells per point: all
+ * points in one cell is quadratic.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_outlier_filter_workspace_bytes(batch, N).
+ * HPL_EINVAL before any launch (and without a device): null pc / prefix / thresh / stats / workspace; batch or mode out of
+ * range; radius <= 0 or not finite; statistical: k outside 1 .. 32, std_ratio < 0 or not finite; radius: min_neighbors < 1,
+ * mean_dist or nbr_d2 given; a prefix that does not start at 0 or decreases; N >= 2^31 / 3; N k >= 2^31 with nbr_d2 given; a
+ * row stride below N; misaligned arrays; a workspace that is too small or misaligned; an output that overlaps pc, the
+ * workspace or another output.  N == 0 is a no-op. */
+int hpl_outlier_filter(const float *pc, int64_t pc_ld, int batch, const int64_t *prefix /* HOST */,
+                       int mode /* 0 statistical, 1 radius */, int k, float radius, float std_ratio, int min_neighbors,
+                       uint8_t *keep /* (N) or NULL */, int32_t *keep_idx /* (N) or NULL */,
+                       float *mean_dist /* (N) or NULL */, int32_t *count /* (N) or NULL */,
+                       float *nbr_d2 /* [N][k] or NULL, statistical only */,
+                       float *thresh /* [batch][4] */, int32_t *stats /* [batch][4] */,
+                       void *workspace, int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
