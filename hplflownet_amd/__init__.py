@@ -15,13 +15,15 @@ Public surface (mirrors the reference's operator interface for the path):
     voxel_downsample                                             (voxel-grid downsampling; flownet.py, ops.voxel_downsample)
     fps_sample                                                   (farthest point sampling; flownet.py, ops.fps)
     frames_from_kitti, frames_from_ft3d                          (clouds from raw disparity / flow maps; flownet.py, ops.frames_from_*)
+    render_maps, visibility, flow_to_kitti_maps                  (maps from clouds: z-buffer, visibility, KITTI's PNG values;
+                                                                  flownet.py, ops.render_maps, ops.maps_to_kitti)
 The arithmetic lives in libhplbcl.so (csrc/*.hip, C ABI in include/hpl_bcl.h).
 """
 from .bcl import (BilateralConvFlex, BilateralCorrelationFlex, Conv1dReLU, Conv2dReLU, Conv3dReLU,  # noqa: F401
                   sparse_sum)
-from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, estimate_normals, fps_sample,  # noqa: F401
+from .flownet import (DenseFlow, DeviceLattice, HPLFlowNet, HPLFlowNetShallow, estimate_normals, flow_to_kitti_maps, fps_sample,  # noqa: F401
                       frames_from_ft3d, frames_from_kitti, icp_register, piecewise_rigid, remove_ground, remove_outliers, rigid_refine, segment_motion,
-                      selfsup_loss,
+                      render_maps, selfsup_loss, visibility,
                       voxel_downsample)
 from .lattice import GenerateDataUnsymmetric, to_reference_format  # noqa: F401
 

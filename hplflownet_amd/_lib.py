@@ -258,6 +258,14 @@ _SIGNATURES = {
     'hpl_outlier_filter_workspace_bytes': (c_i64, [ctypes.c_int, c_i64]),
     'hpl_outlier_filter': (ctypes.c_int, [c_vp, c_i64, ctypes.c_int, ctypes.POINTER(c_i64), ctypes.c_int, ctypes.c_int, c_f32, c_f32,
                                           ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'hpl_render_workspace_bytes': (c_i64, [ctypes.c_int, c_i64]),
+    'hpl_render_maps': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_int, ctypes.c_int, ctypes.POINTER(c_i64),
+                                       ctypes.POINTER(c_f32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(c_i64), ctypes.c_int, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_i64,
+                                       c_vp, c_vp, c_vp, c_i64, c_vp]),
+    'hpl_maps_to_kitti': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, ctypes.c_int, ctypes.POINTER(c_i64),
+                                         ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_i64),
+                                         ctypes.POINTER(c_f32), c_f32, ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     'hpl_icp_plane_workspace_bytes': (c_i64, [ctypes.c_int, c_i64, c_i64]),
     'hpl_icp_plane': (ctypes.c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, ctypes.c_int, ctypes.POINTER(c_i64),
                                      ctypes.POINTER(c_i64), ctypes.c_int, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp,

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libhplbcl.so')
 DIAG_LIB = os.path.join(HERE, 'libhplbcl_diag.so')
-SOURCES = ['index_ops.hip', 'row_order.hip', 'splat_slice.hip', 'train_ops.hip', 'pair_loss.hip', 'gconv.hip', 'gconv3.hip', 'wgrad3.hip', 'lattice.hip', 'lattice_fused.hip', 'executor.hip', 'lattice_builder.hip', 'lattice_query.hip', 'knn_interp.hip', 'rigid_fit.hip', 'motion_segment.hip', 'object_fit.hip', 'selfsup_loss.hip', 'ground_fit.hip', 'voxel_grid.hip', 'fps.hip', 'icp.hip', 'icp_plane.hip', 'normals.hip', 'outlier_filter.hip', 'frames.hip', 'batch_io.hip', 'metrics.hip', 'transforms.hip']
+SOURCES = ['index_ops.hip', 'row_order.hip', 'splat_slice.hip', 'train_ops.hip', 'pair_loss.hip', 'gconv.hip', 'gconv3.hip', 'wgrad3.hip', 'lattice.hip', 'lattice_fused.hip', 'executor.hip', 'lattice_builder.hip', 'lattice_query.hip', 'knn_interp.hip', 'rigid_fit.hip', 'motion_segment.hip', 'object_fit.hip', 'selfsup_loss.hip', 'ground_fit.hip', 'voxel_grid.hip', 'fps.hip', 'icp.hip', 'icp_plane.hip', 'normals.hip', 'outlier_filter.hip', 'frames.hip', 'render.hip', 'batch_io.hip', 'metrics.hip', 'transforms.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
          '-ffp-contract=off',   # every fused multiply-add in the kernels is an explicit fmaf
          '-Wall', '-Wno-unused-function']

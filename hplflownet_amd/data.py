@@ -48,15 +48,18 @@ import numpy as np
 import torch
 
 __all__ = ['ProcessData', 'Augmentation', 'DeviceProcessData', 'DeviceAugmentation', 'FlyingThings3DSubset', 'KITTI', 'Sample',
-           'read_kitti_camera', 'read_kitti_P', 'read_png', 'read_pfm', 'read_flo', 'KITTIRaw', 'FlyingThings3DRaw']
+           'read_kitti_camera', 'read_kitti_P', 'read_png', 'write_png', 'read_pfm', 'read_flo', 'KITTIRaw', 'FlyingThings3DRaw']
 
 #: (f, cx, cy, constx, consty, constz) of every FlyingThings3D frame (utils/geometry.py:59 defaults)
 FT3D_CAMERA = (-1050.0, 479.5, 269.5, 0.0, 0.0, 0.0)
 
 
 class Sample(tuple):
-    """(pc1, pc2, sf) of a reader, with `camera`: the (f, cx, cy, constx, consty, constz) of the frame it came from, or None."""
+    """(pc1, pc2, sf) of a reader, with `camera`: the (f, cx, cy, constx, consty, constz) of the frame it came from, or None;
+    `frame`: that frame's name in its tree (KITTI: NNNNNN); `size`: the (H, W) of its raw maps where the reader saw them."""
     camera = None
+    frame = None
+    size = None
 
 
 def read_kitti_camera(path):
@@ -129,6 +132,30 @@ def read_png(path):
     rows = np.ascontiguousarray(ops.png_unfilter(raw, height, stride, bpp))
     px = rows if depth == 8 else rows.view('>u2').astype(np.uint16)
     return px.reshape(height, width) if channels == 1 else px.reshape(height, width, 3)
+
+
+def write_png(path, arr):
+    """Writes what read_png reads: a uint8 or uint16 array of shape (H, W) (greyscale) or (H, W, 3) (RGB) as a non-interlaced
+    PNG of the same depth -- KITTI's disparity maps are 16-bit grey, its flow maps 16-bit RGB.  Every row goes out with filter
+    type 0 (None), deflated with zlib; the chunks are IHDR, one IDAT and IEND."""
+    import struct
+    import zlib
+    arr = np.asarray(arr)
+    if arr.dtype not in (np.uint8, np.uint16) or arr.ndim not in (2, 3) or (arr.ndim == 3 and arr.shape[2] != 3) or \
+            arr.shape[0] < 1 or arr.shape[1] < 1:
+        raise ValueError('write_png takes uint8 or uint16 arrays of shape (H, W) or (H, W, 3) with H, W >= 1, got %s %s' % (
+            arr.dtype, arr.shape))
+    height, width = arr.shape[:2]
+    samples = arr.astype('>u2') if arr.dtype == np.uint16 else arr           # (PNG samples are big-endian)
+    rows = np.ascontiguousarray(samples).reshape(height, -1).view(np.uint8)
+    raw = np.concatenate([np.zeros((height, 1), np.uint8), rows], axis=1).tobytes()      # a filter byte 0 leads every row
+
+    def chunk(kind, body):
+        return struct.pack('>I', len(body)) + kind + body + struct.pack('>I', zlib.crc32(kind + body) & 0xffffffff)
+
+    header = struct.pack('>IIBBBBB', width, height, 8 * arr.dtype.itemsize, 2 if arr.ndim == 3 else 0, 0, 0, 0)
+    with open(path, 'wb') as fd:
+        fd.write(b'\x89PNG\r\n\x1a\n' + chunk(b'IHDR', header) + chunk(b'IDAT', zlib.compress(raw, 6)) + chunk(b'IEND', b''))
 
 
 def read_pfm(path):
@@ -388,6 +415,10 @@ class _PairFolder(object):
         """The camera of the frame in directory `path`, None if the reader has none."""
         return None
 
+    def size_of(self, path):
+        """The (H, W) of the raw maps of the frame in directory `path`, None if the reader never saw them."""
+        return None
+
     def __getitem__(self, index):
         """-> (pc1, pc2, sf) float32 device tensors (3, N); falls on to the next sample if the
         transform rejects this one (the reference draws a random replacement, :44-47)."""
@@ -398,7 +429,7 @@ class _PairFolder(object):
                 out = self.transform(self.load(path))
                 if out[0] is not None:
                     s_ = out if isinstance(out, Sample) else Sample(out)
-                    s_.camera = self.camera_of(path)
+                    s_.camera, s_.frame, s_.size = self.camera_of(path), os.path.basename(path), self.size_of(path)
                     return s_
                 continue
             out = self.transform(self.load(path)) if self.transform is not None else None
@@ -407,7 +438,7 @@ class _PairFolder(object):
                 out = (pc1, pc2, pc2 - pc1)
             if out[0] is not None:
                 s_ = Sample(torch.from_numpy(np.ascontiguousarray(a[:, :3].T, dtype=np.float32)).to(self.device) for a in out)
-                s_.camera = self.camera_of(path)
+                s_.camera, s_.frame, s_.size = self.camera_of(path), os.path.basename(path), self.size_of(path)
                 return s_
         raise RuntimeError('no usable sample under %s' % self.root)
 
@@ -650,6 +681,10 @@ class KITTIRaw(KITTI):
                                        calib_dir=calib_dir, ground=ground, voxel=voxel, voxel_mode=voxel_mode, fps=fps,
                                        outlier=outlier)
         self.P = {nm: read_kitti_P(os.path.join(calib_dir, nm + '.txt')) for nm in (os.path.basename(d) for d in self.samples)}
+        self.sizes = {}                              # (H, W) of every frame loaded so far
+
+    def size_of(self, path):
+        return self.sizes.get(os.path.basename(path))
 
     def _sample_dirs(self, raw_root):
         self.root = os.path.join(raw_root, 'training')
@@ -661,5 +696,7 @@ class KITTIRaw(KITTI):
     def _load_pair(self, path):
         from .flownet import frames_from_kitti
         name = os.path.basename(path)
-        pc1, pc2 = frames_from_kitti([read_kitti_raw_frame(os.path.dirname(self.root), name) + (self.P[name],)], device=self.device)[:2]
+        raw = read_kitti_raw_frame(os.path.dirname(self.root), name)
+        self.sizes[name] = tuple(raw[0].shape)
+        pc1, pc2 = frames_from_kitti([raw + (self.P[name],)], device=self.device)[:2]
         return _saved(pc1[0]), _saved(pc2[0])

@@ -307,7 +307,7 @@ class Trainer(object):
 
     @torch.no_grad()
     def validate(self, data, batch_size=1, ragged=False, dense=False, dense_fill=None, dense_k=3, rigid=None, segment=None,
-                 icp=None, objects=None):
+                 icp=None, objects=None, write=None):
         """Metrics of `data` (means over its pairs, all ranks).  batch_size = B > 1: runs of consecutive pairs with the same
         point counts are evaluated B at a time (one batched lattice build and one batched forward); a pair whose counts
         differ from its neighbours' forms a batch of its own.  ragged=True: consecutive pairs are batched whatever their
@@ -349,7 +349,11 @@ class Trainer(object):
         piecewise-rigid flow (the ego-motion's rigid flow at its inliers, an object's at the inliers of its fit, the sampled flow
         elsewhere) goes through one more metrics launch into an array of its own.  Behind every other key, and changing none,
         the keys gain piecewise_<metric> plus piecewise_object_inliers: the share of a pair's points whose flow an object fit
-        replaced, from integer counts that stay on the device until the read-back."""
+        replaced, from integer counts that stay on the device until the read-back.
+
+        write=callable(samples, pc1s, flows) (KittiWriter): called behind every forward with the flow that is
+        evaluated -- the dense flow at all valid points with dense=True, else the sampled one -- and the clouds it belongs to.
+        It changes no key and no value."""
         if dense_fill is not None and not dense:
             raise HplError('validate: dense_fill applies to dense=True')
         if rigid is not None:
@@ -426,6 +430,8 @@ class Trainer(object):
             def add(preds, samples, batched=None):
                 ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras_of(samples), sums,
                                        nxt[0], stage)
+                if write is not None and not dense:
+                    write(samples, [s_[0] for s_ in samples], list(preds))
                 fitted = None
                 if rigid is not None:
                     from .flownet import rigid_refine
@@ -469,6 +475,8 @@ class Trainer(object):
                 fulls = [s_.dense for s_ in samples]
                 ops.flow_metrics_pairs(qflows, [f[2] for f in fulls], [f[0] for f in fulls], cameras_of(samples), dsums, nxt[0],
                                        dstage)
+                if write is not None:
+                    write(samples, [f[0] for f in fulls], list(qflows))
                 for b, c in enumerate(covs):
                     dcov[nxt[0] + b, 0] = c.double().mean()
                     dcov[nxt[0] + b, 1] = (c == 1).double().mean()
@@ -891,8 +899,24 @@ def parse_args(argv=None):
                     help='--ground plane: largest tilt of the plane\'s normal from --ground-up in degrees (0 <= DEG < 90, default 20)')
     ap.add_argument('--ground-up', type=float, nargs=3, default=None, metavar=('X', 'Y', 'Z'),
                     help='--ground plane: the up direction (finite, not zero; default 0 1 0, KITTI\'s camera frame as the reader stores it)')
+    ap.add_argument('--write-kitti', default=None, metavar='DIR',
+                    help='--evaluate --dataset KITTI: write every evaluated frame\'s flow -- the dense one with --dense, else the '
+                         'sampled one -- as KITTI\'s three 16-bit PNGs DIR/disp_0|disp_1|flow/NNNNNN_10.png (DESIGN.md §34); the '
+                         'camera is the frame\'s of --kitti-calib, the size the raw frame\'s with --raw-root, else --write-size')
+    ap.add_argument('--write-footprint', type=int, default=None, metavar='R',
+                    help='--write-kitti: every point covers the (2 R + 1)^2 pixels around its own (0 .. 4, default 0)')
+    ap.add_argument('--write-size', type=int, nargs=2, default=None, metavar=('H', 'W'),
+                    help='--write-kitti without --raw-root: the size of the maps')
     ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
     a = ap.parse_args(argv)
+    if a.write_kitti is not None and (not a.evaluate or a.dataset != 'KITTI' or a.kitti_calib is None):
+        ap.error('--write-kitti applies to --evaluate --dataset KITTI with --kitti-calib DIR')
+    if a.write_footprint is not None and (a.write_kitti is None or not 0 <= a.write_footprint <= 4):
+        ap.error('--write-footprint takes 0 .. 4 and applies to --write-kitti')
+    if a.write_size is not None and (a.write_kitti is None or a.raw_root is not None or min(a.write_size) < 1):
+        ap.error('--write-size takes two sizes >= 1 and applies to --write-kitti without --raw-root')
+    if a.write_kitti is not None and a.raw_root is None and a.write_size is None:
+        ap.error('--write-kitti without --raw-root needs --write-size H W')
     if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
         ap.error('--batch-size takes 1 .. 64 and applies to --evaluate (training takes one pair per step)')
     if a.train_batch_size is not None and (a.evaluate or not 1 <= a.train_batch_size <= 64):
@@ -1105,6 +1129,36 @@ class _Both(object):
         return self.sampled(data)
 
 
+class KittiWriter(object):
+    """validate(write=...): the evaluated flow of every frame as KITTI's three 16-bit PNGs below `directory` --
+    disp_0/NNNNNN_10.png, disp_1/NNNNNN_10.png, flow/NNNNNN_10.png -- by one flownet.flow_to_kitti_maps call per forward
+    (DESIGN.md §34).  The camera is the sample's, the one the 2D metrics use; the size is the sample's raw frame's, else `size`.
+    Each call reads its maps back: it is off unless asked for."""
+
+    def __init__(self, directory, footprint=0, size=None, baseline=0.54):
+        self.directory, self.footprint, self.size, self.baseline = directory, int(footprint), size, baseline
+        self.written = []
+        for sub in ('disp_0', 'disp_1', 'flow'):
+            os.makedirs(os.path.join(directory, sub), exist_ok=True)
+
+    def __call__(self, samples, pc1s, flows):
+        from .flownet import flow_to_kitti_maps
+        Ps, sizes = [], []
+        for s_ in samples:
+            cam, size, frame = getattr(s_, 'camera', None), getattr(s_, 'size', None) or self.size, getattr(s_, 'frame', None)
+            if cam is None or size is None or frame is None:
+                raise HplError('KittiWriter: a sample needs its camera, its frame\'s name and a size (frame %r, camera %r, size %r)' % (
+                    frame, cam, size))
+            f, cx, cy, kx, ky, kz = cam          # (read_kitti_camera: f = -P00; the float32 values come back exactly)
+            Ps.append([-f, 0.0, cx, kx, 0.0, -f, cy, ky, 0.0, 0.0, 1.0, kz])
+            sizes.append(tuple(size))
+        maps = flow_to_kitti_maps(list(pc1s), list(flows), Ps, sizes, baseline=self.baseline, footprint=self.footprint)
+        for s_, planes in zip(samples, maps):
+            for sub, x in zip(('disp_0', 'disp_1', 'flow'), planes):
+                data_mod.write_png(os.path.join(self.directory, sub, s_.frame + '_10.png'), x)
+            self.written.append(s_.frame)
+
+
 class DenseFrames(object):
     """A reader whose samples also carry `.dense` = (pc1, pc2, sf) of every valid point of their frame, (3, M) float32 device
     tensors in index order with sf = pc2 - pc1: `full` is a ProcessData / DeviceProcessData with num_points = 0 and
@@ -1179,8 +1233,9 @@ def _real_data(a, tr, dev, rank, world):
         val = DenseFrames(val, full)
     val = _Shard(val, rank, world, cap)
     if train is None:
+        write = KittiWriter(a.write_kitti, a.write_footprint or 0, a.write_size) if a.write_kitti is not None else None
         res = tr.validate(val, a.batch_size, a.ragged, dense=a.dense, dense_fill=a.dense_fill, dense_k=a.dense_k, rigid=a.rigid,
-                          segment=a.segment, icp=a.icp, objects=a.objects)
+                          segment=a.segment, icp=a.icp, objects=a.objects, write=write)
         if a.outlier_filter:                # the run's report carries the filter it ran with (the mode as OUTLIER_MODES' number)
             res['outlier_mode'] = float(ops.OUTLIER_MODES[a.outlier_filter['mode']])
             res.update(('outlier_' + k, float(v)) for k, v in a.outlier_filter.items() if k != 'mode')

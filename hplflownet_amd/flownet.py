@@ -1189,6 +1189,106 @@ def frames_from_ft3d(frames, near=None, f=-1050.0, cx=479.5, cy=269.5, device='c
     return _frame_views(pc1, pc2, pixel, counts, hh, ww)
 
 
+# ----------------------------------------------------------------------------- maps from clouds
+def _per_frame(who, name, x, B, width):
+    """B host rows of `width` numbers from one row for all frames or a sequence of B rows."""
+    try:
+        rows = [x] * B if len(x) == width and not hasattr(x[0], '__len__') else list(x)
+        rows = [tuple(r) for r in rows]
+    except TypeError:
+        rows = []
+    if len(rows) != B or any(len(r) != width for r in rows):
+        raise _lib.HplError('%s: %s is one row of %d numbers or one for each of the %d clouds' % (who, name, width, B))
+    return rows
+
+
+def _render_in(who, pc, camera, size):
+    """(clouds, form, packed cloud, prefix, cameras, heights, widths) of the operands render_maps and visibility take."""
+    clouds, form = _cloud_forms(pc, who, 'pc', rows3=True)
+    B = len(clouds)
+    sizes = [(int(h), int(w)) for h, w in _per_frame(who, 'size', size, B, 2)]
+    prefix = _prefix_of([int(c.shape[1]) for c in clouds])
+    return clouds, form, _packed(pc, clouds, form), prefix, _per_frame(who, 'camera', camera, B, 6), [s[0] for s in sizes], [s[1] for s in sizes]
+
+
+def _per_cloud(x, form, prefix):
+    """A packed (sum N_b,) per-point result in the form of the operand: (B, N), (N,) or a list of (N_b,) views."""
+    if form is None:
+        return x.view(len(prefix) - 1, -1)
+    if form is False:
+        return x
+    return [x[prefix[b]:prefix[b + 1]] for b in range(len(prefix) - 1)]
+
+
+def visibility(pc, camera, size, footprint=1, rel_tol=0.02, abs_tol=0.0, near=1e-3):
+    """Which points of the cloud(s) pc a camera sees, by ONE ops.render_maps call: a point is visible when its
+    pixel lies in the image and no point that covers that pixel is nearer than it by more than the tolerance -- zc <= zmin *
+    (1 + rel_tol) + abs_tol.  pc: a (3, N) cloud, a (B, 3, N) batch or a list of (3, N_b) tensors; camera: one (f, cx, cy,
+    constx, consty, constz) or one per cloud; size: one (H, W) or one per cloud.  For "is pc1 + flow hidden in frame 2" pass the
+    warped cloud together with the second frame's cloud and read the mask of the former.  footprint: every point covers the
+    (2 footprint + 1)^2 pixels around its own -- with 0 a sparse cloud leaks: far points show through the gaps between near
+    ones.  The defaults footprint=1, rel_tol=0.02 are starting values; they are not measured on real frames.
+    -> a boolean mask in the form of pc: (N,), (B, N) or a list of (N_b,).  No read-back."""
+    who = 'visibility'
+    _, form, cloud, prefix, cams, hh, ww = _render_in(who, pc, camera, size)
+    res = ops.render_maps(cloud, cams, hh, ww, footprint=footprint, rel_tol=rel_tol, abs_tol=abs_tol, near=near, prefix=prefix)
+    return _per_cloud(res[4].bool(), form, prefix)
+
+
+def render_maps(pc, camera, size, attrs=None, footprint=0, rel_tol=0.0, abs_tol=0.0, near=1e-3):
+    """The cloud(s) pc splatted into one image each by ONE ops.render_maps call and one read-back, the stats.
+    pc, camera, size: as visibility takes them; attrs: None, or channels that ride with the points -- a (C, N) tensor for one
+    cloud, (B, C, N) for a batch, a list of (C, N_b) -- with C <= 8.  The renderer is a point splat, no surface reconstruction:
+    the footprint is in pixels and is not scaled by depth.
+    -> (winner: list of (H_b, W_b) int32 views, the cloud-local index of each pixel's nearest point or -1; depth: list of
+    (H_b, W_b) float32, its zc or 0; attr_map: list of (C, H_b, W_b) float32 or None; visible: boolean mask(s) in the form of pc;
+    pixel_of: int32 i * W + j of every point's pixel or -1, in the form of pc; stats: B host rows (points inside, pixels
+    covered, points visible, points not projectable))."""
+    who = 'render_maps'
+    clouds, form, cloud, prefix, cams, hh, ww = _render_in(who, pc, camera, size)
+    B = len(clouds)
+    packed_attrs = None
+    if attrs is not None:
+        al = list(attrs) if isinstance(attrs, (list, tuple)) else ([attrs[b] for b in range(attrs.shape[0])] if torch.is_tensor(attrs) and attrs.dim() == 3 else [attrs])
+        if len(al) != B or any(not torch.is_tensor(a) or a.dim() != 2 or a.shape[1] != c.shape[1] or a.shape[0] != al[0].shape[0] for a, c in zip(al, clouds)):
+            raise _lib.HplError('%s: attrs holds (C, N_b) channels for each of the %d clouds' % (who, B))
+        packed_attrs = al[0] if B == 1 else torch.cat(al, dim=1)
+    pixel_of, winner, depth, attr_map, visible, stats = ops.render_maps(
+        cloud, cams, hh, ww, attrs=packed_attrs, footprint=footprint, rel_tol=rel_tol, abs_tol=abs_tol, near=near, prefix=prefix)
+    qq = _prefix_of([h * w for h, w in zip(hh, ww)])
+    frame = lambda x, b: x[..., qq[b]:qq[b + 1]].view(x.shape[:-1] + (hh[b], ww[b]))
+    return ([frame(winner, b) for b in range(B)], [frame(depth, b) for b in range(B)],
+            None if attr_map is None else [frame(attr_map, b) for b in range(B)],
+            _per_cloud(visible.bool(), form, prefix), _per_cloud(pixel_of, form, prefix), stats.cpu().tolist())    # the one read-back
+
+
+def flow_to_kitti_maps(pc1s, flows, Ps, sizes, baseline=0.54, footprint=0):
+    """A scene-flow result in KITTI's own form by ONE ops.maps_to_kitti call.  pc1s: a list of B <= 64 (3, n_b)
+    device clouds (or one); flows: their (3, n_b) or (n_b, 3) flows; Ps: each frame's (3, 4) P_rect_02; sizes: each frame's
+    (H, W); baseline in metres.  Every pixel takes the nearest pc1 point whose footprint covers it.
+    -> a list of (disp_0 (H, W) uint16, disp_1 (H, W) uint16, flow (H, W, 3) uint16) numpy arrays: the raw values of
+    disp_0/NNNNNN_10.png, disp_1/NNNNNN_10.png -- the disparity of pc1 + flow at the pixel of pc1 -- and flow/NNNNNN_10.png
+    (u, v, valid), which data.write_png writes as KITTI's devkit reads them; 0 where no point falls.  Only the maps are read
+    back."""
+    who = 'flow_to_kitti_maps'
+    if torch.is_tensor(pc1s):
+        pc1s, flows, Ps, sizes = [pc1s], [flows], [Ps], [sizes]
+    clouds, _ = _cloud_forms(list(pc1s), who, 'pc1s', rows3=True)
+    B = len(clouds)
+    if len(flows) != B or len(Ps) != B or len(sizes) != B:
+        raise _lib.HplError('%s: %d clouds need as many flows, P matrices and sizes' % (who, B))
+    fls = [ops._flow_view(f, int(c.shape[1]), c.device, who) for f, c in zip(flows, clouds)]
+    pc1 = clouds[0].contiguous() if B == 1 else torch.cat(clouds, dim=1)
+    pc2 = pc1 + (fls[0] if B == 1 else torch.cat(fls, dim=1))
+    hh, ww = [int(s[0]) for s in sizes], [int(s[1]) for s in sizes]
+    d1, d2, fl = ops.maps_to_kitti(pc1, pc2, Ps, hh, ww, baseline=baseline, footprint=footprint,
+                                   prefix=_prefix_of([int(c.shape[1]) for c in clouds]))
+    d1, d2, fl = d1.cpu().numpy(), d2.cpu().numpy(), fl.cpu().numpy()
+    qq = _prefix_of([h * w for h, w in zip(hh, ww)])
+    return [(d1[qq[b]:qq[b + 1]].reshape(hh[b], ww[b]), d2[qq[b]:qq[b + 1]].reshape(hh[b], ww[b]),
+             fl[qq[b]:qq[b + 1]].reshape(hh[b], ww[b], 3)) for b in range(B)]
+
+
 # ----------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(flow, pc1, pc2, k=8, w_chamfer=1.0, w_smooth=1.0):
     """The self-supervised loss of a forward's flow in ONE ops.selfsup_loss call: Chamfer distance between

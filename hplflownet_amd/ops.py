@@ -1238,6 +1238,117 @@ def png_unfilter(raw, height, stride, bpp):
     return rows[:, 1:]
 
 
+# --------------------------------------------------------------------------- maps from clouds
+_RENDER_LIMITS = '%d frames of %d pixels together are outside the limits (64 frames, M < 2^31 / 3)'
+
+
+def _render_shapes(who, n, prefix, heights, widths, footprint):
+    """(point prefix, heights, widths, pixel prefix) of B clouds with one frame each, and the footprint checked."""
+    pp = _prefix(prefix, n, who)
+    hh, ww, qq = _frames_sizes(who, heights, widths)
+    if len(hh) != len(pp) - 1:
+        raise _lib.HplError('%s: %d clouds but %d frame sizes' % (who, len(pp) - 1, len(hh)))
+    _int_in(who, 'footprint', footprint, 0, 4)
+    return pp, hh, ww, qq
+
+
+def _host_rows(who, name, rows, B, width, what):
+    """B host rows of `width` float32 values as a contiguous numpy array."""
+    import numpy as np
+    try:
+        m = np.ascontiguousarray(np.asarray([np.asarray(r, dtype=np.float32).reshape(width) for r in rows], dtype=np.float32))
+    except (TypeError, ValueError):
+        m = np.zeros((0, width), np.float32)
+    if m.shape != (B, width):
+        raise _lib.HplError('%s: %s holds %s of each of the %d frames' % (who, name, what, B))
+    return m
+
+
+def render_maps(pc, camera, heights, widths, attrs=None, footprint=0, rel_tol=0.0, abs_tol=0.0, near=1e-3, prefix=None, out=None):
+    """hpl_render_maps on the current stream: the clouds of a ragged batch splatted into one image each through a
+    z-buffer.  pc (3, N) float32 (rows may be views of a wider buffer); prefix (host sequence of B + 1 ints from 0 to N): B <= 64
+    clouds; camera: B host rows (f, cx, cy, constx, consty, constz), the cameras of the 2D metrics; heights, widths: the B image
+    sizes, image b owning pixels qprefix[b] .. qprefix[b + 1] (the running sum of heights * widths, M in all) of every per-pixel
+    output, row-major; attrs (C, N) float32, C <= 8, or None: channels that ride with the points.  A point is projectable when
+    it is finite with zc = Z + constz >= near, inside when its pixel (rintf of the projection, ties to even) lies in the image;
+    every inside point offers (zc, local index) to the (2 footprint + 1)^2 pixels around its own and a pixel keeps the nearest,
+    ties to the smaller index.
+    -> (pixel_of (N,) int32: i * width + j or -1, winner (M,) int32: the local index of the pixel's point or -1, depth (M,)
+    float32: its zc or 0, attr_map (C, M) float32 or None: its channels or 0, visible (N,) uint8: 1 when the point is inside and
+    zc <= zmin * (1 + rel_tol) + abs_tol with zmin the depth at its own pixel, stats (B, 4) int32 = (points inside, pixels
+    covered, points visible, points not projectable)).  out: a (C, M) float32 tensor with unit stride along the pixels that takes
+    attr_map; it must not overlap pc or attrs.  The same bits for a cloud alone and in any batch.  No autograd, no host
+    synchronisation, no read-back."""
+    who = 'render_maps'
+    pc, pc_ld = _soa3(pc, 'pc', who)
+    N, dev = pc.shape[1], pc.device
+    attrs, C, attr_ld = _attrs(who, attrs, N, dev)
+    pp, hh, ww, qq = _render_shapes(who, N, prefix, heights, widths, footprint)
+    B, M = len(hh), qq[-1]
+    cam = _host_rows(who, 'camera', camera, B, 6, 'the (f, cx, cy, constx, consty, constz)')
+    rel_tol, abs_tol = _scalar(who, 'rel_tol', rel_tol, zero_ok=True), _scalar(who, 'abs_tol', abs_tol, zero_ok=True)
+    near = _scalar(who, 'near', near)
+    attr_map, map_ld = None, max(M, 1)
+    if C:
+        attr_map = torch.empty((C, M), dtype=torch.float32, device=dev) if out is None else out
+        if not torch.is_tensor(attr_map) or tuple(attr_map.shape) != (C, M) or attr_map.dtype != torch.float32 or \
+                attr_map.device != dev or attr_map.requires_grad or (M > 1 and attr_map.stride(1) != 1) or \
+                (C > 1 and attr_map.stride(0) < max(M, 1)):
+            raise _lib.HplError('%s: out must be a (%d, %d) float32 tensor on %s with unit stride along the pixels' % (who, C, M, dev))
+        map_ld = max(M, 1) if C == 1 or attr_map.is_contiguous() else attr_map.stride(0)
+    elif out is not None:
+        raise _lib.HplError('%s: out takes the attribute map, and there are no attrs' % who)
+    pixel_of = torch.empty(N, dtype=torch.int32, device=dev)
+    winner = torch.empty(M, dtype=torch.int32, device=dev)
+    depth = torch.empty(M, dtype=torch.float32, device=dev)
+    visible = torch.empty(N, dtype=torch.uint8, device=dev)
+    if N == 0 and M == 0:                        # nothing to launch
+        return pixel_of, winner, depth, attr_map, visible, torch.zeros((B, 4), dtype=torch.int32, device=dev)
+    stats = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    lib = _lib.load()
+    ws, st = _room(who, dev, lib.hpl_render_workspace_bytes(B, M), _RENDER_LIMITS, B, M)
+    check(lib.hpl_render_maps(pc.data_ptr(), pc_ld, ptr(attrs), attr_ld, C, B, _c_prefix(pp),
+                              cam.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), (ctypes.c_int32 * B)(*hh),
+                              (ctypes.c_int32 * B)(*ww), _c_prefix(qq), footprint, rel_tol, abs_tol, near, pixel_of.data_ptr(),
+                              winner.data_ptr(), depth.data_ptr(), ptr(attr_map), map_ld, visible.data_ptr(), stats.data_ptr(),
+                              ws.data_ptr(), ws.numel(), st), 'hpl_render_maps')
+    return pixel_of, winner, depth, attr_map, visible, stats
+
+
+def maps_to_kitti(pc1, pc2, P, heights, widths, baseline=0.54, footprint=0, prefix=None, out=None):
+    """hpl_maps_to_kitti on the current stream: the raw values of KITTI's three scene-flow PNGs from the two
+    clouds of a ragged batch of frames -- the inverse of frames_from_kitti.  pc1 (3, N) float32: the clouds of frame 1; pc2
+    (3, N): their partners pc1 + flow, point for point; prefix (host sequence of B + 1 ints from 0 to N); P: B (3, 4) or (12,)
+    P_rect_02 matrices (host); heights, widths: the B image sizes (M pixels in all); baseline in metres.  The z-buffer of
+    render_maps over pc1 (camera (-P00, P02, P12, P03, P13, P23), near 1e-3) picks every pixel's point.
+    -> (disp1 (M,) uint16: disparity of frame 1, disp2 (M,) uint16: disparity of the partner, flow (M, 3) uint16: (u, v, 1)), 0
+    where a pixel has no point.  With footprint 0 a batch from frames_from_kitti comes back as its raw maps at every valid
+    pixel.  out: a triple of contiguous uint16 tensors of those shapes.  No autograd, no host synchronisation, no read-back."""
+    who = 'maps_to_kitti'
+    pc1, ld1 = _soa3(pc1, 'pc1', who)
+    N, dev = pc1.shape[1], pc1.device
+    pc2, ld2 = _soa3(pc2, 'pc2', who)
+    if pc2.shape[1] != N or pc2.device != dev:
+        raise _lib.HplError('%s: pc2 must be a (3, %d) tensor on %s like pc1' % (who, N, dev))
+    pp, hh, ww, qq = _render_shapes(who, N, prefix, heights, widths, footprint)
+    B, M = len(hh), qq[-1]
+    Pm = _host_rows(who, 'P', P, B, 12, 'the (3, 4) P_rect_02')
+    if out is None:
+        out = (torch.empty(M, dtype=torch.uint16, device=dev), torch.empty(M, dtype=torch.uint16, device=dev),
+               torch.empty((M, 3), dtype=torch.uint16, device=dev))
+    if not isinstance(out, (list, tuple)) or len(out) != 3 or any(
+            not torch.is_tensor(o) or o.dtype not in _U16 or o.device != dev or not o.is_contiguous() or tuple(o.shape) != s
+            for o, s in zip(out, ((M,), (M,), (M, 3)))):
+        raise _lib.HplError('%s: out must be contiguous uint16 tensors of shapes (%d,), (%d,), (%d, 3) on %s' % (who, M, M, M, dev))
+    lib = _lib.load()
+    ws, st = _room(who, dev, lib.hpl_render_workspace_bytes(B, M), _RENDER_LIMITS, B, M)
+    check(lib.hpl_maps_to_kitti(pc1.data_ptr(), ld1, pc2.data_ptr(), ld2, B, _c_prefix(pp), (ctypes.c_int32 * B)(*hh),
+                                (ctypes.c_int32 * B)(*ww), _c_prefix(qq), Pm.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                float(baseline), footprint, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
+                                ws.data_ptr(), ws.numel(), st), 'hpl_maps_to_kitti')
+    return tuple(out)
+
+
 # --------------------------------------------------------------------------- self-supervised loss
 def selfsup_loss(pc1, flow, pc2, k=8, w_chamfer=1.0, w_smooth=1.0, prefix1=None, prefix2=None, need_grad=True,
                  return_neighbors=False, out=None):

@@ -1557,6 +1557,81 @@ int hpl_outlier_filter(const float *pc, int64_t pc_ld, int batch, const int64_t 
                        float *thresh /* [batch][4] */, int32_t *stats /* [batch][4] */,
                        void *workspace, int64_t workspace_bytes, hplStream stream);
 
+/* ------------------------------------------------------------------------ *
+ * Maps from clouds (csrc/render.hip): every point projected through its frame's pinhole camera, a z-buffer that keeps the
+ * nearest point per pixel, which points the camera sees, and the raw values of KITTI's three scene-flow PNGs -- the inverse
+ * of the frames entries above.
+ * ------------------------------------------------------------------------ */
+/* BOTH ENTRIES take a ragged batch of clouds and one frame per cloud: batch 1 .. 64; prefix HOST, batch + 1 ints from 0 to N,
+ * non-decreasing (empty clouds allowed): cloud b owns the packed points prefix[b] .. prefix[b + 1], and a point's LOCAL index
+ * counts from its cloud's start.  height[b], width[b] HOST int32, each >= 0; pixel_prefix HOST, batch + 1 ints from 0 to M with
+ * pixel_prefix[b + 1] - pixel_prefix[b] == height[b] * width[b] (empty frames allowed): frame b owns those pixels of every
+ * packed per-pixel array, row-major, pixel (i, j) -- row i, column j -- at i * width + j.  N < 2^31 / 3 and M < 2^31 / 3.
+ * PROJECTION of a point (X, Y, Z) by the camera (f, cx, cy, constx, consty, constz) -- the six floats of
+ * hpl_metrics_pair.camera, the order of the reference's utils/geometry.py:project_3d_to_2d, which is what hpl_flow_metrics
+ * computes --, every operation in float32, rounded once, no contraction:
+ *   zc = Z + constz;  u = ((X * f + cx * Z) + constx) / zc;  v = ((Y * f + cy * Z) + consty) / zc
+ * The point is PROJECTABLE when X, Y, Z are finite and zc >= near_z (a NaN zc is not).  Its pixel is j = rintf(u),
+ * i = rintf(v), ties to even; it is INSIDE when it is projectable, 0 <= rintf(u) <= width - 1 and 0 <= rintf(v) <= height - 1,
+ * decided on the floats before any conversion to an integer: a huge, infinite or NaN u is outside and is never cast,
+ * rintf(-0.5f) = -0.0f is inside.
+ * Z-BUFFER: one 64-bit word per pixel, all ones at first.  Every inside point offers the key (bits(zc) << 32) | local index to
+ * every pixel of the (2 footprint + 1)^2 square around (i, j) that lies in the image (a point that is not inside offers
+ * nothing); the pixel keeps the smallest key (a 64-bit integer atomic minimum).  zc > 0, so its bits order as its value: the
+ * pixel's WINNER is the nearest point, ties going to the smaller index, whatever the order of the atomics.  A point looks at
+ * the word first and leaves the atomic out when its key cannot lower it: the word only ever decreases.
+ * Stream-ordered, launches whose number and sizes depend on the prefixes alone (clear, splat with a lane per point, then a
+ * lane per pixel -- hpl_render_maps: and a lane per point again), no copy back, no host synchronisation, no floating-point
+ * atomic (the counts are integers); no lane or workgroup waits for another.  A cloud's outputs are the same bits alone,
+ * anywhere in a batch and beside other work.
+ * workspace: DEVICE, 256-byte aligned, >= hpl_render_workspace_bytes(batch, M): the z-buffer.
+ * HPL_EINVAL before any launch (and without a device): batch out of range; a null array (those marked "or NULL" may be, and
+ * so may an array of no elements); a prefix that does not start at 0 or decreases; a negative height or width; a pixel prefix that disagrees with height * width;
+ * N or M >= 2^31 / 3; footprint outside 0 .. 4; a row stride below its count or above 2^40; misaligned arrays (4 bytes for
+ * float32 and int32, 2 for uint16); a workspace that is too small or misaligned; an output that overlaps an input, another
+ * output or the workspace (row by row: views that interleave inside one buffer are fine); and what each entry adds below. */
+/* Workspace of either entry for `batch` frames of m_total pixels together, in bytes (monotone in m_total); -1 for a batch
+ * outside 1 .. 64 or m_total outside 0 .. 2^31 / 3 - 1. */
+int64_t hpl_render_workspace_bytes(int batch, int64_t m_total);
+/* pc (3, N) float32 SoA (row stride pc_ld >= N); attr (channels, N) float32 SoA (row stride attr_ld >= N) riding along,
+ * channels 0 .. 8 (attr may be NULL with channels == 0); camera HOST [batch][6]; rel_tol, abs_tol finite and >= 0; near_z
+ * finite and > 0.  Refused as well: channels out of range, an f that is zero or not finite, a negative or non-finite
+ * tolerance, near_z <= 0 or not finite.
+ * OUTPUTS: pixel_of (N) int32: i * width + j of the point's own pixel, -1 for a point that is not inside.  winner (M) int32:
+ * the local index of the pixel's winner, -1 without one.  depth (M) float32: the winner's zc, 0 without one.  attr_map
+ * (channels, M) float32 (row stride attr_map_ld >= M) or NULL: the winner's channels, 0 without one.  visible (N) uint8: 1 when
+ * the point is inside and zc <= (zmin * (1 + rel_tol)) + abs_tol in float32, each operation (the sum 1 + rel_tol too) rounded
+ * once, zmin the depth at the point's own pixel; else 0.  A pixel's winner is always visible; with a footprint the zmin of a
+ * point's pixel may belong to a neighbour.  stats [batch][4] int32 = (points inside, pixels covered, points visible, points
+ * not projectable).
+ * Four launches: clear, splat (writes pixel_of), resolve (winner, depth, attr_map; the covered count a wave reduction and one
+ * integer atomic), visibility.  With N == 0 and M == 0 nothing is launched and nothing is written; with one of them 0 the
+ * launches of the other side still run (an empty image sees no point, an empty cloud covers no pixel). */
+int hpl_render_maps(const float *pc, int64_t pc_ld, const float *attr, int64_t attr_ld, int channels, int batch,
+                    const int64_t *prefix /* HOST */, const float *camera /* HOST [batch][6] */, const int32_t *height /* HOST */,
+                    const int32_t *width /* HOST */, const int64_t *pixel_prefix /* HOST */, int footprint, float rel_tol,
+                    float abs_tol, float near_z, int32_t *pixel_of /* (N) */, int32_t *winner /* (M) */, float *depth /* (M) */,
+                    float *attr_map /* (channels, M) or NULL */, int64_t attr_map_ld, uint8_t *visible /* (N) */,
+                    int32_t *stats /* [batch][4] */, void *workspace, int64_t workspace_bytes, hplStream stream);
+/* The raw values of KITTI's scene-flow PNGs from a frame's two clouds: pc1 (3, N) the cloud of frame 1, pc2 (3, N) its partner
+ * pc1 + flow, point for point; P HOST [batch][12]: each frame's P_rect_02 (the rules of hpl_frames_from_kitti: P01, P10, P20,
+ * P21 == 0, P00 == P11 finite and not zero); baseline finite.  The camera of frame b is (-P00, P02, P12, P03, P13, P23), near_z
+ * is 1e-3f, and the z-buffer is over pc1: a pixel's winner is the nearest pc1 point whose footprint covers it.
+ * Per pixel (i, j) with a winner, whose two points are (X1, Y1, Z1) and (X2, Y2, Z2), in float32, every operation rounded once:
+ *   fb = P00 * (float)baseline;  (px2, py2) = the projection of (X2, Y2, Z2)
+ *   r_k = rintf((fb / Z_k - 1e-5f) * 256) clamped to 1 .. 65535     (Z is the depth the back-projection calls z)
+ *   u = rintf((px2 - (float)j) * 64 + 32768) clamped to 0 .. 65535, v likewise with py2 and i;  m = 1
+ * (a NaN clamps to the lower end).  disp1, disp2 (M) uint16 take r_1, r_2 and flow [M][3] uint16 takes (u, v, m), interleaved
+ * as the flow_occ file has them.  A pixel without a winner gets 0 in all five planes; one whose winner's pc2 point is not
+ * projectable gets r_1 alone and 0 elsewhere.  With footprint 0 a frame back-projected by hpl_frames_from_kitti comes back as
+ * its raw maps: every valid pixel exactly, 0 at every other.
+ * Three launches: clear, splat, emit.  M == 0 is a no-op. */
+int hpl_maps_to_kitti(const float *pc1, int64_t pc1_ld, const float *pc2, int64_t pc2_ld, int batch,
+                      const int64_t *prefix /* HOST */, const int32_t *height /* HOST */, const int32_t *width /* HOST */,
+                      const int64_t *pixel_prefix /* HOST */, const float *P /* HOST [batch][12] */, float baseline, int footprint,
+                      uint16_t *disp1 /* (M) */, uint16_t *disp2 /* (M) */, uint16_t *flow /* [M][3] */, void *workspace,
+                      int64_t workspace_bytes, hplStream stream);
+
 #ifdef __cplusplus
 }
 #endif
