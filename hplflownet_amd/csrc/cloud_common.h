@@ -1,6 +1,8 @@
-// cloud_common.h -- what the ops over packed ragged batches of point clouds share (knn_interp, rigid_fit, motion_segment,
-// selfsup_loss, ground_fit): the limits, the search from a workgroup to its pair, the entry points' argument
-// checks, the workspace carver, the fixed-order float64 sums and the cyclic Jacobi eigen-solver.  Header only.  Every rule here is a promise about bits or about a 32-bit limit: it is stated once.
+// cloud_common.h -- what the ops over packed ragged batches of point clouds share: the limits, the search
+// from a workgroup to its group, the entry points' argument checks, the workspace carver, the fixed-order float64 sums and the
+// cyclic Jacobi eigen-solver.  Included by knn_interp, rigid_fit (and rigid_solve.h), pair_loss, fps, ground_fit, frames and
+// render, and through grid_common.h (§31) by the ops on a sorted grid.  Header only.  Every rule here is a promise about bits
+// or about a 32-bit limit: it is stated once.
 #pragma once
 #include "common.h"
 
@@ -20,6 +22,12 @@ __host__ __device__ __forceinline__ int group_of(const int32_t *prefix, int batc
 #pragma unroll
     for (int s = 32; s > 0; s >>= 1) b = (b + s < batch && prefix[b + s] <= x) ? b + s : b;
     return b;
+}
+
+// The group of workgroup blk over a workgroup prefix, in a scalar register: every lane computes the same b, and what is
+// indexed by it afterwards (the prefixes, a camera, a plane) arrives by scalar loads.
+__device__ __forceinline__ int block_group(const int32_t *bprefix, int batch, int blk) {
+    return __builtin_amdgcn_readfirstlane(group_of(bprefix, batch, blk));
 }
 
 // ---------------------------------------------------------------------------------------------- the entry points' checks

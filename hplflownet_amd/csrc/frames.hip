@@ -5,7 +5,8 @@
 // inverse of the five PNG row filters for data.read_png.
 //
 //   k_frames_count   a workgroup per FR_SPAN pixels of one frame: the valid pixels it holds (an integer)
-//   k_frames_scan    a workgroup per frame: its workgroups' counts become offsets, their sum counts[b]
+//   k_frames_scan    a workgroup per frame: its workgroups' counts become offsets, their sum counts[b] (the pattern of
+//                    DESIGN.md §35; count and emit rank quads, not rows, and keep their text)
 //   k_frames_emit    the same workgroups again: a valid pixel's two points and its index go to prefix[b] + its rank, and every
 //                    position of the frame's range at or behind counts[b] is cleared (0 in the clouds, -1 in pixel)
 //
@@ -159,10 +160,6 @@ __device__ __forceinline__ void load_quad(const FrArgs &a, int64_t i0, int p0, i
     }
 }
 
-__device__ __forceinline__ int frame_of(const FrArgs &a, int blk) {
-    return __builtin_amdgcn_readfirstlane(group_of(a.bprefix, a.batch, blk));
-}
-
 // the first packed index of lane t's quad in workgroup blk of frame b: the frame's quads start at its start rounded down to 4
 __device__ __forceinline__ int64_t quad_start(const FrArgs &a, int b, int blk, int t) {
     return (int64_t)(a.pprefix[b] & ~(FR_QUAD - 1)) + (int64_t)(blk - a.bprefix[b]) * FR_SPAN + (int64_t)t * FR_QUAD;
@@ -179,7 +176,7 @@ template <int FORM>
 __global__ void __launch_bounds__(FR_BLOCK) k_frames_count(const FrArgs a) {
     __shared__ int wt[FR_WAVES];
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = frame_of(a, blk);
+    const int b = block_group(a.bprefix, a.batch, blk);
     Quad q;
     load_quad<FORM, false>(a, quad_start(a, b, blk, t), a.pprefix[b], a.pprefix[b + 1], q);
     int n = valid_count(q);
@@ -196,6 +193,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_frames_count(const FrArgs a) {
 }
 
 __global__ void __launch_bounds__(FR_BLOCK) k_frames_scan(const FrArgs a) {
+    // (k_ground_scan's text: as one function for both, this kernel's A/B fell outside the parent's span -- rule R)
     __shared__ int sc[FR_BLOCK];
     __shared__ int carry;
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
@@ -226,7 +224,7 @@ template <int FORM>
 __global__ void __launch_bounds__(FR_BLOCK) k_frames_emit(const FrArgs a) {
     __shared__ int wt[FR_WAVES];
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = frame_of(a, blk);
+    const int b = block_group(a.bprefix, a.batch, blk);
     const int p0 = a.pprefix[b], p1 = a.pprefix[b + 1], W = a.width[b];
     const int64_t i0 = quad_start(a, b, blk, t);
     const int total = a.counts[b];

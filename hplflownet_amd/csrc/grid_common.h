@@ -1,6 +1,6 @@
 // grid_common.h -- what the ops that sort a cloud onto a uniform grid share (motion_segment, voxel_grid, icp + icp_plane,
-// normals): the 64-bit cell key and its limits, the float64 cell of a point, the sorted record, the
-// one-atomic-per-workgroup counter, and the room kept for rocPRIM's temporaries (selfsup_loss takes that alone).  Header only.  Every rule here is a promise about bits: it is stated once.
+// normals, outlier_filter): the 64-bit cell key and its limits, the float64 cell of a point, the sorted record,
+// the pick of a run's bounds, the one-atomic-per-workgroup counter, and the room kept for rocPRIM's temporaries (selfsup_loss takes that alone).  Header only.  Every rule here is a promise about bits: it is stated once.
 #pragma once
 #include "cloud_common.h"
 
@@ -66,6 +66,16 @@ __device__ __forceinline__ void grid_store(const Args &a, const int32_t *prefix,
 
 // (The search for the 9 runs of the 27 cells around a cell is not here: as one function it changed the code of k_normals and
 // of the ICP kernels and k_normals<32> was slower; match_point and k_normals keep its text, written with grid_key.  DESIGN.md §31.)
+
+// The element `which` of the 9 runs' bounds v[0 .. 8], written with compile-time indices only (k_normals, k_outlier_search).
+// The compiler turns the chain back into an index and keeps the 18 bounds of a lane in LDS (72 bytes a lane, 18 432 a
+// workgroup of 256; private slots, no barrier): not scratch.
+__device__ __forceinline__ int pick9(const int (&v)[9], int which) {
+    int r = v[0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) r = which == k ? v[k] : r;
+    return r;
+}
 
 // ---------------------------------------------------------------------------------------------- the counter
 // adds v to stats[group][slot] (4 slots a group) for every lane with v != 0; a workgroup inside one group sends one atomic.

@@ -58,15 +58,6 @@ __global__ void __launch_bounds__(NR_BLOCK) k_normals_keys(const NormalsArgs a) 
     grid_store(a, a.prefix, j, a.pc[j], a.pc[a.pc_ld + j], a.pc[2 * a.pc_ld + j]);
 }
 
-// The element `which` of v[0 .. 8], written with compile-time indices only.  The compiler turns the chain back into an index
-// and keeps the 18 bounds of a lane in LDS (72 bytes a lane, 18 432 a workgroup; private slots, no barrier): not scratch.
-__device__ __forceinline__ int pick9(const int (&v)[9], int which) {
-    int r = v[0];
-#pragma unroll
-    for (int k = 1; k < 9; ++k) r = which == k ? v[k] : r;
-    return r;
-}
-
 template <int K>
 __global__ void __launch_bounds__(NR_BLOCK) k_normals(const NormalsArgs a) {
     const int64_t s64 = (int64_t)blockIdx.x * NR_BLOCK + threadIdx.x;

@@ -73,14 +73,6 @@ __global__ void __launch_bounds__(OF_BLOCK) k_outlier_keys(const OutlierArgs a) 
     grid_store(a, a.prefix, j, a.pc[j], a.pc[a.pc_ld + j], a.pc[2 * a.pc_ld + j]);
 }
 
-// the element `which` of v[0 .. 8], written with compile-time indices only (normals.hip's pick9)
-__device__ __forceinline__ int pick9(const int (&v)[9], int which) {
-    int r = v[0];
-#pragma unroll
-    for (int k = 1; k < 9; ++k) r = which == k ? v[k] : r;
-    return r;
-}
-
 template <int K>                                     // K = 0: the count alone
 __global__ void __launch_bounds__(OF_BLOCK) k_outlier_search(const OutlierArgs a) {
     const int64_t s64 = (int64_t)blockIdx.x * OF_BLOCK + threadIdx.x;
@@ -175,11 +167,6 @@ __global__ void __launch_bounds__(OF_BLOCK) k_outlier_search(const OutlierArgs a
     }
 }
 
-// the cloud of workgroup blk, in a scalar register
-__device__ __forceinline__ int cloud_of(const OutlierArgs &a, int blk) {
-    return __builtin_amdgcn_readfirstlane(group_of(a.bprefix, a.batch, blk));
-}
-
 // (n', mu) of cloud b from its pass-1 partials: the same bits in every workgroup that asks.  All lanes call it.
 __device__ __forceinline__ void fold_mu(const OutlierArgs &a, int b, double (&run)[OF_RUNS][2], double (&tot)[2], int t) {
     fold_partials<2, OF_RUNS, OF_BLOCK>(a.part1, a.bprefix[b], a.bprefix[b + 1] - a.bprefix[b], run, tot, t);
@@ -188,7 +175,7 @@ __device__ __forceinline__ void fold_mu(const OutlierArgs &a, int b, double (&ru
 __global__ void __launch_bounds__(OF_BLOCK) k_outlier_sum1(const OutlierArgs a) {
     __shared__ double red[2][OF_BLOCK];
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int b = cloud_of(a, blk);
+    const int b = block_group(a.bprefix, a.batch, blk);
     const int p1 = a.prefix[b + 1];
     const int64_t base = (int64_t)a.prefix[b] + (int64_t)(blk - a.bprefix[b]) * OF_SPAN;
     double acc[2] = {0.0, 0.0};
@@ -209,7 +196,7 @@ __global__ void __launch_bounds__(OF_BLOCK) k_outlier_sum2(const OutlierArgs a) 
     __shared__ double run[OF_RUNS][2];
     __shared__ double tot[2];
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int b = cloud_of(a, blk);
+    const int b = block_group(a.bprefix, a.batch, blk);
     fold_mu(a, b, run, tot, t);
     const double mu = tot[0] > 0.0 ? tot[1] / tot[0] : 0.0;
     const int p1 = a.prefix[b + 1];
@@ -256,7 +243,7 @@ __device__ __forceinline__ bool keeps(const OutlierArgs &a, int64_t i, float T, 
 
 __global__ void __launch_bounds__(OF_BLOCK) k_outlier_classify(const OutlierArgs a) {
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x;
-    const int b = cloud_of(a, blk);
+    const int b = block_group(a.bprefix, a.batch, blk);
     const int p1 = a.prefix[b + 1];
     const int64_t base = (int64_t)a.prefix[b] + (int64_t)(blk - a.bprefix[b]) * OF_SPAN;
     const float T = a.thresh[(int64_t)b * 4 + 2];
@@ -276,6 +263,7 @@ __global__ void __launch_bounds__(OF_BLOCK) k_outlier_classify(const OutlierArgs
 }
 
 __global__ void __launch_bounds__(OF_BLOCK) k_outlier_scan(const OutlierArgs a) {
+    // (k_ground_scan's text with a second column, summed only: through two calls of one function it was slower -- rule R, §35)
     __shared__ int sc[OF_BLOCK], sp[OF_BLOCK];
     __shared__ int carry, carry_p;
     const int b = (int)blockIdx.x, t = (int)threadIdx.x;
@@ -309,9 +297,10 @@ __global__ void __launch_bounds__(OF_BLOCK) k_outlier_scan(const OutlierArgs a) 
 }
 
 __global__ void __launch_bounds__(OF_BLOCK) k_outlier_emit(const OutlierArgs a) {
+    // (k_ground_emit's rank: as one function for both, each call's A/B fell outside the parent's span -- rule R)
     __shared__ int wc[OF_PER_LANE * OF_WAVES];
     const int blk = (int)blockIdx.x, t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int b = cloud_of(a, blk);
+    const int b = block_group(a.bprefix, a.batch, blk);
     const int p0 = a.prefix[b], p1 = a.prefix[b + 1];
     const int64_t base = (int64_t)p0 + (int64_t)(blk - a.bprefix[b]) * OF_SPAN;
     const float T = a.thresh[(int64_t)b * 4 + 2];

@@ -64,10 +64,6 @@ __device__ __forceinline__ bool in_range(float r, int n) { return r >= 0.f && (d
 
 __device__ __forceinline__ int wave_count(bool x) { return __popcll(__ballot(x)); }
 
-__device__ __forceinline__ int group_of_block(const RdArgs &a) {
-    return __builtin_amdgcn_readfirstlane(group_of(a.bprefix, a.batch, (int)blockIdx.x));
-}
-
 __global__ void __launch_bounds__(RD_BLOCK) k_render_clear(const RdArgs a) {
     const int64_t i = (int64_t)blockIdx.x * RD_BLOCK + threadIdx.x;
     if (i < a.m_total) a.zbuf[i] = RD_EMPTY;
@@ -76,7 +72,7 @@ __global__ void __launch_bounds__(RD_BLOCK) k_render_clear(const RdArgs a) {
 
 template <bool SKIP>
 __global__ void __launch_bounds__(RD_BLOCK) k_render_splat(const RdArgs a) {
-    const int b = group_of_block(a);
+    const int b = block_group(a.bprefix, a.batch, (int)blockIdx.x);
     const int p0 = a.pprefix[b], n = a.pprefix[b + 1] - p0;
     const int local = ((int)blockIdx.x - a.bprefix[b]) * RD_BLOCK + (int)threadIdx.x;
     const bool live = local < n;
@@ -118,7 +114,7 @@ __global__ void __launch_bounds__(RD_BLOCK) k_render_splat(const RdArgs a) {
 }
 
 __global__ void __launch_bounds__(RD_BLOCK) k_render_resolve(const RdArgs a) {
-    const int b = group_of_block(a);
+    const int b = block_group(a.bprefix, a.batch, (int)blockIdx.x);
     const int q0 = a.qprefix[b], m = a.qprefix[b + 1] - q0;
     const int local = ((int)blockIdx.x - a.bprefix[b]) * RD_BLOCK + (int)threadIdx.x;
     bool covered = false;
@@ -139,7 +135,7 @@ __global__ void __launch_bounds__(RD_BLOCK) k_render_resolve(const RdArgs a) {
 }
 
 __global__ void __launch_bounds__(RD_BLOCK) k_render_visible(const RdArgs a) {
-    const int b = group_of_block(a);
+    const int b = block_group(a.bprefix, a.batch, (int)blockIdx.x);
     const int p0 = a.pprefix[b], n = a.pprefix[b + 1] - p0;
     const int local = ((int)blockIdx.x - a.bprefix[b]) * RD_BLOCK + (int)threadIdx.x;
     bool seen = false;
@@ -164,7 +160,7 @@ __device__ __forceinline__ uint16_t raw16(float x, float lo, float hi) {
 }
 
 __global__ void __launch_bounds__(RD_BLOCK) k_render_kitti(const RdArgs a) {
-    const int b = group_of_block(a);
+    const int b = block_group(a.bprefix, a.batch, (int)blockIdx.x);
     const int q0 = a.qprefix[b], m = a.qprefix[b + 1] - q0;
     const int local = ((int)blockIdx.x - a.bprefix[b]) * RD_BLOCK + (int)threadIdx.x;
     if (local >= m) return;

@@ -132,6 +132,30 @@ def test_shapes_together_start_at_every_residue():
     check(run_ft3d(fts, near=-35.0), want_ft3d(fts, -35.0))
 
 
+def test_the_scan_past_its_first_chunk():
+    """A 3 x 5 frame, then frames that own 257 and 256 workgroups: the per-frame scan (k_frames_scan) takes
+    a frame's workgroups 256 at a time, so the second frame's last workgroup gets its offset from the carry of the first chunk;
+    both large frames start off a multiple of 4 and neither at workgroup 0.  A stretch of 1424 invalid pixels in the second
+    frame covers its 256th workgroup and reaches into the 255th and the 257th."""
+    def frame_blocks(p0, p1):                                 # csrc/frames.hip: quads start at the frame's start rounded down to 4
+        return -(-(p1 - p0 // 4 * 4) // 1024) if p1 > p0 else 0
+
+    shapes = [(3, 5), (2002, 131), (2000, 131)]
+    starts = np.cumsum([0] + [h * w for h, w in shapes])
+    assert [frame_blocks(int(a), int(b)) for a, b in zip(starts, starts[1:])] == [1, 257, 256] and starts[1] % 4 == 3 and starts[2] % 4 == 1
+    lo, hi = 12 + 255 * 1024 - 300 - 15, 12 + 256 * 1024 + 100 - 15        # pixels of the second frame, from packed indices
+    rng = np.random.RandomState(78)
+    frames = [FO.kitti_raw(rng, *s) + (FO.read_P(FO.CALIB_NAMES[i]),) for i, s in enumerate(shapes)]
+    frames[1][0].reshape(-1)[lo:hi] = 0                       # disp1 = 0: not valid
+    want = want_kitti(frames)
+    px = want['pixel'][15:15 + want['counts'][1]]
+    assert not ((px >= lo) & (px < hi)).any() and (px < lo).any() and (px >= hi).any()
+    check(run_kitti(frames), want)
+    fts = [FO.ft3d_raw(rng, *s) for s in shapes]
+    fts[1][3].reshape(-1)[lo:hi] = 255                        # occluded in the first view
+    check(run_ft3d(fts, near=-35.0), want_ft3d(fts, -35.0))
+
+
 def test_all_invalid_all_valid_and_an_empty_frame_between():
     rng = np.random.RandomState(5)
     d1, d2, fl = FO.kitti_raw(rng, 9, 131)

@@ -80,6 +80,28 @@ def test_votes_of_a_large_cloud():
     same_classification(pc, [0, pc.shape[1]], got, 0.3)
 
 
+def test_the_scan_past_its_first_chunk():
+    """Clouds that own 1, 0, 255, 257 and 256 workgroups of S points in one batch.  The per-cloud scan (k_ground_scan,
+    DESIGN.md §35) takes a cloud's workgroups 256 at a time: the fourth cloud's last workgroup gets its offset from the carry of
+    the first chunk, and no cloud but the first starts at workgroup 0.  That cloud holds 501 non-finite points (kept, height
+    NaN), its lone last point among them; about half of every large cloud is ground, so the -1 fill behind the kept count
+    spans many workgroups."""
+    sizes = [1, 0, 255 * S, 256 * S + 1, 256 * S]
+    assert [-(-n // S) for n in sizes] == [1, 0, 255, 257, 256]
+    parts = [cloud(max(n, 300), 200 + i)[:, :n] for i, n in enumerate(sizes)]
+    rng = np.random.RandomState(8)
+    bad = np.append(rng.choice(256 * S, 500, replace=False), 256 * S)
+    parts[3][rng.randint(0, 3, bad.size), bad] = np.array([np.nan, np.inf, -np.inf], np.float32)[rng.randint(0, 3, bad.size)]
+    pc, prefix = np.concatenate(parts, axis=1), prefix_of(parts)
+    got = run(pc, prefix, hyps=64, refine=0, seed=13)
+    assert got['stats'][:, 0].tolist() == [0, 0, 1, 1, 1]
+    same_classification(pc, prefix, got, 0.3)
+    kept = got['stats'][:, 3].tolist()
+    assert kept[:2] == [1, 0] and all(0.3 * n < k < 0.7 * n for n, k in zip(sizes[2:], kept[2:]))
+    assert np.isnan(got['height'][prefix[3] + bad]).all() and np.isin(prefix[3] + bad, got['keep_idx']).all()
+    assert got['keep_idx'][prefix[3] + kept[3] - 1] == prefix[3] + 256 * S       # the last workgroup's one point, kept last
+
+
 def test_invalid_hypotheses_count_minus_one():
     """A draw of a non-finite point, collinear (here: repeated) draws and a failed gate each give votes -1."""
     rng = np.random.RandomState(3)

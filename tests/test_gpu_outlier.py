@@ -219,6 +219,42 @@ def test_radius_mode_at_other_radii():
         assert 0 < got['stats'][0, 1] < got['stats'][0, 0]
 
 
+def test_the_scan_past_its_first_chunk():
+    """Clouds that own 1, 0, 255, 257 and 256 workgroups of 1024 points in one batch, radius mode.  The per-cloud scan
+    (k_outlier_scan) takes a cloud's workgroups 256 at a time: the fourth cloud's last workgroup gets its
+    offset from the carry of the first chunk, and no cloud but the first starts at workgroup 0.  The points are uniform in a
+    cube of 64 m, at most one per cubic metre -- one per cell of 1.001 m, 4.2 neighbours within the radius of 1 m on average,
+    so that min_neighbors = 4 keeps about half --, with 1000 NaN points in the fourth cloud, whose participating count then
+    differs from its size and from its kept count, and its last five points in one place: the lone point of its last workgroup
+    is kept.  The all-pairs restatement is too slow here: keep_idx and stats are held to the returned mask, the mask itself to
+    the restatement in the clouds of up to 1024 points, for which a sixth cloud of 300 points, denser, with 5 NaN, is added."""
+    sizes = [1, 0, 255 * 1024, 256 * 1024 + 1, 256 * 1024]
+    assert [-(-n // 1024) for n in sizes] == [1, 0, 255, 257, 256]
+    rng = np.random.RandomState(12)
+    clouds = [rng.uniform(0, 64, (3, n)).astype(F) for n in sizes]
+    clouds[3][:, -5:] = np.array([[32.5], [32.5], [32.5]], F)
+    nans = rng.choice(sizes[3] - 5, 1000, replace=False)
+    clouds[3][rng.randint(0, 3, 1000), nans] = np.nan
+    sizes.append(300)                                         # behind them, for the restatement: a 6 m cube, 5.8 neighbours on average
+    clouds.append(rng.uniform(0, 6, (3, 300)).astype(F))
+    clouds[5][:, :5] = np.nan
+    pc, pre = np.concatenate(clouds, 1), prefix_of(sizes)
+    got = run(pc, 'radius', prefix=pre, radius=1.0, min_neighbors=4)
+    finite = ~np.isnan(pc).any(0)
+    for b, (p0, p1) in enumerate(zip(pre, pre[1:])):
+        mask = got['keep'][p0:p1].astype(bool)
+        idx, part = p0 + np.flatnonzero(mask), int(finite[p0:p1].sum())
+        assert np.array_equal(got['keep_idx'][p0:p0 + len(idx)], idx) and (got['keep_idx'][p0 + len(idx):p1] == -1).all(), b
+        assert got['stats'][b].tolist() == [part, len(idx), part - len(idx), p1 - p0 - part], b
+        assert not mask[~finite[p0:p1]].any()
+        if p1 - p0 <= 1024:
+            assert np.array_equal(mask, O.outlier_filter(clouds[b], 'radius', radius=1.0, min_neighbors=4)['keep'].astype(bool))
+        else:
+            assert 0.3 * (p1 - p0) < len(idx) < 0.8 * (p1 - p0)
+    assert 50 < got['stats'][5, 1] < 250 and got['stats'][5, 3] == 5
+    assert got['stats'][3, 3] == 1000 and got['keep'][pre[4] - 1] == 1 and got['keep_idx'][pre[3] + got['stats'][3, 1] - 1] == pre[4] - 1
+
+
 # ----------------------------------------------------------------------------- 3. what the filter is for
 @pytest.mark.parametrize('n,n_out,k,radius', [(300, 10, 8, 4.0), (1025, 25, 16, 2.0), (3000, 60, 16, 2.0), (3000, 60, 32, 2.0),
                                               (3000, 60, 8, 1.0)])
