@@ -179,9 +179,7 @@ class Trainer(object):
             else:
                 r = self.tplan.step(pc1, pc2, sf, lat)
             if r is not None:
-                self.tplan.finish()
-                if not self.tplan.adam_step(self.opt):         # one launch over the flat arrays (hpl_adam_flat)
-                    self.opt.step()
+                self._step_tail(native=True)
                 self.native_steps += 1
                 return r[1][0].clone()
             self.tplan.gflat.zero_()                 # a lattice the native backward refuses: autograd adds into the same arena
@@ -190,13 +188,23 @@ class Trainer(object):
         if self.tplan is None:
             self.opt.zero_grad(set_to_none=True)
         loss.backward()
-        if self.tplan is not None:
-            self.tplan.reduce_fallback()             # same bucket order as the ranks that ran the native program
+        self._step_tail(native=False)
+        return loss.detach()
+
+    def _step_tail(self, native):
+        """The end of every optimiser step, behind its backward: the gradients' all-reduce, then the update.  native: the native
+        program ran the backward and reduces in its own bucket order (finish); else autograd did, and with a native plan the
+        fallback reduces in that same order -- ranks that ran the native program post the same collectives -- (reduce_fallback),
+        without one through the reducer.  The update is one launch over the plan's flat arrays (hpl_adam_flat) where it has
+        them, else the optimiser's."""
+        if native:
+            self.tplan.finish()
+        elif self.tplan is not None:
+            self.tplan.reduce_fallback()
         elif self.reducer is not None:
             self.reducer()
         if self.tplan is None or not self.tplan.adam_step(self.opt):
             self.opt.step()
-        return loss.detach()
 
     def train_step_batch(self, pc1, pc2, sf, lat):
         """One optimiser step over B pairs: pc1, sf (B, 3, N1), pc2 (B, 3, N2) and their lattice of
@@ -210,9 +218,7 @@ class Trainer(object):
         if self.tplan is not None:
             r = self.tplan.step_batch(pc1, pc2, sf, lat, self.loss, self.selfsup)
             if r is not None:
-                self.tplan.finish()
-                if not self.tplan.adam_step(self.opt):
-                    self.opt.step()
+                self._step_tail(native=True)
                 self.native_steps += 1
                 return r[2]
             self.tplan.gflat.zero_()                 # the native program refuses the batch: autograd adds into the same arena
@@ -239,12 +245,7 @@ class Trainer(object):
             loss = self._pair_loss(flow, pc1[b], pc2[b], sf[b])
             (loss / B).backward()
             losses.append(loss.detach())
-        if self.tplan is not None:
-            self.tplan.reduce_fallback()
-        elif self.reducer is not None:
-            self.reducer()
-        if self.tplan is None or not self.tplan.adam_step(self.opt):
-            self.opt.step()
+        self._step_tail(native=False)
         return torch.stack(losses)
 
     def _single_lattice(self, pc1, pc2):
@@ -357,9 +358,7 @@ class Trainer(object):
         if dense_fill is not None and not dense:
             raise HplError('validate: dense_fill applies to dense=True')
         if rigid is not None:
-            if not isinstance(rigid, dict) or set(rigid) - {'iters', 'tau'}:
-                raise HplError('validate: rigid takes {\'iters\': T, \'tau\': tau}, got %r' % (rigid,))
-            rigid = {'iters': int(rigid.get('iters', 4)), 'tau': float(rigid.get('tau', 0.1))}
+            rigid = _options('rigid', rigid)
         if segment is not None:
             if rigid is None:
                 raise HplError('validate: segment applies to rigid')
@@ -369,18 +368,15 @@ class Trainer(object):
                 raise HplError('validate: objects applies to rigid with segment')
             objects = object_options(objects, rigid)
         if icp is not None:
-            if not isinstance(icp, dict) or set(icp) - {'iters', 'max_dist', 'tau', 'init', 'metric', 'normals_k', 'normals_radius'} or \
-                    icp.get('init', 'identity') not in ('identity', 'rigid') or icp.get('metric', 'point') not in ('point', 'plane') or \
-                    (icp.get('metric', 'point') != 'plane' and ('normals_k' in icp or 'normals_radius' in icp)):
-                raise HplError('validate: icp takes {\'iters\': T, \'max_dist\': d, \'tau\': tau, \'init\': \'identity\' | '
-                               '\'rigid\', \'metric\': \'point\' | \'plane\'[, \'normals_k\': K, \'normals_radius\': R with '
-                               '\'plane\']}, got %r' % (icp,))
-            icp_plane = {k: icp[k] for k in ('metric', 'normals_k', 'normals_radius') if k in icp and icp.get('metric') == 'plane'}
-            icp_init = icp.get('init', 'identity')
-            if icp_init == 'rigid' and rigid is None:
+            _known_keys('icp', icp)
+            if icp.get('metric') != 'plane' and ('normals_k' in icp or 'normals_radius' in icp):
+                raise HplError(_GROUPS['icp'].takes % (icp,))
+            if icp.get('init') == 'rigid' and rigid is None:
                 raise HplError('validate: icp init \'rigid\' starts from the rigid fit: it takes rigid')
-            icp = {'iters': int(icp.get('iters', 30)), 'max_dist': float(icp.get('max_dist', 1.0)), 'tau': float(icp.get('tau', 0.3))}
-            icp.update(icp_plane)                # (point-to-plane, DESIGN.md §29: icp_register runs ops.normals on pc2)
+            icp = _GROUPS['icp'].filled(icp, None)
+            icp_init = icp.pop('init')
+            if icp.get('metric') != 'plane':     # (point-to-plane, DESIGN.md §29: icp_register runs ops.normals on pc2)
+                icp.pop('metric', None)
         self.model.eval()
         cams = bool(getattr(data, 'has_cameras', False))
         keys = metric_keys(data)
@@ -391,45 +387,25 @@ class Trainer(object):
         rkeys = rkeys + ['piecewise_' + k for k in keys] + list(OBJECT_STATS) if objects is not None else rkeys
         self.val_batches = 0
         self.val_pairs = []
-        self._dense = None
+        forward = lambda p1, p2, lat, samples: self.model(p1, p2, lat)       # noqa: E731
         n = len(data)
         if n > 0:
-            sums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
-            stage = ops.MetricsStage(n, self.device)     # pinned descriptor rows, one per sample: no row is refilled in a call
+            nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
+            rows = _Rows(n, self.device, cams, nxt)
             if dense:
-                dsums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
-                dstage = ops.MetricsStage(n, self.device)
-                dcov = torch.zeros((n, 2), dtype=torch.float64, device=self.device)
                 from .flownet import DenseFlow
-                self._dense = DenseFlow(self.model)
-                self._dense_fill = (dense_fill, dense_k)
+                drows, dflow = _Rows(n, self.device, cams, nxt, 'dense_'), DenseFlow(self.model)
+                dcov = torch.zeros((n, 2), dtype=torch.float64, device=self.device)
             if rigid is not None:
-                rsums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
-                rstage = ops.MetricsStage(n, self.device)
-                rstats = []                              # every forward's (B, 4) fit statistics, on the device
+                rrows, rstats = _Rows(n, self.device, cams, nxt, 'rigid_'), []      # every forward's (B, 4) fit statistics, on the device
                 sstats, scounts = [], []                 # segment: every forward's (B, 4) integer counts, on the device
             if objects is not None:
-                osums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
-                ostage = ops.MetricsStage(n, self.device)
-                ocounts = []                             # every forward's (B,) counts of the rows an object fit replaced
+                orows, ocounts = _Rows(n, self.device, cams, nxt, 'piecewise_'), []  # every forward's (B,) counts of the replaced rows
             if icp is not None:
-                isums = torch.zeros((n, 8), dtype=torch.float64, device=self.device)
-                istage = ops.MetricsStage(n, self.device)
-                istats = []                              # every forward's (B, 6) registration statistics, on the device
-            nxt = [0]                                    # sample index of the next pair (groups are runs of consecutive samples)
-
-            def cameras_of(samples):
-                cameras = []
-                for s_ in samples:
-                    cam = getattr(s_, 'camera', None) if cams else None
-                    if cams and cam is None:
-                        raise HplError('validate: the reader has cameras, but sample %d came without one' % (nxt[0] + len(cameras)))
-                    cameras.append(cam)
-                return cameras
+                irows, istats = _Rows(n, self.device, cams, nxt, 'icp_'), []        # every forward's (B, 6) registration statistics
 
             def add(preds, samples, batched=None):
-                ops.flow_metrics_pairs(preds, [s_[2] for s_ in samples], [s_[0] for s_ in samples], cameras_of(samples), sums,
-                                       nxt[0], stage)
+                rows.add(preds, samples, samples)
                 if write is not None and not dense:
                     write(samples, [s_[0] for s_ in samples], list(preds))
                 fitted = None
@@ -439,82 +415,82 @@ class Trainer(object):
                     pc1, flow = batched if batched is not None else ([s_[0] for s_ in samples], list(preds))
                     if segment is None:
                         fit = rigid_refine(pc1, flow, **rigid)
-                        st, refined = fit[2], fit[3]
                     elif objects is not None:
                         from .flownet import _piecewise
                         whole = _piecewise(pc1, flow, None, rigid['iters'], rigid['tau'], objects['iters'], objects['tau'], None,
                                            segment, keep_ego=True)
                         fit = whole.fit
-                        st, refined = fit[2], fit[3]
                         sstats.append(whole.seg[3])
                         scounts.extend(int(s_[0].shape[1]) for s_ in samples)
                         ocounts.append(whole.replaced)
                     else:
                         from .flownet import segment_motion
                         fit = rigid_refine(pc1, flow, return_residual=True, **rigid)
-                        st, refined = fit[2], fit[3]
                         sstats.append(segment_motion(pc1, flow, rigid=fit, tau=rigid['tau'], **segment)[3])
                         scounts.extend(int(s_[0].shape[1]) for s_ in samples)
                     fitted = (fit[0], fit[1])
-                    rstats.append(st)            # (sample order: the groups are runs of consecutive samples)
-                    ops.flow_metrics_pairs(list(refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
-                                           cameras_of(samples), rsums, nxt[0], rstage)
+                    rstats.append(fit[2])        # (sample order: the groups are runs of consecutive samples)
+                    rrows.add(list(fit[3]), samples, samples)
                     if objects is not None:
-                        ops.flow_metrics_pairs(list(whole.refined), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
-                                               cameras_of(samples), osums, nxt[0], ostage)
+                        orows.add(list(whole.refined), samples, samples)
                 if icp is not None:
                     from .flownet import icp_register
                     res = icp_register([s_[0] for s_ in samples], [s_[1] for s_ in samples],
                                        init=fitted if icp_init == 'rigid' else None, **icp)
                     istats.append(res[2])
-                    ops.flow_metrics_pairs(list(res[3]), [s_[2] for s_ in samples], [s_[0] for s_ in samples],
-                                           cameras_of(samples), isums, nxt[0], istage)
+                    irows.add(list(res[3]), samples, samples)
                 nxt[0] += len(samples)
 
-            def add_dense(qflows, covs, samples):
+            def dense_forward(p1, p2, lat, samples):
+                """The forward through DenseFlow, the frames' full clouds queried behind it (their metrics are added before the
+                sampled ones': both write the rows from the same sample index)."""
+                flow, state = dflow.forward(p1, p2, lat)
                 fulls = [s_.dense for s_ in samples]
-                ops.flow_metrics_pairs(qflows, [f[2] for f in fulls], [f[0] for f in fulls], cameras_of(samples), dsums, nxt[0],
-                                       dstage)
+                qs = [f[0] for f in fulls]
+                qf, cov = dflow.query(state, qs if state.batch > 1 else qs[0], fill=dense_fill, k=dense_k)
+                if state.batch == 1:
+                    qf, cov = [qf], [cov]
+                drows.add(qf, fulls, samples)
                 if write is not None:
-                    write(samples, [f[0] for f in fulls], list(qflows))
-                for b, c in enumerate(covs):
+                    write(samples, qs, list(qf))
+                for b, c in enumerate(cov):
                     dcov[nxt[0] + b, 0] = c.double().mean()
                     dcov[nxt[0] + b, 1] = (c == 1).double().mean()
-            self._dense_add = add_dense if dense else None
+                return flow
             try:
-                self._validate_forwards(data, batch_size, ragged, add)
-                words = sums.cpu().numpy()               # the one read-back (it follows every launch on this stream)
+                self._validate_forwards(data, batch_size, ragged, add, dense_forward if dense else forward)
+                rows.read()                              # the one read-back (it follows every launch on this stream)
                 if dense:
-                    dwords, dcv = dsums.cpu().numpy(), dcov.cpu().numpy()
+                    drows.read()
+                    dcv = dcov.cpu().numpy()
                 if rigid is not None:
-                    rwords, rst = rsums.cpu().numpy(), torch.cat(rstats).cpu().numpy()
+                    rrows.read()
+                    rst = torch.cat(rstats).cpu().numpy()
                     if segment is not None:
                         sst = torch.cat(sstats).cpu().numpy()
                     if objects is not None:
-                        owords, oct_ = osums.cpu().numpy(), torch.cat(ocounts).cpu().numpy()
+                        orows.read()
+                        oct_ = torch.cat(ocounts).cpu().numpy()
                 if icp is not None:
-                    iwords, ist = isums.cpu().numpy(), torch.cat(istats).cpu().numpy()
+                    irows.read()
+                    ist = torch.cat(istats).cpu().numpy()
             finally:
                 torch.cuda.current_stream(self.device).synchronize()     # the stage's copies have run before it is released
-                self._dense = self._dense_add = None
-            self.val_pairs = [(i, ops.flow_metrics_fold(words[i], cams)) for i in range(n)]
-            if dense:
-                for i, v in self.val_pairs:
-                    v.update({'dense_' + k: x for k, x in ops.flow_metrics_fold(dwords[i], cams).items()})
+            self.val_pairs = [(i, rows.fold(i)) for i in range(n)]
+            for i, v in self.val_pairs:
+                if dense:
+                    v.update(drows.fold(i))
                     v['dense_coverage'], v['dense_full'] = float(dcv[i, 0]), float(dcv[i, 1])
-            if rigid is not None:
-                for i, v in self.val_pairs:
-                    v.update({'rigid_' + k: x for k, x in ops.flow_metrics_fold(rwords[i], cams).items()})
+                if rigid is not None:
+                    v.update(rrows.fold(i))
                     v.update(zip(RIGID_STATS, (float(x) for x in rst[i, 1:])))
                     if segment is not None:
                         v.update(zip(SEGMENT_STATS, segment_fold(sst[i], scounts[i])))
-            if icp is not None:
-                for i, v in self.val_pairs:
-                    v.update({'icp_' + k: x for k, x in ops.flow_metrics_fold(iwords[i], cams).items()})
+                if icp is not None:
+                    v.update(irows.fold(i))
                     v.update(zip(ICP_STATS, (float(x) for x in ist[i, 1:])))
-            if objects is not None:
-                for i, v in self.val_pairs:
-                    v.update({'piecewise_' + k: x for k, x in ops.flow_metrics_fold(owords[i], cams).items()})
+                if objects is not None:
+                    v.update(orows.fold(i))
                     v['piecewise_object_inliers'] = int(oct_[i]) / max(1, scounts[i])
         keys = keys + dkeys + rkeys
         agg = [sum(v[k] for _, v in self.val_pairs) for k in keys]      # (in sample order)
@@ -524,13 +500,14 @@ class Trainer(object):
         self.val_samples = int(tot[-1])         # over all ranks: 0 = no rank had a validation sample
         return {k: v / max(1.0, tot[-1]) for k, v in zip(keys, tot[:-1])}
 
-    def _validate_forwards(self, data, batch_size, ragged, add):
-        """The forwards of validate(): add(preds, samples) after each, preds[b] the (3, N_b) flow view of samples[b]; an equal
-        batch adds its own (pc1, flow) tensors, both (B, 3, N), as a third argument."""
+    def _validate_forwards(self, data, batch_size, ragged, add, forward):
+        """The forwards of validate(): flow = forward(p1, p2, lat, samples) -- the model's, or the dense rider's around it --, then
+        add(preds, samples), preds[b] the (3, N_b) flow view of samples[b]; an equal batch adds its own (pc1, flow) tensors, both
+        (B, 3, N), as a third argument."""
         if batch_size > 1 and ragged:
             for group in self._ragged_batches(data, batch_size):
                 p1, p2 = [g[0] for g in group], [g[1] for g in group]
-                flows = self._forward(p1, p2, self.gen.build_native_batch(p1, p2), group)      # (a list of one pair: build_native)
+                flows = forward(p1, p2, self.gen.build_native_batch(p1, p2), group)      # (a list of one pair: build_native)
                 self.val_batches += 1
                 add([f[0] for f in flows], group)
         elif batch_size > 1:
@@ -538,57 +515,25 @@ class Trainer(object):
                 p1 = torch.stack([g[0] for g in group])
                 p2 = torch.stack([g[1] for g in group])
                 lat = self.gen.build_native_batch(p1, p2) if len(group) > 1 else self.gen.build_native(p1[0], p2[0])
-                flow = self._forward(p1, p2, lat, group)
+                flow = forward(p1, p2, lat, group)
                 self.val_batches += 1
                 add(list(flow), group, (p1, flow))
         else:
             for s_, lat in self._lattices(data, list(range(len(data))), False):
-                flow = self._forward(s_[0][None], s_[1][None], lat, [s_])
+                flow = forward(s_[0][None], s_[1][None], lat, [s_])
                 self.val_batches += 1
                 add([flow[0]], [s_])
-
-    def _forward(self, p1, p2, lat, samples):
-        """model(p1, p2, lat); under validate(dense=True) through DenseFlow, the frames' full clouds queried behind it (their
-        metrics are added before the sampled ones': both write the rows from the same sample index)."""
-        if self._dense is None:
-            return self.model(p1, p2, lat)
-        flow, state = self._dense.forward(p1, p2, lat)
-        qs = [s_.dense[0] for s_ in samples]
-        fill, k = self._dense_fill
-        qf, cov = self._dense.query(state, qs if state.batch > 1 else qs[0], fill=fill, k=k)
-        if state.batch == 1:
-            qf, cov = [qf], [cov]
-        self._dense_add(qf, cov, samples)
-        return flow
 
     @staticmethod
     def _batches(data, batch_size):
         """Consecutive samples of `data` (each fetched once) in groups of <= batch_size with equal point counts."""
-        group = []
-        for i in range(len(data)):
-            s_ = data[i]
-            if group and (len(group) == batch_size or not same_counts(group[0], s_)):
-                yield group
-                group = []
-            group.append(s_)
-        if group:
-            yield group
+        return _grouped((data[i] for i in range(len(data))), _sample_counts, _equal_rule(batch_size))
 
     @staticmethod
     def _ragged_batches(data, batch_size, budget=None):
         """Consecutive samples of `data` (each fetched once, in order) in the groups of ragged_groups."""
-        budget = RAGGED_POINT_BUDGET if budget is None else budget
-        group, tot = [], (0, 0)
-        for i in range(len(data)):
-            s_ = data[i]
-            c = (int(s_[0].shape[-1]), int(s_[1].shape[-1]))
-            if group and ragged_closes(len(group), tot, c, batch_size, budget):
-                yield group
-                group, tot = [], (0, 0)
-            group.append(s_)
-            tot = (tot[0] + c[0], tot[1] + c[1])
-        if group:
-            yield group
+        return _grouped((data[i] for i in range(len(data))), _sample_counts,
+                        _ragged_rule(batch_size, RAGGED_POINT_BUDGET if budget is None else budget))
 
     # ------------------------------------------------------------------ checkpoints
     def state(self):
@@ -642,6 +587,31 @@ class Trainer(object):
         return self.min_loss
 
 
+class _Rows(object):
+    """validate()'s metric rows under a key prefix: the (n, 8) float64 sums of one flow per pair on the device, written at the
+    pairs' sample indices (`nxt`) by one hpl_flow_metrics launch per forward, and their pinned descriptor rows (one per sample:
+    no row is refilled in a call)."""
+
+    def __init__(self, n, device, cams, nxt, prefix=''):
+        self.cams, self.nxt, self.prefix = cams, nxt, prefix
+        self.sums = torch.zeros((n, 8), dtype=torch.float64, device=device)
+        self.stage = ops.MetricsStage(n, device)
+
+    def add(self, flows, clouds, samples):
+        """A forward's pairs: flows[b] measured on clouds[b] = (pc1, pc2, sf), with the camera of samples[b]."""
+        cameras = [getattr(s_, 'camera', None) if self.cams else None for s_ in samples]
+        missing = [b for b, cam in enumerate(cameras) if self.cams and cam is None]
+        if missing:
+            raise HplError('validate: the reader has cameras, but sample %d came without one' % (self.nxt[0] + missing[0]))
+        ops.flow_metrics_pairs(flows, [c[2] for c in clouds], [c[0] for c in clouds], cameras, self.sums, self.nxt[0], self.stage)
+
+    def read(self):
+        self.words = self.sums.cpu().numpy()
+
+    def fold(self, i):
+        return {self.prefix + k: x for k, x in ops.flow_metrics_fold(self.words[i], self.cams).items()}
+
+
 def selfsup_options(loss, selfsup):
     """Trainer's loss / selfsup arguments, checked: None for 'epe3d', else {'k': 8, 'w_chamfer': 1.0, 'w_smooth': 1.0} with the
     given entries in place."""
@@ -651,13 +621,11 @@ def selfsup_options(loss, selfsup):
         if selfsup is not None:
             raise HplError('Trainer: selfsup options apply to loss=\'selfsup\'')
         return None
-    selfsup = {} if selfsup is None else selfsup
-    if not isinstance(selfsup, dict) or set(selfsup) - {'k', 'w_chamfer', 'w_smooth'}:
-        raise HplError('Trainer: selfsup takes {\'k\': k, \'w_chamfer\': w, \'w_smooth\': w}, got %r' % (selfsup,))
-    o = {'k': selfsup.get('k', 8), 'w_chamfer': float(selfsup.get('w_chamfer', 1.0)), 'w_smooth': float(selfsup.get('w_smooth', 1.0))}
+    o = _options('selfsup', {} if selfsup is None else selfsup)
+    # (wider than the command line: k = 0 switches the smoothness term off, and k is taken as the int it is, never cast)
     if isinstance(o['k'], bool) or not isinstance(o['k'], int) or not 0 <= o['k'] <= 8 or \
             not 0 <= o['w_chamfer'] < float('inf') or not 0 <= o['w_smooth'] < float('inf') or (o['k'] == 0 and o['w_smooth'] != 0):
-        raise HplError('Trainer: selfsup needs k in 1 .. 8 (0 with w_smooth = 0) and finite weights >= 0, got %r' % (selfsup,))
+        raise HplError(_GROUPS['selfsup'].needs_text % (selfsup,))
     return o
 
 
@@ -667,13 +635,7 @@ SEGMENT_STATS = ('seg_objects', 'seg_moving', 'seg_noise')
 
 def segment_options(segment):
     """validate's segment argument, checked and with its defaults: {'eps': 0.5, 'dv': inf, 'min_points': 5}."""
-    if not isinstance(segment, dict) or set(segment) - {'eps', 'dv', 'min_points'}:
-        raise HplError('validate: segment takes {\'eps\': e, \'dv\': v, \'min_points\': m}, got %r' % (segment,))
-    o = {'eps': float(segment.get('eps', 0.5)), 'dv': float(segment.get('dv', float('inf'))),
-         'min_points': int(segment.get('min_points', 5))}
-    if not (0 < o['eps'] < float('inf')) or not o['dv'] > 0 or o['min_points'] < 1:
-        raise HplError('validate: segment needs eps finite and > 0, dv > 0 and min_points >= 1, got %r' % (segment,))
-    return o
+    return _options('segment', segment, ranges=True)
 
 
 #: validate(objects=...): the per-pair key beside the piecewise_<metric> keys
@@ -682,12 +644,7 @@ OBJECT_STATS = ('piecewise_object_inliers',)
 
 def object_options(objects, rigid):
     """validate's objects argument, checked and with its defaults: the rigid fit's iters and tau."""
-    if not isinstance(objects, dict) or set(objects) - {'iters', 'tau'}:
-        raise HplError('validate: objects takes {\'iters\': T, \'tau\': tau}, got %r' % (objects,))
-    o = {'iters': int(objects.get('iters', rigid['iters'])), 'tau': float(objects.get('tau', rigid['tau']))}
-    if not 0 <= o['iters'] <= 16 or not 0 < o['tau'] < float('inf'):
-        raise HplError('validate: objects needs iters in 0 .. 16 and tau finite and > 0, got %r' % (objects,))
-    return o
+    return _options('objects', objects, {'rigid': rigid}, ranges=True)
 
 
 def segment_fold(row, points):
@@ -709,30 +666,52 @@ def metric_keys(data):
     return list(ops.METRICS_3D) + (list(ops.METRICS_2D) if getattr(data, 'has_cameras', False) else [])
 
 
+# ---------------------------------------------------------------------- batches: two grouping rules, each stated once
+def _sample_counts(s_):
+    """(N1, N2) of a sample (pc1, pc2, sf), (3, N) each."""
+    return (int(s_[0].shape[-1]), int(s_[1].shape[-1]))
+
+
 def same_counts(a, b):
     """True if samples a and b ((pc1, pc2, sf), (3, N) each) have the same point counts: they can share a batch."""
-    return a[0].shape[-1] == b[0].shape[-1] and a[1].shape[-1] == b[1].shape[-1]
+    return _sample_counts(a) == _sample_counts(b)
 
 
 def point_counts(data, i):
     """(N1, N2) of sample i of a reader: its point_counts(i) if it has one (no fetch), else the shapes of data[i]."""
     f = getattr(data, 'point_counts', None)
-    if f is not None:
-        return tuple(f(i))
-    s_ = data[i]
-    return (int(s_[0].shape[-1]), int(s_[1].shape[-1]))
+    return tuple(f(i)) if f is not None else _sample_counts(data[i])
+
+
+def _grouped(items, counts, closes):
+    """Consecutive `items` in groups, each item drawn once and in order (a reader may sample randomly): closes(held, c) -- held
+    the counts of the open group's members, c = counts(item) those of the next item -- ends the group before that item."""
+    group, held = [], []
+    for x in items:
+        c = counts(x)
+        if group and closes(held, c):
+            yield group
+            group, held = [], []
+        group.append(x)
+        held.append(c)
+    if group:
+        yield group
+
+
+def _equal_rule(batch_size):
+    """Equal counts, at most batch_size."""
+    return lambda held, c: len(held) >= batch_size or held[0] != c
+
+
+def _ragged_rule(batch_size, budget):
+    """At most batch_size pairs and the point budget (ragged_closes)."""
+    return lambda held, c: ragged_closes(len(held), (sum(h[0] for h in held), sum(h[1] for h in held)), c, batch_size, budget)
 
 
 def batch_groups(counts, batch_size):
     """Index groups validate(batch_size=...) forms from per-sample point counts [(n1, n2), ...]: consecutive, equal
     counts, at most batch_size each."""
-    out = []
-    for i, c in enumerate(counts):
-        if out and len(out[-1]) < batch_size and counts[out[-1][0]] == c:
-            out[-1].append(i)
-        else:
-            out.append([i])
-    return out
+    return list(_grouped(range(len(counts)), counts.__getitem__, _equal_rule(batch_size)))
 
 
 #: points per cloud side of a ragged evaluation batch: at most the largest batch DESIGN.md §11 ran (B = 16 x N = 8 192), well
@@ -748,314 +727,325 @@ def ragged_closes(n, tot, c, batch_size, budget):
 def ragged_groups(counts, batch_size, budget=RAGGED_POINT_BUDGET):
     """Index groups validate(batch_size=..., ragged=True) forms from per-sample point counts [(n1, n2), ...]: consecutive,
     whatever the counts, at most batch_size each and at most `budget` points per cloud side (a pair above it alone)."""
-    out, tot = [], (0, 0)
-    for i, c in enumerate(counts):
-        if not out or ragged_closes(len(out[-1]), tot, c, batch_size, budget):
-            out.append([])
-            tot = (0, 0)
-        out[-1].append(i)
-        tot = (tot[0] + c[0], tot[1] + c[1])
-    return out
+    return list(_grouped(range(len(counts)), counts.__getitem__, _ragged_rule(batch_size, budget)))
+
+
+# ---------------------------------------------------------------------- the options, declared once (DESIGN.md §36)
+_INF = float('inf')
+_OMIT = object()                 # an option's value when it is not given: its key is left out of the group's dict
+_POS = (lambda v: 0 < v < _INF, 'a finite value > 0')
+_NONNEG = (lambda v: 0 <= v < _INF, 'a finite value >= 0')
+_Check = collections.namedtuple('Check', 'group bad text')       # a check of parse_args whose sentence has no regular form
+
+
+def _within(lo, hi):
+    return (lambda v: lo <= v <= hi, '%d .. %d' % (lo, hi))
+
+
+def _as_is(v):
+    return v
+
+
+class _Flag(object):
+    """One flag of the command line; _FLAGS holds them in the order of --help, a _Check at its place among its group's options.
+    With a group the flag is one of its options: `key` its name in the group's dict and in the programmatic argument, `unset`
+    its value when not given (a value, _OMIT, or a function of the groups built so far: another option's value), `takes` =
+    (range predicate, its words), `on` = (switch, its words) where the option's switch is narrower than its group's, `cast`
+    what the programmatic side applies to a value (default: the flag's type).  The keywords are add_argument's."""
+
+    def __init__(self, flag, group=None, key=None, unset=None, takes=None, on=None, cast=None, **kw):
+        self.flag, self.dest, self.group, self.key, self.unset, self.on, self.kw = \
+            flag, flag[2:].replace('-', '_'), group, key, unset, on, kw
+        self.ok, self.takes = takes or ((lambda v: True), None)
+        self.cast = cast or kw.get('type') or _as_is
+
+
+class _Group(object):
+    """A group of options; _GROUPS holds them in the order parse_args checks them.  `flag` [`value`] names the switch in the
+    options' "applies to ..." and `on` reads it; `needs` = (what the switch itself requires, its words).  as_dict: parse_args
+    leaves a.<name> = {key: value}, None with the switch off, and the programmatic side takes the same dict: `takes` is its
+    refusal of an unknown key or of a value outside an option's choices, `needs_text` that of a range, where it checks one."""
+
+    def __init__(self, name, flag, on, needs, value=None, as_dict=True, takes=None, needs_text=None):
+        self.name, self.flag, self.on, self.needs, self.as_dict, self.takes, self.needs_text = \
+            name, flag, on, needs, as_dict, takes, needs_text
+        self.applies = flag if value is None else '%s %s' % (flag, value)
+
+    def rows(self):
+        return [r for r in _FLAGS if r.group == self.name]
+
+    def options(self):
+        return [r for r in self.rows() if getattr(r, 'key', None) is not None]
+
+    def filled(self, given, built, rows=None):
+        """{key: value}: given[key] where it is given, else the option's value when unset."""
+        o = {}
+        for r in self.options() if rows is None else rows:
+            v = given[r.key] if r.key in given else r.unset(built) if callable(r.unset) else r.unset
+            if v is not _OMIT:
+                o[r.key] = r.cast(v)
+        return o
+
+
+def _known_keys(name, given):
+    g = _GROUPS[name]
+    if not isinstance(given, dict) or set(given) - {r.key for r in g.options()} or \
+            any(r.key in given and given[r.key] not in r.kw['choices'] for r in g.options() if 'choices' in r.kw):
+        raise HplError(g.takes % (given,))
+
+
+def _options(name, given, built=None, ranges=False):
+    """The programmatic side of a group: `given` checked against the declared keys, then filled and cast; ranges=True: the
+    options' ranges checked too (validate's rigid and icp leave theirs to the op wrappers)."""
+    _known_keys(name, given)
+    o = _GROUPS[name].filled(given, built)
+    if ranges and not all(r.ok(o[r.key]) for r in _GROUPS[name].options()):
+        raise HplError(_GROUPS[name].needs_text % (given,))
+    return o
+
+
+_ON_KITTI = (lambda a: a.dataset == 'KITTI', '--dataset KITTI')
+_GROUPS = collections.OrderedDict((g.name, g) for g in (
+    _Group('write', '--write-kitti', lambda a: a.write_kitti is not None, as_dict=False,
+          needs=(lambda a: a.evaluate and a.dataset == 'KITTI' and a.kitti_calib is not None,
+                 '--evaluate --dataset KITTI with --kitti-calib DIR')),
+    _Group('run', None, lambda a: False, None, as_dict=False),
+    _Group('dense', '--dense', lambda a: a.dense, as_dict=False,
+          needs=(lambda a: a.evaluate and a.dataset != 'synthetic', '--evaluate with --dataset FlyingThings3DSubset|KITTI')),
+    _Group('rigid', '--rigid-refine', lambda a: a.rigid_refine, needs=(lambda a: a.evaluate, '--evaluate'),
+          takes='validate: rigid takes {\'iters\': T, \'tau\': tau}, got %r'),
+    _Group('segment', '--segment', lambda a: a.segment, needs=(lambda a: a.evaluate and a.rigid_refine, '--evaluate --rigid-refine'),
+          takes='validate: segment takes {\'eps\': e, \'dv\': v, \'min_points\': m}, got %r',
+          needs_text='validate: segment needs eps finite and > 0, dv > 0 and min_points >= 1, got %r'),
+    _Group('objects', '--object-refine', lambda a: a.object_refine,
+          needs=(lambda a: a.evaluate and a.rigid_refine and a.segment, '--evaluate --rigid-refine --segment'),
+          takes='validate: objects takes {\'iters\': T, \'tau\': tau}, got %r',
+          needs_text='validate: objects needs iters in 0 .. 16 and tau finite and > 0, got %r'),
+    _Group('icp', '--baseline', lambda a: a.baseline == 'icp', value='icp', needs=(lambda a: a.evaluate, '--evaluate'),
+          takes='validate: icp takes {\'iters\': T, \'max_dist\': d, \'tau\': tau, \'init\': \'identity\' | \'rigid\', \'metric\': '
+                '\'point\' | \'plane\'[, \'normals_k\': K, \'normals_radius\': R with \'plane\']}, got %r'),
+    _Group('selfsup', '--loss', lambda a: a.loss == 'selfsup', value='selfsup',
+          needs=(lambda a: not a.evaluate, 'training (--evaluate reports the supervised metrics)'),
+          takes='Trainer: selfsup takes {\'k\': k, \'w_chamfer\': w, \'w_smooth\': w}, got %r',
+          needs_text='Trainer: selfsup needs k in 1 .. 8 (0 with w_smooth = 0) and finite weights >= 0, got %r'),
+    _Group('ground_fit', '--ground', lambda a: a.ground == 'plane', value='plane', needs=_ON_KITTI),
+    _Group('voxel', '--voxel', lambda a: a.voxel is not None, needs=_ON_KITTI, as_dict=False),
+    _Group('outlier_filter', '--outlier', lambda a: a.outlier is not None, needs=_ON_KITTI),
+    _Group('fps', '--fps', lambda a: a.fps is not None, needs=_ON_KITTI, as_dict=False)))
+_PLANE = (lambda a: a.icp_metric == 'plane', '--icp-metric plane')
+_STATISTICAL = (lambda a: a.outlier == 'statistical', '--outlier statistical')
+
+_FLAGS = [
+    _Flag('--arch', default='HPLFlowNet', choices=sorted(ARCHS)),
+    _Flag('--points', type=int, default=8192),
+    _Flag('--pairs', type=int, default=None,
+         help='pairs per epoch and rank: synthetic data default 8; real datasets default 0 = the whole '
+              'split (a positive value caps the shard and is logged)'),
+    _Flag('--val-pairs', type=int, default=None,
+         help='validation pairs per rank while training: synthetic default 2, real datasets default 0 = all'),
+    _Flag('--epochs', type=int, default=1),
+    _Flag('--lr', type=float, default=1e-4),
+    _Flag('--ckpt-dir', default=None),
+    _Flag('--resume', default=None),
+    _Flag('--evaluate', action='store_true'),
+    _Flag('--batch-size', type=int, default=1,
+         help='--evaluate: pairs per batched lattice build and forward (1 .. 64); consecutive pairs with equal point '
+              'counts are batched (default 1: one pair at a time)'),
+    _Flag('--ragged', action='store_true',
+         help='--evaluate --batch-size B: batch consecutive pairs whatever their point counts (<= B pairs and <= %d '
+              'points per cloud side a batch) instead of runs of equal counts' % RAGGED_POINT_BUDGET),
+    _Flag('--train-batch-size', type=int, default=None,
+         help='training: pairs per native step (1 .. 64, default 1); consecutive pairs with equal point counts share '
+              'one batched lattice build and one step, whose gradient is the mean over them.  With W ranks the global '
+              'batch is W x B pairs'),
+    _Flag('--selfsup-native', action='store_true',
+         help='--loss selfsup: run the step as the native training program (its loss and gradient from '
+              'hpl_selfsup_loss between the forward and the backward) instead of the autograd path'),
+    _Flag('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI']),
+    _Flag('--data-root', default=None),
+    _Flag('--raw-root', default=None, metavar='DIR',
+         help='--dataset KITTI|FlyingThings3DSubset: read the RAW download below DIR (disparity, optical-flow and '
+              'occlusion maps) instead of a processed tree below --data-root, back-projecting every frame on the '
+              'device as it is read (data.KITTIRaw / FlyingThings3DRaw, DESIGN.md §25); KITTI needs --kitti-calib'),
+    _Flag('--kitti-calib', default=None, metavar='DIR',
+         help='--dataset KITTI: directory of KITTI\'s calib_cam_to_cam/<frame>.txt files; the camera (P_rect_02) of each '
+              'frame gives the 2D metrics EPE2D / Acc2D (without it KITTI evaluation reports the four 3D metrics)'),
+    _Flag('--device-transforms', action='store_true',
+         help='--dataset FlyingThings3DSubset|KITTI: run the data transforms on the device (data.DeviceAugmentation for '
+              'training, data.DeviceProcessData for validation and --evaluate): the same protocol from a counter-based '
+              'random stream, so a different random sample than the host transforms (DESIGN.md §15)'),
+    _Check('run', lambda a: not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate),
+          '--batch-size takes 1 .. 64 and applies to --evaluate (training takes one pair per step)'),
+    _Check('run', lambda a: a.train_batch_size is not None and (a.evaluate or not 1 <= a.train_batch_size <= 64),
+          '--train-batch-size takes 1 .. 64 and applies to training (--evaluate batches with --batch-size)'),
+    _Check('run', lambda a: a.ragged and (not a.evaluate or a.batch_size < 2), '--ragged applies to --evaluate with --batch-size >= 2'),
+    _Check('run', lambda a: a.kitti_calib is not None and (a.dataset != 'KITTI' or not os.path.isdir(a.kitti_calib)),
+          '--kitti-calib takes an existing directory and applies to --dataset KITTI'),
+    _Check('run', lambda a: a.raw_root is not None and (a.dataset == 'synthetic' or not os.path.isdir(a.raw_root)),
+          '--raw-root takes an existing directory and applies to --dataset FlyingThings3DSubset|KITTI'),
+    _Check('run', lambda a: a.raw_root is not None and a.data_root is not None, '--raw-root and --data-root exclude each other'),
+    _Check('run', lambda a: a.raw_root is not None and a.dataset == 'KITTI' and a.kitti_calib is None,
+          '--raw-root with --dataset KITTI needs --kitti-calib DIR (every frame\'s P_rect_02)'),
+    _Check('run', lambda a: a.device_transforms and a.dataset == 'synthetic',
+          '--device-transforms applies to --dataset FlyingThings3DSubset|KITTI (synthetic pairs have no transform)'),
+    _Flag('--dense', action='store_true',
+         help='with --evaluate on FlyingThings3DSubset / KITTI: also the metrics of the flow at every valid point of each '
+              'frame, answered from the sampled forward (DenseFlow, DESIGN.md §16; not the paper\'s protocol)'),
+    _Flag('--dense-fill', 'dense', choices=['knn'],
+         help='with --dense: fill the part of each query that the sampled lattice does not cover by inverse-distance '
+              'interpolation of the sampled flow from the --dense-k nearest sampled points (DESIGN.md §17)'),
+    _Flag('--dense-k', 'dense', unset=3, takes=_within(1, 8), on=(lambda a: a.dense_fill is not None, '--dense-fill knn'), type=int,
+         metavar='K',
+         help='neighbours of --dense-fill knn (1 .. 8, default 3)'),
+    _Flag('--rigid-refine', action='store_true',
+         help='with --evaluate: behind each forward fit the rigid motion that explains most of its sampled flow (per '
+              'pair, on the device) and also report the metrics of the flow whose inliers are replaced by the rigid '
+              'flow, as rigid_<metric>, with rigid_inliers / rigid_angle_deg / rigid_trans (DESIGN.md §18; with --dense '
+              'the sampled flow only)'),
+    _Flag('--rigid-iters', 'rigid', 'iters', unset=4, takes=_within(0, 16), type=int, metavar='T',
+         help='reweighted solves of --rigid-refine after the least-squares one (0 .. 16, default 4)'),
+    _Flag('--rigid-tau', 'rigid', 'tau', unset=0.1, takes=_POS, type=float, metavar='TAU',
+         help='--rigid-refine: inlier threshold and scale of the Geman-McClure weights in metres (> 0, default 0.1)'),
+    _Flag('--segment', action='store_true',
+         help='with --evaluate --rigid-refine: group the points the rigid fit leaves unexplained (residual above '
+              '--rigid-tau) into moving objects on the device and report seg_objects / seg_moving / seg_noise '
+              '(DESIGN.md §19)'),
+    _Flag('--object-refine', action='store_true',
+         help='with --evaluate --rigid-refine --segment: fit every listed object\'s own rigid motion on the device and '
+              'also report the metrics of the piecewise-rigid flow -- ego-motion on the static points, each '
+              'object\'s motion on its points -- as piecewise_<metric>, with piecewise_object_inliers (DESIGN.md §32)'),
+    _Flag('--object-iters', 'objects', 'iters', unset=lambda built: built['rigid']['iters'], takes=_within(0, 16), type=int, metavar='T',
+         help='reweighted solves of --object-refine after the least-squares one (0 .. 16, default: --rigid-iters)'),
+    _Flag('--object-tau', 'objects', 'tau', unset=lambda built: built['rigid']['tau'], takes=_POS, type=float, metavar='TAU',
+         help='--object-refine: inlier threshold and weight scale of the object fits in metres (> 0, default: '
+              '--rigid-tau)'),
+    _Flag('--segment-eps', 'segment', 'eps', unset=0.5, takes=_POS, type=float, metavar='E',
+         help='--segment: link radius in metres (finite and > 0, default 0.5)'),
+    _Flag('--segment-dv', 'segment', 'dv', unset=_INF, takes=(lambda v: v > 0, 'a value > 0'), type=float, metavar='V',
+         help='--segment: largest flow difference of two linked points in metres (> 0, default inf: positions alone)'),
+    _Flag('--segment-min-points', 'segment', 'min_points', unset=5, takes=(lambda v: v >= 1, 'a value >= 1'), type=int, metavar='M',
+         help='--segment: points of the smallest object (>= 1, default 5)'),
+    _Flag('--baseline', default=None, choices=['icp'],
+         help='with --evaluate: behind each forward also register pc1 onto pc2 from the clouds alone by robust '
+              'point-to-point ICP on the device and report the metrics of its flow as icp_<metric>, with icp_matched / '
+              'icp_rmse / icp_angle_deg / icp_trans / icp_rounds (DESIGN.md §27)'),
+    _Flag('--icp-iters', 'icp', 'iters', unset=30, takes=_within(0, 64), type=int, metavar='T',
+         help='--baseline icp: rounds at most (0 .. 64, default 30)'),
+    _Flag('--icp-max-dist', 'icp', 'max_dist', unset=1.0, takes=_POS, type=float, metavar='D',
+         help='--baseline icp: a match is accepted within D metres (finite and > 0, default 1.0)'),
+    _Flag('--icp-tau', 'icp', 'tau', unset=0.3, takes=_POS, type=float, metavar='TAU',
+         help='--baseline icp: scale of the Geman-McClure weights in metres (finite and > 0, default 0.3)'),
+    _Flag('--icp-init', 'icp', 'init', unset='identity', choices=['identity', 'rigid'],
+         help='--baseline icp: start from identity (the papers\' baseline, independent of the model; default) or from '
+              'the fit of --rigid-refine (network + ICP)'),
+    _Check('icp', lambda a: a.icp_init == 'rigid' and not a.rigid_refine, '--icp-init rigid starts from the fit of --rigid-refine'),
+    _Flag('--icp-metric', 'icp', 'metric', unset=_OMIT, choices=['point', 'plane'],
+         help='--baseline icp: the residual of a round: point-to-point (default) or point-to-plane on the normals of '
+              'pc2, estimated on the device behind each forward (DESIGN.md §29)'),
+    _Flag('--icp-normals-k', 'icp', 'normals_k', unset=_OMIT, takes=_within(3, 32), on=_PLANE, cast=_as_is, type=int, metavar='K',
+         help='--icp-metric plane: neighbours of a normal (3 .. 32, default 16)'),
+    _Flag('--icp-normals-radius', 'icp', 'normals_radius', unset=_OMIT, takes=_POS, on=_PLANE, cast=_as_is, type=float, metavar='R',
+         help='--icp-metric plane: radius of a normal\'s neighbourhood in metres (finite and > 0, default --icp-max-dist)'),
+    _Flag('--loss', default='epe3d', choices=['epe3d', 'selfsup'],
+         help='training loss: epe3d against the ground-truth flow (default), or selfsup: Chamfer distance between the '
+              'warped cloud and pc2 plus the smoothness of the flow over the k nearest neighbours -- no flow label is '
+              'read; it runs on the autograd path (DESIGN.md §20) unless --selfsup-native is given'),
+    _Flag('--selfsup-k', 'selfsup', 'k', unset=8, takes=_within(1, 8), cast=_as_is, type=int, metavar='K',
+         help='--loss selfsup: neighbours of the smoothness graph (1 .. 8, default 8)'),
+    _Flag('--selfsup-chamfer-weight', 'selfsup', 'w_chamfer', unset=1.0, takes=_NONNEG, type=float, metavar='W',
+         help='--loss selfsup: weight of the Chamfer term (finite and >= 0, default 1)'),
+    _Flag('--selfsup-smooth-weight', 'selfsup', 'w_smooth', unset=1.0, takes=_NONNEG, type=float, metavar='W',
+         help='--loss selfsup: weight of the smoothness term (finite and >= 0, default 1)'),
+    _Check('selfsup', lambda a: a.selfsup_native and a.loss != 'selfsup', '--selfsup-native applies to --loss selfsup'),
+    _Flag('--ground', default='threshold', choices=['threshold', 'plane'],
+         help='--dataset KITTI: how the reader removes the ground: threshold -- the reference\'s rule, a correspondence '
+              'with y < -1.4 in both clouds is dropped (default) --, or plane: the same pair rule on a plane fitted to '
+              'each cloud on the device (DESIGN.md §21)'),
+    _Flag('--voxel', type=float, default=None, metavar='V',
+         help='--dataset KITTI: put every frame on a voxel grid of edge V metres (finite and > 0) on the device after '
+              'the ground removal and before the sampling of --points: one correspondence per occupied cell '
+              '(flownet.voxel_downsample, DESIGN.md §24); default off'),
+    _Check('voxel', lambda a: a.voxel is not None and not 0 < a.voxel < _INF, '--voxel takes a finite value > 0'),
+    _Flag('--voxel-mode', 'voxel', choices=['centroid', 'nearest'],
+         help='--voxel: a cell becomes the mean of its points (centroid, the default) or the point nearest to it'),
+    _Flag('--outlier', 'outlier_filter', 'mode', choices=['statistical', 'radius'],
+         help='--dataset KITTI: remove every frame\'s stray points on the device after the ground removal and before '
+              '--voxel: a correspondence is dropped when it is an outlier in either cloud (flownet.remove_outliers, '
+              'DESIGN.md §33); default off'),
+    _Flag('--outlier-k', 'outlier_filter', 'k', unset=16, takes=_within(1, 32), on=_STATISTICAL, type=int, metavar='K',
+         help='--outlier statistical: the nearest neighbours of the mean distance, 1 .. 32 (default 16)'),
+    _Flag('--outlier-radius', 'outlier_filter', 'radius', unset=1.0, takes=_POS, type=float, metavar='R',
+         help='--outlier: the search radius in metres, finite and > 0 (default 1.0)'),
+    _Flag('--outlier-std-ratio', 'outlier_filter', 'std_ratio', unset=2.0, takes=_NONNEG, on=_STATISTICAL, type=float, metavar='S',
+         help='--outlier statistical: kept up to mu + S sigma of the mean distances, finite and >= 0 (default 2.0)'),
+    _Flag('--outlier-min-neighbors', 'outlier_filter', 'min_neighbors', unset=2, takes=(lambda v: 1 <= v <= 2 ** 31 - 1, 'an int >= 1'),
+         on=(lambda a: a.outlier == 'radius', '--outlier radius'), type=int, metavar='M',
+         help='--outlier radius: kept with at least M neighbours within the radius, >= 1 (default 2)'),
+    _Flag('--fps', type=int, default=None, metavar='K',
+         help='--dataset KITTI: sample every frame to K correspondences (an int >= 1) by farthest point sampling on the '
+              'device, after the ground removal and --voxel and before the sampling of --points '
+              '(flownet.fps_sample, DESIGN.md §30); default off'),
+    _Check('fps', lambda a: a.fps is not None and a.fps < 1, '--fps takes an int >= 1'),
+    _Flag('--ground-tau', 'ground_fit', 'tau', unset=0.1, takes=_POS, type=float, metavar='TAU',
+         help='--ground plane: inlier distance of the fit in metres (finite and > 0, default 0.1)'),
+    _Flag('--ground-cut', 'ground_fit', 'cut', unset=0.3, takes=_NONNEG, type=float, metavar='C',
+         help='--ground plane: a point at most C metres above the plane is ground (finite and >= 0, default 0.3)'),
+    _Flag('--ground-hyps', 'ground_fit', 'hyps', unset=256, takes=_within(1, 1024), type=int, metavar='H',
+         help='--ground plane: three-point hypotheses per cloud (1 .. 1024, default 256)'),
+    _Flag('--ground-tilt', 'ground_fit', 'max_tilt_deg', unset=20.0, takes=(lambda v: 0 <= v < 90, '0 <= DEG < 90'), type=float,
+         metavar='DEG',
+         help='--ground plane: largest tilt of the plane\'s normal from --ground-up in degrees (0 <= DEG < 90, default 20)'),
+    _Flag('--ground-up', 'ground_fit', 'up', unset=(0.0, 1.0, 0.0),
+         takes=(lambda v: all(abs(x) < _INF for x in v) and any(v), 'three finite numbers, not all zero,'), cast=tuple, type=float, nargs=3,
+         metavar=('X', 'Y', 'Z'),
+         help='--ground plane: the up direction (finite, not zero; default 0 1 0, KITTI\'s camera frame as the reader stores it)'),
+    _Flag('--write-kitti', default=None, metavar='DIR',
+         help='--evaluate --dataset KITTI: write every evaluated frame\'s flow -- the dense one with --dense, else the '
+              'sampled one -- as KITTI\'s three 16-bit PNGs DIR/disp_0|disp_1|flow/NNNNNN_10.png (DESIGN.md §34); the '
+              'camera is the frame\'s of --kitti-calib, the size the raw frame\'s with --raw-root, else --write-size'),
+    _Flag('--write-footprint', 'write', takes=_within(0, 4), type=int, metavar='R',
+         help='--write-kitti: every point covers the (2 R + 1)^2 pixels around its own (0 .. 4, default 0)'),
+    _Flag('--write-size', 'write', takes=(lambda v: min(v) >= 1, 'two sizes >= 1'),
+         on=(lambda a: a.write_kitti is not None and a.raw_root is None, '--write-kitti without --raw-root'), type=int, nargs=2,
+         metavar=('H', 'W'),
+         help='--write-kitti without --raw-root: the size of the maps'),
+    _Check('write', lambda a: a.write_kitti is not None and a.raw_root is None and a.write_size is None,
+          '--write-kitti without --raw-root needs --write-size H W'),
+    _Flag('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal']),
+]
 
 
 def parse_args(argv=None):
-    """The command line of main(), checked (argparse exits with a message on a bad combination)."""
+    """The command line of main(), checked (argparse exits with a message on a bad combination): the flags of _FLAGS, then
+    the _GROUPS in their order -- the switch's own requirement, then each option and each hand-written check in turn --, each
+    group that becomes a dict left as a.<group>."""
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument('--arch', default='HPLFlowNet', choices=sorted(ARCHS))
-    ap.add_argument('--points', type=int, default=8192)
-    ap.add_argument('--pairs', type=int, default=None,
-                    help='pairs per epoch and rank: synthetic data default 8; real datasets default 0 = the whole '
-                         'split (a positive value caps the shard and is logged)')
-    ap.add_argument('--val-pairs', type=int, default=None,
-                    help='validation pairs per rank while training: synthetic default 2, real datasets default 0 = all')
-    ap.add_argument('--epochs', type=int, default=1)
-    ap.add_argument('--lr', type=float, default=1e-4)
-    ap.add_argument('--ckpt-dir', default=None)
-    ap.add_argument('--resume', default=None)
-    ap.add_argument('--evaluate', action='store_true')
-    ap.add_argument('--batch-size', type=int, default=1,
-                    help='--evaluate: pairs per batched lattice build and forward (1 .. 64); consecutive pairs with equal point '
-                         'counts are batched (default 1: one pair at a time)')
-    ap.add_argument('--ragged', action='store_true',
-                    help='--evaluate --batch-size B: batch consecutive pairs whatever their point counts (<= B pairs and <= %d '
-                         'points per cloud side a batch) instead of runs of equal counts' % RAGGED_POINT_BUDGET)
-    ap.add_argument('--train-batch-size', type=int, default=None,
-                    help='training: pairs per native step (1 .. 64, default 1); consecutive pairs with equal point counts share '
-                         'one batched lattice build and one step, whose gradient is the mean over them.  With W ranks the global '
-                         'batch is W x B pairs')
-    ap.add_argument('--selfsup-native', action='store_true',
-                    help='--loss selfsup: run the step as the native training program (its loss and gradient from '
-                         'hpl_selfsup_loss between the forward and the backward) instead of the autograd path')
-    ap.add_argument('--dataset', default='synthetic', choices=['synthetic', 'FlyingThings3DSubset', 'KITTI'])
-    ap.add_argument('--data-root', default=None)
-    ap.add_argument('--raw-root', default=None, metavar='DIR',
-                    help='--dataset KITTI|FlyingThings3DSubset: read the RAW download below DIR (disparity, optical-flow and '
-                         'occlusion maps) instead of a processed tree below --data-root, back-projecting every frame on the '
-                         'device as it is read (data.KITTIRaw / FlyingThings3DRaw, DESIGN.md §25); KITTI needs --kitti-calib')
-    ap.add_argument('--kitti-calib', default=None, metavar='DIR',
-                    help='--dataset KITTI: directory of KITTI\'s calib_cam_to_cam/<frame>.txt files; the camera (P_rect_02) of each '
-                         'frame gives the 2D metrics EPE2D / Acc2D (without it KITTI evaluation reports the four 3D metrics)')
-    ap.add_argument('--device-transforms', action='store_true',
-                    help='--dataset FlyingThings3DSubset|KITTI: run the data transforms on the device (data.DeviceAugmentation for '
-                         'training, data.DeviceProcessData for validation and --evaluate): the same protocol from a counter-based '
-                         'random stream, so a different random sample than the host transforms (DESIGN.md §15)')
-    ap.add_argument('--dense', action='store_true',
-                    help='with --evaluate on FlyingThings3DSubset / KITTI: also the metrics of the flow at every valid point of each '
-                         'frame, answered from the sampled forward (DenseFlow, DESIGN.md §16; not the paper\'s protocol)')
-    ap.add_argument('--dense-fill', default=None, choices=['knn'],
-                    help='with --dense: fill the part of each query that the sampled lattice does not cover by inverse-distance '
-                         'interpolation of the sampled flow from the --dense-k nearest sampled points (DESIGN.md §17)')
-    ap.add_argument('--dense-k', type=int, default=None, metavar='K', help='neighbours of --dense-fill knn (1 .. 8, default 3)')
-    ap.add_argument('--rigid-refine', action='store_true',
-                    help='with --evaluate: behind each forward fit the rigid motion that explains most of its sampled flow (per '
-                         'pair, on the device) and also report the metrics of the flow whose inliers are replaced by the rigid '
-                         'flow, as rigid_<metric>, with rigid_inliers / rigid_angle_deg / rigid_trans (DESIGN.md §18; with --dense '
-                         'the sampled flow only)')
-    ap.add_argument('--rigid-iters', type=int, default=None, metavar='T',
-                    help='reweighted solves of --rigid-refine after the least-squares one (0 .. 16, default 4)')
-    ap.add_argument('--rigid-tau', type=float, default=None, metavar='TAU',
-                    help='--rigid-refine: inlier threshold and scale of the Geman-McClure weights in metres (> 0, default 0.1)')
-    ap.add_argument('--segment', action='store_true',
-                    help='with --evaluate --rigid-refine: group the points the rigid fit leaves unexplained (residual above '
-                         '--rigid-tau) into moving objects on the device and report seg_objects / seg_moving / seg_noise '
-                         '(DESIGN.md §19)')
-    ap.add_argument('--object-refine', action='store_true',
-                    help='with --evaluate --rigid-refine --segment: fit every listed object\'s own rigid motion on the device and '
-                         'also report the metrics of the piecewise-rigid flow -- ego-motion on the static points, each '
-                         'object\'s motion on its points -- as piecewise_<metric>, with piecewise_object_inliers (DESIGN.md §32)')
-    ap.add_argument('--object-iters', type=int, default=None, metavar='T',
-                    help='reweighted solves of --object-refine after the least-squares one (0 .. 16, default: --rigid-iters)')
-    ap.add_argument('--object-tau', type=float, default=None, metavar='TAU',
-                    help='--object-refine: inlier threshold and weight scale of the object fits in metres (> 0, default: '
-                         '--rigid-tau)')
-    ap.add_argument('--segment-eps', type=float, default=None, metavar='E',
-                    help='--segment: link radius in metres (finite and > 0, default 0.5)')
-    ap.add_argument('--segment-dv', type=float, default=None, metavar='V',
-                    help='--segment: largest flow difference of two linked points in metres (> 0, default inf: positions alone)')
-    ap.add_argument('--segment-min-points', type=int, default=None, metavar='M',
-                    help='--segment: points of the smallest object (>= 1, default 5)')
-    ap.add_argument('--baseline', default=None, choices=['icp'],
-                    help='with --evaluate: behind each forward also register pc1 onto pc2 from the clouds alone by robust '
-                         'point-to-point ICP on the device and report the metrics of its flow as icp_<metric>, with icp_matched / '
-                         'icp_rmse / icp_angle_deg / icp_trans / icp_rounds (DESIGN.md §27)')
-    ap.add_argument('--icp-iters', type=int, default=None, metavar='T', help='--baseline icp: rounds at most (0 .. 64, default 30)')
-    ap.add_argument('--icp-max-dist', type=float, default=None, metavar='D',
-                    help='--baseline icp: a match is accepted within D metres (finite and > 0, default 1.0)')
-    ap.add_argument('--icp-tau', type=float, default=None, metavar='TAU',
-                    help='--baseline icp: scale of the Geman-McClure weights in metres (finite and > 0, default 0.3)')
-    ap.add_argument('--icp-init', default=None, choices=['identity', 'rigid'],
-                    help='--baseline icp: start from identity (the papers\' baseline, independent of the model; default) or from '
-                         'the fit of --rigid-refine (network + ICP)')
-    ap.add_argument('--icp-metric', default=None, choices=['point', 'plane'],
-                    help='--baseline icp: the residual of a round: point-to-point (default) or point-to-plane on the normals of '
-                         'pc2, estimated on the device behind each forward (DESIGN.md §29)')
-    ap.add_argument('--icp-normals-k', type=int, default=None, metavar='K',
-                    help='--icp-metric plane: neighbours of a normal (3 .. 32, default 16)')
-    ap.add_argument('--icp-normals-radius', type=float, default=None, metavar='R',
-                    help='--icp-metric plane: radius of a normal\'s neighbourhood in metres (finite and > 0, default --icp-max-dist)')
-    ap.add_argument('--loss', default='epe3d', choices=['epe3d', 'selfsup'],
-                    help='training loss: epe3d against the ground-truth flow (default), or selfsup: Chamfer distance between the '
-                         'warped cloud and pc2 plus the smoothness of the flow over the k nearest neighbours -- no flow label is '
-                         'read; it runs on the autograd path (DESIGN.md §20) unless --selfsup-native is given')
-    ap.add_argument('--selfsup-k', type=int, default=None, metavar='K',
-                    help='--loss selfsup: neighbours of the smoothness graph (1 .. 8, default 8)')
-    ap.add_argument('--selfsup-chamfer-weight', type=float, default=None, metavar='W',
-                    help='--loss selfsup: weight of the Chamfer term (finite and >= 0, default 1)')
-    ap.add_argument('--selfsup-smooth-weight', type=float, default=None, metavar='W',
-                    help='--loss selfsup: weight of the smoothness term (finite and >= 0, default 1)')
-    ap.add_argument('--ground', default='threshold', choices=['threshold', 'plane'],
-                    help='--dataset KITTI: how the reader removes the ground: threshold -- the reference\'s rule, a correspondence '
-                         'with y < -1.4 in both clouds is dropped (default) --, or plane: the same pair rule on a plane fitted to '
-                         'each cloud on the device (DESIGN.md §21)')
-    ap.add_argument('--voxel', type=float, default=None, metavar='V',
-                    help='--dataset KITTI: put every frame on a voxel grid of edge V metres (finite and > 0) on the device after '
-                         'the ground removal and before the sampling of --points: one correspondence per occupied cell '
-                         '(flownet.voxel_downsample, DESIGN.md §24); default off')
-    ap.add_argument('--voxel-mode', default=None, choices=['centroid', 'nearest'],
-                    help='--voxel: a cell becomes the mean of its points (centroid, the default) or the point nearest to it')
-    ap.add_argument('--outlier', default=None, choices=['statistical', 'radius'],
-                    help='--dataset KITTI: remove every frame\'s stray points on the device after the ground removal and before '
-                         '--voxel: a correspondence is dropped when it is an outlier in either cloud (flownet.remove_outliers, '
-                         'DESIGN.md §33); default off')
-    ap.add_argument('--outlier-k', type=int, default=None, metavar='K',
-                    help='--outlier statistical: the nearest neighbours of the mean distance, 1 .. 32 (default 16)')
-    ap.add_argument('--outlier-radius', type=float, default=None, metavar='R',
-                    help='--outlier: the search radius in metres, finite and > 0 (default 1.0)')
-    ap.add_argument('--outlier-std-ratio', type=float, default=None, metavar='S',
-                    help='--outlier statistical: kept up to mu + S sigma of the mean distances, finite and >= 0 (default 2.0)')
-    ap.add_argument('--outlier-min-neighbors', type=int, default=None, metavar='M',
-                    help='--outlier radius: kept with at least M neighbours within the radius, >= 1 (default 2)')
-    ap.add_argument('--fps', type=int, default=None, metavar='K',
-                    help='--dataset KITTI: sample every frame to K correspondences (an int >= 1) by farthest point sampling on the '
-                         'device, after the ground removal and --voxel and before the sampling of --points '
-                         '(flownet.fps_sample, DESIGN.md §30); default off')
-    ap.add_argument('--ground-tau', type=float, default=None, metavar='TAU',
-                    help='--ground plane: inlier distance of the fit in metres (finite and > 0, default 0.1)')
-    ap.add_argument('--ground-cut', type=float, default=None, metavar='C',
-                    help='--ground plane: a point at most C metres above the plane is ground (finite and >= 0, default 0.3)')
-    ap.add_argument('--ground-hyps', type=int, default=None, metavar='H',
-                    help='--ground plane: three-point hypotheses per cloud (1 .. 1024, default 256)')
-    ap.add_argument('--ground-tilt', type=float, default=None, metavar='DEG',
-                    help='--ground plane: largest tilt of the plane\'s normal from --ground-up in degrees (0 <= DEG < 90, default 20)')
-    ap.add_argument('--ground-up', type=float, nargs=3, default=None, metavar=('X', 'Y', 'Z'),
-                    help='--ground plane: the up direction (finite, not zero; default 0 1 0, KITTI\'s camera frame as the reader stores it)')
-    ap.add_argument('--write-kitti', default=None, metavar='DIR',
-                    help='--evaluate --dataset KITTI: write every evaluated frame\'s flow -- the dense one with --dense, else the '
-                         'sampled one -- as KITTI\'s three 16-bit PNGs DIR/disp_0|disp_1|flow/NNNNNN_10.png (DESIGN.md §34); the '
-                         'camera is the frame\'s of --kitti-calib, the size the raw frame\'s with --raw-root, else --write-size')
-    ap.add_argument('--write-footprint', type=int, default=None, metavar='R',
-                    help='--write-kitti: every point covers the (2 R + 1)^2 pixels around its own (0 .. 4, default 0)')
-    ap.add_argument('--write-size', type=int, nargs=2, default=None, metavar=('H', 'W'),
-                    help='--write-kitti without --raw-root: the size of the maps')
-    ap.add_argument('--init', default='hash', choices=['hash', 'xavier', 'normal', 'kaiming', 'orthogonal'])
+    for r in _FLAGS:
+        if isinstance(r, _Flag):
+            ap.add_argument(r.flag, **r.kw)
     a = ap.parse_args(argv)
-    if a.write_kitti is not None and (not a.evaluate or a.dataset != 'KITTI' or a.kitti_calib is None):
-        ap.error('--write-kitti applies to --evaluate --dataset KITTI with --kitti-calib DIR')
-    if a.write_footprint is not None and (a.write_kitti is None or not 0 <= a.write_footprint <= 4):
-        ap.error('--write-footprint takes 0 .. 4 and applies to --write-kitti')
-    if a.write_size is not None and (a.write_kitti is None or a.raw_root is not None or min(a.write_size) < 1):
-        ap.error('--write-size takes two sizes >= 1 and applies to --write-kitti without --raw-root')
-    if a.write_kitti is not None and a.raw_root is None and a.write_size is None:
-        ap.error('--write-kitti without --raw-root needs --write-size H W')
-    if not 1 <= a.batch_size <= 64 or (a.batch_size > 1 and not a.evaluate):
-        ap.error('--batch-size takes 1 .. 64 and applies to --evaluate (training takes one pair per step)')
-    if a.train_batch_size is not None and (a.evaluate or not 1 <= a.train_batch_size <= 64):
-        ap.error('--train-batch-size takes 1 .. 64 and applies to training (--evaluate batches with --batch-size)')
-    if a.ragged and (not a.evaluate or a.batch_size < 2):
-        ap.error('--ragged applies to --evaluate with --batch-size >= 2')
-    if a.kitti_calib is not None and (a.dataset != 'KITTI' or not os.path.isdir(a.kitti_calib)):
-        ap.error('--kitti-calib takes an existing directory and applies to --dataset KITTI')
-    if a.raw_root is not None:
-        if a.dataset == 'synthetic' or not os.path.isdir(a.raw_root):
-            ap.error('--raw-root takes an existing directory and applies to --dataset FlyingThings3DSubset|KITTI')
-        if a.data_root is not None:
-            ap.error('--raw-root and --data-root exclude each other')
-        if a.dataset == 'KITTI' and a.kitti_calib is None:
-            ap.error('--raw-root with --dataset KITTI needs --kitti-calib DIR (every frame\'s P_rect_02)')
-    if a.device_transforms and a.dataset == 'synthetic':
-        ap.error('--device-transforms applies to --dataset FlyingThings3DSubset|KITTI (synthetic pairs have no transform)')
-    if a.dense and (not a.evaluate or a.dataset == 'synthetic'):
-        ap.error('--dense applies to --evaluate with --dataset FlyingThings3DSubset|KITTI')
-    if a.dense_fill is not None and not a.dense:
-        ap.error('--dense-fill applies to --dense')
-    if a.dense_k is not None and (a.dense_fill is None or not 1 <= a.dense_k <= 8):
-        ap.error('--dense-k takes 1 .. 8 and applies to --dense-fill knn')
-    a.dense_k = a.dense_k or 3
-    if a.rigid_refine and not a.evaluate:
-        ap.error('--rigid-refine applies to --evaluate')
-    if a.rigid_iters is not None and (not a.rigid_refine or not 0 <= a.rigid_iters <= 16):
-        ap.error('--rigid-iters takes 0 .. 16 and applies to --rigid-refine')
-    if a.rigid_tau is not None and (not a.rigid_refine or not 0 < a.rigid_tau < float('inf')):
-        ap.error('--rigid-tau takes a finite value > 0 and applies to --rigid-refine')
-    a.rigid = {'iters': 4 if a.rigid_iters is None else a.rigid_iters,
-               'tau': 0.1 if a.rigid_tau is None else a.rigid_tau} if a.rigid_refine else None
-    if a.segment and not (a.evaluate and a.rigid_refine):
-        ap.error('--segment applies to --evaluate --rigid-refine')
-    if a.segment_eps is not None and (not a.segment or not 0 < a.segment_eps < float('inf')):
-        ap.error('--segment-eps takes a finite value > 0 and applies to --segment')
-    if a.segment_dv is not None and (not a.segment or not a.segment_dv > 0):
-        ap.error('--segment-dv takes a value > 0 and applies to --segment')
-    if a.segment_min_points is not None and (not a.segment or a.segment_min_points < 1):
-        ap.error('--segment-min-points takes a value >= 1 and applies to --segment')
-    a.segment = {'eps': 0.5 if a.segment_eps is None else a.segment_eps,
-                 'dv': float('inf') if a.segment_dv is None else a.segment_dv,
-                 'min_points': 5 if a.segment_min_points is None else a.segment_min_points} if a.segment else None
-    if a.object_refine and not (a.evaluate and a.rigid_refine and a.segment):
-        ap.error('--object-refine applies to --evaluate --rigid-refine --segment')
-    if a.object_iters is not None and (not a.object_refine or not 0 <= a.object_iters <= 16):
-        ap.error('--object-iters takes 0 .. 16 and applies to --object-refine')
-    if a.object_tau is not None and (not a.object_refine or not 0 < a.object_tau < float('inf')):
-        ap.error('--object-tau takes a finite value > 0 and applies to --object-refine')
-    a.objects = {'iters': a.rigid['iters'] if a.object_iters is None else a.object_iters,
-                 'tau': a.rigid['tau'] if a.object_tau is None else a.object_tau} if a.object_refine else None
-    on = a.baseline == 'icp'
-    if on and not a.evaluate:
-        ap.error('--baseline applies to --evaluate')
-    if a.icp_iters is not None and (not on or not 0 <= a.icp_iters <= 64):
-        ap.error('--icp-iters takes 0 .. 64 and applies to --baseline icp')
-    if a.icp_max_dist is not None and (not on or not 0 < a.icp_max_dist < float('inf')):
-        ap.error('--icp-max-dist takes a finite value > 0 and applies to --baseline icp')
-    if a.icp_tau is not None and (not on or not 0 < a.icp_tau < float('inf')):
-        ap.error('--icp-tau takes a finite value > 0 and applies to --baseline icp')
-    if a.icp_init is not None and not on:
-        ap.error('--icp-init applies to --baseline icp')
-    if a.icp_init == 'rigid' and not a.rigid_refine:
-        ap.error('--icp-init rigid starts from the fit of --rigid-refine')
-    if a.icp_metric is not None and not on:
-        ap.error('--icp-metric applies to --baseline icp')
-    if a.icp_normals_k is not None and (a.icp_metric != 'plane' or not 3 <= a.icp_normals_k <= 32):
-        ap.error('--icp-normals-k takes 3 .. 32 and applies to --icp-metric plane')
-    if a.icp_normals_radius is not None and (a.icp_metric != 'plane' or not 0 < a.icp_normals_radius < float('inf')):
-        ap.error('--icp-normals-radius takes a finite value > 0 and applies to --icp-metric plane')
-    a.icp = {'iters': 30 if a.icp_iters is None else a.icp_iters,
-             'max_dist': 1.0 if a.icp_max_dist is None else a.icp_max_dist,
-             'tau': 0.3 if a.icp_tau is None else a.icp_tau,
-             'init': a.icp_init or 'identity'} if on else None
-    if on and a.icp_metric is not None:          # (recorded in the configuration the run prints; the report keys do not change)
-        a.icp['metric'] = a.icp_metric
-        if a.icp_normals_k is not None:
-            a.icp['normals_k'] = a.icp_normals_k
-        if a.icp_normals_radius is not None:
-            a.icp['normals_radius'] = a.icp_normals_radius
-    on = a.loss == 'selfsup'
-    if on and a.evaluate:
-        ap.error('--loss applies to training (--evaluate reports the supervised metrics)')
-    if a.selfsup_k is not None and (not on or not 1 <= a.selfsup_k <= 8):
-        ap.error('--selfsup-k takes 1 .. 8 and applies to --loss selfsup')
-    for v, name in ((a.selfsup_chamfer_weight, '--selfsup-chamfer-weight'), (a.selfsup_smooth_weight, '--selfsup-smooth-weight')):
-        if v is not None and (not on or not 0 <= v < float('inf')):
-            ap.error('%s takes a finite value >= 0 and applies to --loss selfsup' % name)
-    if a.selfsup_native and not on:
-        ap.error('--selfsup-native applies to --loss selfsup')
-    a.selfsup = {'k': 8 if a.selfsup_k is None else a.selfsup_k,
-                 'w_chamfer': 1.0 if a.selfsup_chamfer_weight is None else a.selfsup_chamfer_weight,
-                 'w_smooth': 1.0 if a.selfsup_smooth_weight is None else a.selfsup_smooth_weight} if on else None
-    on = a.ground == 'plane'
-    if on and a.dataset != 'KITTI':
-        ap.error('--ground applies to --dataset KITTI')
-    if a.ground_tau is not None and (not on or not 0 < a.ground_tau < float('inf')):
-        ap.error('--ground-tau takes a finite value > 0 and applies to --ground plane')
-    if a.ground_cut is not None and (not on or not 0 <= a.ground_cut < float('inf')):
-        ap.error('--ground-cut takes a finite value >= 0 and applies to --ground plane')
-    if a.ground_hyps is not None and (not on or not 1 <= a.ground_hyps <= 1024):
-        ap.error('--ground-hyps takes 1 .. 1024 and applies to --ground plane')
-    if a.ground_tilt is not None and (not on or not 0 <= a.ground_tilt < 90):
-        ap.error('--ground-tilt takes 0 <= DEG < 90 and applies to --ground plane')
-    if a.ground_up is not None and (not on or not all(abs(x) < float('inf') for x in a.ground_up) or not any(a.ground_up)):
-        ap.error('--ground-up takes three finite numbers, not all zero, and applies to --ground plane')
-    a.ground_fit = {'tau': 0.1 if a.ground_tau is None else a.ground_tau,
-                    'cut': 0.3 if a.ground_cut is None else a.ground_cut,
-                    'hyps': 256 if a.ground_hyps is None else a.ground_hyps,
-                    'max_tilt_deg': 20.0 if a.ground_tilt is None else a.ground_tilt,
-                    'up': (0.0, 1.0, 0.0) if a.ground_up is None else tuple(a.ground_up)} if on else None
-    if a.voxel is not None and a.dataset != 'KITTI':
-        ap.error('--voxel applies to --dataset KITTI')
-    if a.voxel is not None and not 0 < a.voxel < float('inf'):
-        ap.error('--voxel takes a finite value > 0')
-    if a.voxel_mode is not None and a.voxel is None:
-        ap.error('--voxel-mode applies to --voxel')
-    if a.outlier is not None and a.dataset != 'KITTI':
-        ap.error('--outlier applies to --dataset KITTI')
-    if a.outlier_k is not None and (a.outlier != 'statistical' or not 1 <= a.outlier_k <= 32):
-        ap.error('--outlier-k takes 1 .. 32 and applies to --outlier statistical')
-    if a.outlier_radius is not None and (a.outlier is None or not 0 < a.outlier_radius < float('inf')):
-        ap.error('--outlier-radius takes a finite value > 0 and applies to --outlier')
-    if a.outlier_std_ratio is not None and (a.outlier != 'statistical' or not 0 <= a.outlier_std_ratio < float('inf')):
-        ap.error('--outlier-std-ratio takes a finite value >= 0 and applies to --outlier statistical')
-    if a.outlier_min_neighbors is not None and (a.outlier != 'radius' or not 1 <= a.outlier_min_neighbors <= 2 ** 31 - 1):
-        ap.error('--outlier-min-neighbors takes an int >= 1 and applies to --outlier radius')
-    a.outlier_filter = None
-    if a.outlier is not None:
-        a.outlier_filter = {'mode': a.outlier, 'radius': 1.0 if a.outlier_radius is None else a.outlier_radius}
-        if a.outlier == 'statistical':
-            a.outlier_filter.update(k=16 if a.outlier_k is None else a.outlier_k,
-                                    std_ratio=2.0 if a.outlier_std_ratio is None else a.outlier_std_ratio)
-        else:
-            a.outlier_filter.update(min_neighbors=2 if a.outlier_min_neighbors is None else a.outlier_min_neighbors)
-    if a.fps is not None and a.dataset != 'KITTI':
-        ap.error('--fps applies to --dataset KITTI')
-    if a.fps is not None and a.fps < 1:
-        ap.error('--fps takes an int >= 1')
+    built = {}
+    for g in _GROUPS.values():
+        on = g.on(a)
+        if on and not g.needs[0](a):
+            ap.error('%s applies to %s' % (g.flag, g.needs[1]))
+        for r in g.rows():
+            if isinstance(r, _Check):
+                if r.bad(a):
+                    ap.error(r.text)
+                continue
+            v = getattr(a, r.dest)
+            r_on, words = (on, g.applies) if r.on is None else (r.on[0](a), r.on[1])
+            if v is not None and not (r_on and r.ok(v)):
+                ap.error('%s takes %s and applies to %s' % (r.flag, r.takes, words) if r.takes else '%s applies to %s' % (r.flag, words))
+            if not g.as_dict and v is None:
+                setattr(a, r.dest, r.unset)
+        if g.as_dict:       # (an option whose own switch is off is no key of the dict: --outlier-k under --outlier radius)
+            given = {r.key: getattr(a, r.dest) for r in g.options() if getattr(a, r.dest) is not None}
+            built[g.name] = g.filled(given, built, [r for r in g.options() if r.on is None or r.on[0](a)]) if on else None
+            setattr(a, g.name, built[g.name])
+    if a.outlier_filter:                # (the run's report lists the filter's values in this order)
+        a.outlier_filter = {k: a.outlier_filter[k] for k in ('mode', 'radius', 'k', 'std_ratio', 'min_neighbors') if k in a.outlier_filter}
     a.train_batch_size = a.train_batch_size or 1
     if a.pairs is None:
         a.pairs = 8 if a.dataset == 'synthetic' else 0

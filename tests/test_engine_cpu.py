@@ -3,10 +3,25 @@ checkpoint dict layout / file naming of the reference (main.py:183-189, main_uti
 import os
 
 import numpy as np
+import pytest
 import torch
 
+import engine_refusals
 from hplflownet_amd import engine
 from hplflownet_amd.flownet import HPLFlowNetShallow, load_reference_checkpoint
+
+
+@pytest.mark.parametrize('argv, text', engine_refusals.ARGV, ids=lambda x: ' '.join(x) if isinstance(x, list) else None)
+def test_parse_args_refusal_texts(argv, text, tmp_path):
+    """Every error site of parse_args says what it said before the option table: argparse's exit 2 and the text."""
+    assert engine_refusals.argv_verdict(engine, argv, str(tmp_path)) == ('SystemExit 2', text)
+
+
+@pytest.mark.parametrize('row', engine_refusals.CALLS, ids=lambda r: '%s %r %r' % r[:3])
+def test_option_call_refusal_texts(row):
+    """The programmatic side of the same options: an HplError with its text, or a range left to the op wrappers is taken."""
+    name, args, kw, text = row
+    assert engine_refusals.call_verdict(engine, name, args, kw) == (('taken', '') if text is None else ('HplError', text))
 
 
 def test_metrics_match_reference_formulas():
